@@ -12,8 +12,14 @@ input resident in HBM.  Workloads (BASELINE.json configs):
   C2: 256 channels x 48000 samples, filter.c + receiver.c only (no protodec).
   C5: 16384 channels x 192000 samples at 192 kHz (144 taps, pllinc 0x10000/20).
 
-`--config` picks the one the headline line is about; a default single-GPU run also
+`--config` picks the one the headline line is about; a `--full` single-GPU run also
 measures the other two briefly and reports them under "other_configs".
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+line (`ms_per_step` = milliseconds of one timed step).  Everything else it can measure -- the
+CPU baseline, C2 / C5, the exact-FIR chain, per-kernel timings, PMC traffic, the message-layer
+legs -- runs with `--full`.  `--dump-outputs DIR` writes what the last timed step computed
+(the frame records a caller drains, the receivers' counters) as DIR/<name>.npy.
 
 Channels shard embarrassingly over GPUs (weak scaling, no data-path collective):
 `--gpus N` started plainly runs ONE process that drives every device through the library's
@@ -22,9 +28,9 @@ node object (gnuais_node_*: a batch and a host thread per device, merged results
 nothing shared but a start/stop barrier; launched by torch.distributed.run, the ranks it
 created are used and RCCL provides the barrier and the max-over-ranks time.
 
-Rank 0 prints ONE compact JSON line (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, the other
-configs' ms / frac / bound) as the LAST line of stdout; every other measurement (per-kernel VALU tables, PMC
-traffic detail, stage masks, the texts that say what each figure is) goes to bench_detail.json.
+Rank 0 prints ONE compact JSON line (< 4 KB: the contract's keys and, with `--full`, `roofline`, `cpu_baseline`,
+the other configs' ms / frac / bound) as the LAST line of stdout; with `--full` every other measurement (per-kernel
+VALU tables, PMC traffic detail, stage masks, the texts that say what each figure is) goes to bench_detail.json.
 """
 import argparse
 import json
@@ -188,9 +194,34 @@ class DistSync:
         return (t, m, s, ranks) if self.rank == 0 else None
 
 
+DUMP_FRAMES = 131072           # --dump-outputs: at most this many frame records (a fixed, seeded sample beyond): < 40 MB
+
+
+def dump_outputs(path, frames, counters):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the frame records it drains and
+    the receivers' counters -- one float .npy per field (every integer exact: float32 below 2**24, float64 above)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(frames)
+    idx = np.arange(n)
+    if n > DUMP_FRAMES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_FRAMES, replace=False))
+    fr = frames[idx]
+    arrays = {"n_frames": np.array([n], dtype=np.float64),
+              "frame_index": idx.astype(np.float64),
+              "frame_channel": fr["channel"].astype(np.float64),
+              "frame_end_bit": fr["end_bit"].astype(np.float64),
+              "frame_payload": fr["payload"].astype(np.float32),
+              "frame_flags": fr["flags"].astype(np.float32),
+              "frame_nbits": fr["nbits"].astype(np.float32),
+              "counters": np.stack([counters[k] for k in counters.dtype.names], axis=1).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def measure(cfg, args, local, rank, sync, steps, warmup, isolated=True, post=False, keep_input=False, kernel_leg=True,
-            options=None, uncalibrated=False):
-    """One workload on this rank's GPU.  Returns a dict of raw measurements."""
+            options=None, uncalibrated=False, legs=True, dump_dir=None):
+    """One workload on this rank's GPU.  Returns a dict of raw measurements.  legs=False: the timed region alone (a
+    plain run), no kernel-timing leg behind it; dump_dir: the last timed step's outputs go there (dump_outputs)."""
     import torch
     from gnuais_amd import ReceiverBatch, params, synth, tile_channels
 
@@ -239,13 +270,18 @@ def measure(cfg, args, local, rank, sync, steps, warmup, isolated=True, post=Fal
     sync.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if dump_dir else steps):
         step()
+    if dump_dir:                # the last timed step keeps its frames for the dump
+        b.run(x, stream=stream, sync=False)
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0
     sync.barrier()
     dt = time.perf_counter() - t0
     rx1 = b.total_received()
+    if dump_dir:
+        b.sync()
+        dump_outputs(dump_dir, b.drain_frames(), b.counters())
     iso = None
     if isolated:        # one call at a time, nothing overlapping: context only (BEHIND the region: its syncs leave the chip idle)
         b.set_timing(True)
@@ -264,7 +300,7 @@ def measure(cfg, args, local, rank, sync, steps, warmup, isolated=True, post=Fal
            "call_latency_isolated_ms": iso_total if isolated else None}
     # `kernel_ms`: the same loop again, long enough for a stable mean -- a 20-step region sampled on every 4th call gives
     # five samples per kernel, and which of two stages of nearly equal length "dominates" then flips from run to run
-    leg = KERNEL_LEG_CALLS if kernel_leg else 12
+    leg = (KERNEL_LEG_CALLS if kernel_leg else 12) if legs else 0
     if leg:
         b.set_timing(True)
         b.set_option("timing_stride", KERNEL_LEG_STRIDE)
@@ -530,8 +566,8 @@ def pmc_traffic(args, config, device=0):
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {"error": "rocprofv3 not found"}
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--no-cpu", "--no-others", "--no-e2e",
-             "--no-traffic", "--no-kernel-leg", "--steps", "6", "--warmup", "1", "--base", str(args.base)]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--full", "--no-cpu", "--no-others",
+             "--no-e2e", "--no-traffic", "--no-kernel-leg", "--steps", "6", "--warmup", "1", "--base", str(args.base)]
     short = (("fir_sign", "fir_slice"), ("fir_slice_generic", "fir_slice"), ("fir_slice", "fir_slice"), ("pll_h3_kernel", "pll"), ("pll_tp_kernel", "pll"),
              ("hdlc_events", "hdlc_deframe"), ("hdlc_deframe", "hdlc_deframe"), ("hdlc_crc", "hdlc_crc"))
     env = dict(os.environ, TMPDIR="/tmp")
@@ -623,7 +659,7 @@ def pmc_traffic(args, config, device=0):
     return {"bytes_per_launch": res, "chain_bytes_per_call": sum(res.values()), "raw_kib_per_launch": raw, "valu": valu,
             "how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES "
                    "SQ_WAVES GRBM_GUI_ACTIVE (three separate passes) -- python bench.py --config " + config +
-                   " --no-cpu --no-others --no-e2e --no-traffic --no-kernel-leg --steps 6 --warmup 1, launched by this run; "
+                   " --full --no-cpu --no-others --no-e2e --no-traffic --no-kernel-leg --steps 6 --warmup 1, launched by this run; "
                    "sizes in KiB, FETCH_SIZE x 2 (gfx950 correction of MI355X_MICROARCH.md); issue_floor_ms = "
                    "SQ_ACTIVE_INST_VALU x 4 cycles / (1024 SIMDs x clock); launches run one at a time under the profiler"}
 
@@ -782,6 +818,10 @@ def compact_line(out, detail_path=None):
 def emit(out, args):
     """Everything measured -> the detail file (bench_detail.json beside this script, and under gpurun_out/ when that
     exists so that it comes back from the GPU box); the compact line -> stdout, LAST."""
+    if not getattr(args, "full", True):         # a plain run: the line alone
+        sys.stderr.flush()
+        print(compact_line(out), flush=True)
+        return
     detail = getattr(args, "detail", None) or os.path.join(ROOT, "bench_detail.json")
     written = None
     for path in [detail] + ([os.path.join(ROOT, "gpurun_out", "bench_detail.json")]
@@ -810,8 +850,10 @@ def rank_main(rank, local, world, args, sync):
     # the FIRST collective brings RCCL up (communicator, buffers, kernels: hundreds of ms with the device idle); it must not be
     # the barrier that opens the timed region -- behind it the first steps ran at idle clocks (0.59 instead of 0.50 ms per step)
     sync.barrier()
-    m = measure(cfg, args, local, rank, sync, args.steps, args.warmup, post=(rank == 0), keep_input=want_cpu,
-                kernel_leg=args.kernel_leg, uncalibrated=(world == 1))
+    full = args.full            # a plain run: the timed region alone
+    m = measure(cfg, args, local, rank, sync, args.steps, args.warmup, isolated=full, post=full and rank == 0,
+                keep_input=want_cpu, kernel_leg=args.kernel_leg, uncalibrated=full and world == 1, legs=full,
+                dump_dir=(args.dump_outputs or None) if rank == 0 else None)
     x_cpu, x_wide = m.pop("x_cpu", None), m.pop("x_wide", None)
     per_rank = {"rank": rank, "device": local, "ms_per_step": m["dt_own"] / m["steps"] * 1e3}
     # every rank left the opening barrier together and clocked its own K steps up to its own synchronize; the job's time is
@@ -833,26 +875,29 @@ def rank_main(rank, local, world, args, sync):
                    "parallelism": f"channels sharded over {world} GPU(s), one process per GPU, no collectives"},
         "valid_crc_msgs_per_s": msgs / dt,
         "x_realtime_channels": value / (cfg["rate"] / 1e6),
-        "kernel_ms": m["kernel_ms"], "kernel_ms_isolated": m["kernel_ms_isolated"],
-        "kernel_ms_calls": m["kernel_ms_calls"], "kernel_ms_leg": m.get("kernel_ms_leg"),
         "per_gpu": ranks,
-        "end_to_end": m.get("end_to_end"),
-        "message_lines": m.get("message_lines"),
-        "roofline": roofline_of(m, dt / args.steps * 1e3,
-                                pmc_traffic(args, args.config, local) if args.traffic else None,
-                                n_taps=144 if cfg["wide"] else 36),
-        "float_path": float_path(args, local) if (world == 1 and args.e2e and args.config == "C3") else None,
-        "steady_state": m.get("steady_state"),
-        "stage_masks": m.get("stage_masks"),
-        "uncalibrated_ms_per_step": m.get("uncalibrated_ms_per_step"),
-        "call_latency_ms": {"isolated": m.get("call_latency_isolated_ms"), "in_loop": m.get("call_latency_in_loop_ms"),
-                            "what": "one call, first kernel's start to last kernel's end (HIP events): alone on the chip / "
-                                    "inside the pipelined loop, where three calls are in flight"},
-        "uncalibrated_what": "the same K steps BEFORE gnuais_batch_autotune() (after 200 warm-up calls): the library's default "
-                             "stage -> stream assignment, what a plain gnuais_batch_run() caller gets",
-        "note": "the receive path slices the sign of the filter output and never stores the pre-slicer "
-                "floats; gnuais_batch_filter() produces them (bit-exact, tests/test_hip_parity.py)",
     }
+    if full:
+        out.update({
+            "kernel_ms": m["kernel_ms"], "kernel_ms_isolated": m["kernel_ms_isolated"],
+            "kernel_ms_calls": m["kernel_ms_calls"], "kernel_ms_leg": m.get("kernel_ms_leg"),
+            "end_to_end": m.get("end_to_end"),
+            "message_lines": m.get("message_lines"),
+            "roofline": roofline_of(m, dt / args.steps * 1e3,
+                                    pmc_traffic(args, args.config, local) if args.traffic else None,
+                                    n_taps=144 if cfg["wide"] else 36),
+            "float_path": float_path(args, local) if (world == 1 and args.e2e and args.config == "C3") else None,
+            "steady_state": m.get("steady_state"),
+            "stage_masks": m.get("stage_masks"),
+            "uncalibrated_ms_per_step": m.get("uncalibrated_ms_per_step"),
+            "call_latency_ms": {"isolated": m.get("call_latency_isolated_ms"), "in_loop": m.get("call_latency_in_loop_ms"),
+                                "what": "one call, first kernel's start to last kernel's end (HIP events): alone on the chip / "
+                                        "inside the pipelined loop, where three calls are in flight"},
+            "uncalibrated_what": "the same K steps BEFORE gnuais_batch_autotune() (after 200 warm-up calls): the library's default "
+                                 "stage -> stream assignment, what a plain gnuais_batch_run() caller gets",
+            "note": "the receive path slices the sign of the filter output and never stores the pre-slicer "
+                    "floats; gnuais_batch_filter() produces them (bit-exact, tests/test_hip_parity.py)",
+        })
     if world == 1 and args.others and args.config == "C3" and not args.channels and not args.len:
         # the same chain with the EXACT FIR in it (fir_slice_kernel: the reference's ordered 36-tap fp32 sum formed for
         # every sample, then `out > 0`) instead of the sign-certified slicer the receive path runs by default: same
@@ -928,12 +973,16 @@ def node_main(world, args):
         torch.cuda.synchronize(d)
     node.mark()                     # per-shard bookkeeping inside the library: a slow device must show by itself
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1 if args.dump_outputs else args.steps):
         step()
+    if args.dump_outputs:           # the last timed step keeps its frames for the dump
+        node.run(slabs)
     node.sync()
     for d in set(devs):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, node.drain_frames(), node.counters())
     stats = node.shard_stats()
     msgs = node.total_received() - rx0
     samples = float(per) * world * total * args.steps
@@ -1055,22 +1104,28 @@ def main():
     ap.add_argument("--no-traffic", dest="traffic", action="store_false",
                     help="skip the rocprofv3 --pmc child runs that fill roofline.traffic")
     ap.add_argument("--e2e", dest="e2e", action="store_true", default=True,
-                    help="(the default) the message-layer legs too: message_lines, end_to_end (run + streamed NMEA text into "
+                    help="(the default of --full) the message-layer legs too: message_lines, end_to_end (run + streamed NMEA text into "
                          "pinned host memory every step), float_path; the sinks' host post-stage rides with the CPU baseline")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false", help="skip them (the profiler's child runs do)")
     ap.add_argument("--no-traffic-others", dest="traffic_others", action="store_false",
                     help="skip the rocprofv3 --pmc child runs for C2 and C5 (six passes; other_configs.*.traffic stays null)")
     ap.add_argument("--traffic-others", dest="traffic_others", action="store_true", help="(the default; kept for old command lines)")
     ap.set_defaults(traffic_others=True)
-    ap.add_argument("--full", action="store_true", help="everything: --e2e as well")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: CPU baseline, C2 / C5, exact chain, kernel timings, PMC traffic, "
+                         "message-layer legs, bench_detail.json (a plain run sets up, warms up, times --steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (frame records, counters) as DIR/<name>.npy")
     ap.add_argument("--detail", default="", help="where the full measurements go (default: bench_detail.json here)")
     ap.add_argument("--print-detail", action="store_true",
                     help="also print the full measurements as an EARLIER stdout line (the compact line stays last)")
     ap.add_argument("--no-others", dest="others", action="store_false",
-                    help="skip the brief C2 / C5 measurements of a default single-GPU run")
+                    help="skip the brief C2 / C5 measurements of a --full single-GPU run")
     args = ap.parse_args()
-    if args.full:
-        args.e2e = args.traffic_others = True
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:               # a plain run: the headline alone; the --no-* options below shape a --full run
+        args.cpu = args.traffic = args.e2e = args.others = False
 
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
         # launched by torch.distributed.run: its ranks, RCCL for the barrier and the reductions

@@ -162,6 +162,9 @@ def main():
         fsm["fsm_" + name] = np.array(list(ref.fsm(0).values()), dtype=np.int32)
     np.savez_compressed(os.path.join(HERE, "deframer_bits.npz"), **fsm)
     make_nmea()
+    # 7. the reference's answers on the seeded inputs of the pin tests (tests/ref_pins.py)
+    import ref_pins
+    ref_pins.store()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -133,3 +133,33 @@ def test_ranks_of_torch_distributed_run_that_cannot_start_say_so_together():
     assert c["value"] is None and c["n_gpus"] == 2
     assert "rank 0 (device 0)" in c["error"] and "rank 1 (device 1)" in c["error"]
     assert [g["rank"] for g in c["per_gpu"]] == [0, 1]
+
+
+def test_dump_outputs_are_floats_within_budget_and_repeatable(tmp_path):
+    """--dump-outputs: every array float32 / float64 with its integers exact, a fixed seeded sample of a large step's
+    frames, under 64 MB in all, and the same files for the same records."""
+    import numpy as np
+    from gnuais_amd.lib import COUNTERS_DTYPE, FRAME_DTYPE
+    rng = np.random.default_rng(5)
+    fr = np.zeros(300000, dtype=FRAME_DTYPE)
+    fr["channel"] = rng.integers(0, 16384, len(fr))
+    fr["end_bit"] = rng.integers(0, 2 ** 32, len(fr), dtype=np.uint32)
+    fr["payload"] = rng.integers(0, 256, fr["payload"].shape)
+    fr["nbits"] = rng.integers(0, 424, len(fr))
+    cnt = np.zeros(16384, dtype=COUNTERS_DTYPE)
+    cnt["receivedframes"] = rng.integers(0, 1 << 30, len(cnt))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), fr, cnt)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "frame_payload.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / n)
+    assert total < 64 << 20
+    idx = np.load(tmp_path / "a" / "frame_index.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_FRAMES and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "frame_end_bit.npy"), fr["end_bit"][idx].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "counters.npy")[:, 0], cnt["receivedframes"].astype(np.float64))
+    assert np.load(tmp_path / "a" / "n_frames.npy")[0] == len(fr)

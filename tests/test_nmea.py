@@ -2,7 +2,7 @@
 protodec_getdata() / protodec_generate_nmea() -- byte for byte.
 
 CPU tests: committed golden text (tests/golden/nmea.npz, made by make_golden.py from
-oracle/_ref) and, where oracle/_ref is present, fresh random frames against the reference.
+oracle/_ref) and seeded random frames against the reference (live from oracle/_ref, else tests/ref_pins.py's stored copy).
 The function is host code inside libgnuais_hip.so; no device call is made here."""
 import os
 
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import cases
-from oracle_lib import FRAME_DTYPE, have_reference, reference
+import ref_pins
+from oracle_lib import FRAME_DTYPE
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -75,12 +76,12 @@ def test_stdout_text_golden():
         assert tx == g[name + "_stdout"].tobytes()
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built (reference tree absent)")
 @pytest.mark.parametrize("seed", [71, 72])
 def test_stdout_text_random_frames_vs_reference(seed):
     from gnuais_amd import messages_from_frames
     fr, n_ch = cases.nmea_frames(seed=seed, n_channels=4, n_random=1500)
-    want_nm, seq_want, want_tx = reference().nmea_of_frames(fr, n_ch, stdout=True)
+    w = ref_pins.want("stdout_text_%d" % seed)
+    want_nm, seq_want, want_tx = w["nmea"].tobytes(), w["seq"], w["text"].tobytes()
     seq = np.zeros(n_ch, dtype=np.uint8)
     nm, tx = messages_from_frames(fr, seq)
     assert nm == want_nm and np.array_equal(seq, seq_want)
@@ -134,11 +135,11 @@ def test_nmea_state_carries_and_sizes():
                                        C.byref(need), C.byref(ns)) == -1   # GNUAIS_E_ARG
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built (reference tree absent)")
 @pytest.mark.parametrize("seed", [61, 62, 63])
 def test_nmea_random_frames_vs_reference(seed):
     fr, n_ch = cases.nmea_frames(seed=seed, n_channels=7, n_random=900)
-    want, seq_want = reference().nmea_of_frames(fr, n_ch)
+    w = ref_pins.want("nmea_%d" % seed)
+    want, seq_want = w["nmea"].tobytes(), w["seq"]
     got, seq = nmea(fr, n_ch)
     assert got == want
     assert np.array_equal(seq, seq_want)

@@ -2,14 +2,16 @@
 its position decoders call it (protodec.c:399,441,628) -- float for float.
 
 CPU tests: committed golden (tests/golden/range.npz, made by make_golden.py from oracle/_ref) and,
-where oracle/_ref is present, fresh random fixes.  Host code inside libgnuais_hip.so."""
+seeded random fixes against the reference (live from oracle/_ref, else tests/ref_pins.py's stored copy).  Host code inside
+libgnuais_hip.so."""
 import os
 
 import numpy as np
 import pytest
 
 import cases
-from oracle_lib import FRAME_DTYPE, have_reference, reference
+import ref_pins
+from oracle_lib import FRAME_DTYPE
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -62,13 +64,10 @@ def test_range_argument_errors():
         ranges(fr, 2, 60.0, 10.0)                         # a frame of channel >= n_channels
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built")
 @pytest.mark.parametrize("seed", [5, 6])
 def test_range_random_against_reference(seed):
-    rng = np.random.default_rng(seed)
     fr, n_ch = cases.range_frames(seed=100 + seed, n_random=300, own_channel=True)
-    ref = reference()
-    for _ in range(4):
-        lat, lon = float(rng.uniform(-89.9, 89.9)), float(rng.uniform(-179.9, 179.9))
-        want = ref.range_of_frames(fr, n_ch, lat, lon)
+    w = ref_pins.want("range_%d" % seed)
+    for i, (lat, lon) in enumerate(ref_pins.range_locations(seed)):
+        want = w["range_%d" % i]
         assert ranges(fr, n_ch, lat, lon).tobytes() == want.tobytes()

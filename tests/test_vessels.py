@@ -3,14 +3,16 @@
 (protodec.c:282,390,435,516,619,676-678,740,772) -- field for field, floats bit for bit.
 
 CPU tests: committed golden (tests/golden/vessels.npz, made by make_golden.py from oracle/_ref)
-and, where oracle/_ref is present, fresh random traffic.  Host code inside libgnuais_hip.so."""
+and seeded random traffic against the reference (live from oracle/_ref, else tests/ref_pins.py's stored copy).  Host code
+inside libgnuais_hip.so."""
 import os
 
 import numpy as np
 import pytest
 
 import cases
-from oracle_lib import FRAME_DTYPE, have_reference, reference
+import ref_pins
+from oracle_lib import FRAME_DTYPE
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -67,12 +69,11 @@ def test_vessels_argument_errors():
     assert L.gnuais_vessels_from_frames(fr.ctypes.data, 0, small.ctypes.data, 3, C.byref(n)) == -1
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built")
 @pytest.mark.parametrize("seed,n_mmsi", [(7, 40), (8, 900)])
 def test_vessels_random_against_reference(seed, n_mmsi):
     from gnuais_amd import vessels_from_frames
     fr, n_ch = cases.vessel_frames(seed=200 + seed, n=900, n_mmsi=n_mmsi)
-    want = reference().cache_of_frames(fr, n_ch, pieces=[300, 301])
+    want = ref_pins.want("vessels_%d_%d" % (seed, n_mmsi))["table"]
     assert vessels_from_frames(fr).tobytes() == want.tobytes()
 
 
