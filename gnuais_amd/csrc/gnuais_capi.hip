@@ -204,6 +204,13 @@ struct gnuais_batch {
     // cross-stream event waits per call in the loop that sets the period become stream order: 20-step 0.550 -> 0.544,
     // steady 0.527 -> 0.522 (three A/B pairs, profiles/r04_k3_on_the_deframers_stream.txt).  0 = a stream of its own.
     int k3_same = 1;
+    // complex baseband in (gnuais_batch_run_iq / _discriminate, iq_disc.hip): the discriminator's carry -- the last (I, Q)
+    // pair an I/Q call saw, per channel -- and the audio it writes for the chain, [max_len][N] (allocated on first use).
+    // The audio's only reader is K1 of the same call, on the same stream (see e_in_hook).
+    int16_t *iq_prev = nullptr;                 // [N][2]
+    int16_t *iq_audio = nullptr;
+    hipStream_t iq_stream = nullptr;            // the stream of the last discriminator launch
+    bool iq_used = false;                       // a discriminator has been launched since create / reset
 };
 
 static int set_device(const gnuais_batch *b)
@@ -269,7 +276,8 @@ void gnuais_batch_destroy(gnuais_batch *b)
     }
     void *ptrs[] = {b->hist[0], b->hist[1], b->hist[2], b->hist[3], b->pll, b->lastbit, b->prev, b->ctl, b->cand,
                     b->frame_count, b->counters, b->maxval[0], b->maxval[1], b->maxval[2], b->maxval[3], b->frames, b->d_taps, b->d_mfma,
-                    b->stage_x, b->d_seq[0], b->d_seq[1], b->d_text, b->nmea_scratch, b->d_msg, b->d_word, b->stage_f, b->vt, b->vt_fslot};
+                    b->stage_x, b->d_seq[0], b->d_seq[1], b->d_text, b->nmea_scratch, b->d_msg, b->d_word, b->stage_f, b->vt, b->vt_fslot,
+                    b->iq_prev, b->iq_audio};
     for (void *p : ptrs)
         if (p) (void) hipFree(p);
     for (auto &set : b->evr)
@@ -530,6 +538,7 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     for (int q = 0; q < gnuais_batch::HB; ++q) alloc((void **) &b->maxval[q], sizeof(int) * N);
     alloc((void **) &b->frames, sizeof(gnuais_frame) * (size_t) b->frame_cap);
     alloc((void **) &b->d_taps, sizeof(float) * b->NT);
+    alloc((void **) &b->iq_prev, sizeof(int16_t) * 2 * N);
     if (b->mfma_ok) {
         alloc((void **) &b->d_mfma, sizeof(MfmaTaps));
         if (e == hipSuccess) e = hipMemcpy(b->d_mfma, &b->mfma_host, sizeof(MfmaTaps), hipMemcpyHostToDevice);
@@ -637,6 +646,8 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->ring_cur = 0;
     b->stream_calls = 0;
     HIP_TRY(launch_hdlc_reset(b->ctl, b->N, nullptr));                // protodec.c:87-100
+    HIP_TRY(hipMemset(b->iq_prev, 0, sizeof(int16_t) * 2 * N));       // the discriminator's previous pair: (0, 0)
+    b->iq_used = false;
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
     return GNUAIS_OK;
@@ -1182,6 +1193,65 @@ int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int l
     }
     b->host_calls++;                            // also after a failed run: the copy from pin[q] may still be in flight
     return rc;
+}
+
+// ---- complex baseband in (include/gnuais_hip.h): the discriminator (iq_disc.hip) in front of the unchanged chain ----
+
+// The carry goes from launch to launch in stream order; a discriminator on another stream than the last one waits for
+// that one on the host first (as gnuais_batch_run does for the chain's own carries).
+static int iq_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s)
+{
+    if (b->iq_used && s != b->iq_stream) HIP_TRY(hipStreamSynchronize(b->iq_stream));
+    HIP_TRY(launch_iq_discriminator(d_iq, d_out, b->iq_prev, b->N, len, s));
+    b->iq_stream = s;
+    b->iq_used = true;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream)
+{
+    if (!b || !d_iq || !d_out) return fail(GNUAIS_E_ARG, "discriminate: NULL argument");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "discriminate: len out of range (max_len)");
+    if (int rc = set_device(b)) return rc;
+    return iq_discriminate(b, d_iq, len, d_out, (hipStream_t) stream);
+}
+
+int gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *stream)
+{
+    if (!b || !d_iq) return fail(GNUAIS_E_ARG, "run_iq: NULL argument");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_iq: len out of range (max_len)");
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s0 = (hipStream_t) stream;
+    if (!b->iq_audio) {
+        const size_t need = sizeof(int16_t) * (size_t) b->max_len * (size_t) b->N;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "run_iq: the discriminator's audio for %d channels x %d samples needs %.2f GB of device "
+                     "memory, device %d has %.2f GB free of %.2f", b->N, b->max_len, need / 1e9, b->device, free_b / 1e9,
+                     total_b / 1e9);
+            return fail(GNUAIS_E_HIP, msg);
+        }
+        HIP_TRY(hipMalloc((void **) &b->iq_audio, need));
+    }
+    // One audio buffer serves every call: its reader, K1, runs on the stream of its call, so the next discriminator on
+    // that stream is ordered behind it.  On ANOTHER stream it is not -- and gnuais_batch_run drains the previous stream
+    // only once it is entered, after this discriminator would have overwritten the audio -- so drain it here.
+    if (b->calls > 0 && s0 != b->last_stream) HIP_TRY(hipStreamSynchronize(b->last_stream));
+    if (int rc = iq_discriminate(b, d_iq, len, b->iq_audio, s0)) return rc;
+    return gnuais_batch_run(b, b->iq_audio, len, stream);
+}
+
+int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
+{
+    if (!b || !h_iq) return fail(GNUAIS_E_ARG, "run_iq_host: NULL argument");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_iq_host: len out of range");
+    if (int rc = set_device(b)) return rc;
+    const size_t bytes = sizeof(int16_t) * 2 * (size_t) len * (size_t) b->N;
+    if (int rc = ensure_stage(b, bytes)) return rc;
+    HIP_TRY(hipMemcpy(b->stage_x, h_iq, bytes, hipMemcpyHostToDevice));
+    if (int rc = gnuais_batch_run_iq(b, b->stage_x, len, nullptr)) return rc;
+    return gnuais_batch_sync(b);
 }
 
 int gnuais_batch_filter(gnuais_batch *b, const int16_t *d_samples, int len, float *d_out,

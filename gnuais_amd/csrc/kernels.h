@@ -126,6 +126,12 @@ hipError_t launch_crc16(const uint8_t *data, int stride, const int32_t *len, int
 hipError_t launch_crc16_bits(const uint8_t *bits, int n_bytes, uint16_t *crc, uint8_t *msb, int n_out,
                              hipStream_t stream);
 
+// ---- complex baseband in: the FM discriminator (iq_disc.hip) ----------------------
+// iq [len][N][2] int16 (I, Q) -> out [len][N] int16, the definition in include/gnuais_hip.h; carry [N][2] int16 is the
+// previous pair of each channel, read at the start and replaced by row len-1.  iq and out must not overlap.
+constexpr int IQ_DISC_ROWS = 64;     // rows per thread (a segment); each segment reads one row more
+hipError_t launch_iq_discriminator(const int16_t *iq, int16_t *out, int16_t *carry, int N, int len, hipStream_t stream);
+
 // K1s evaluates the NC = 12 central taps in direct form with symmetric pre-adds (fir_slice.hip); the
 // host's error bound for y_c follows the same order of operations (gnuais_capi.hip)
 constexpr bool K1S_DIRECT(int nc) { return nc <= 12; }

@@ -101,6 +101,7 @@ struct Shard {
     int device = 0, first = 0, n = 0;
     gnuais_batch *b = nullptr;
     int16_t *d_in[2] = {nullptr, nullptr};      // run_host: the shard's [len][n] slab, double-buffered
+    bool in_iq = false;                         // run_iq_host has widened the slabs to [max_len][n][2]
     hipStream_t s_in = nullptr;
     hipEvent_t e_free[2] = {nullptr, nullptr};  // the FIR that read d_in[q] is done (recorded behind the run on s_in)
     unsigned long long host_calls = 0;
@@ -339,6 +340,67 @@ int gnuais_node_run_host(gnuais_node *nd, const int16_t *h_samples, int len)
         // the caller's buffer is borrowed for the call only (src/ais.c:216 reuses it): the copy out of it must be done
         if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
             return node_fail(GNUAIS_E_HIP, "node_run_host: copy");
+        return rc;
+    });
+}
+
+int gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams)
+{
+    if (!nd || !d_iq) return node_fail(GNUAIS_E_ARG, "node_run_iq: NULL argument");
+    if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run_iq: len out of range");
+    std::vector<Shard *> &sh = nd->shards;
+    return run_all(nd, [&](Shard &s) {
+        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
+        const double t0 = wall_ms();
+        const int rc = gnuais_batch_run_iq(s.b, d_iq[i], len, streams ? streams[i] : nullptr);
+        if (s.m_calls++ == 0) s.m_first = t0;
+        s.m_submit_ms += wall_ms() - t0;
+        return rc;
+    });
+}
+
+// gnuais_node_run_host with (I, Q) pairs: the staging slabs are twice as wide (allocated so on first use, or widened once,
+// after the shard's input stream -- the only user of a slab -- has drained)
+int gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len)
+{
+    if (!nd || !h_iq) return node_fail(GNUAIS_E_ARG, "node_run_iq_host: NULL argument");
+    if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run_iq_host: len out of range");
+    const int N = nd->N, max_len = nd->max_len;
+    return run_all(nd, [=](Shard &s) -> int {
+        const double t0 = wall_ms();
+        if (s.m_calls++ == 0) s.m_first = t0;
+        struct Stop { Shard &s; double t0; ~Stop() { s.m_submit_ms += wall_ms() - t0; } } stop{s, t0};
+        if (hipSetDevice(s.device) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_iq_host: hipSetDevice");
+        if (!s.s_in) {
+            if (hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess)
+                return node_fail(GNUAIS_E_HIP, "node_run_iq_host: stream");
+            for (int q = 0; q < 2; ++q)
+                if (hipEventCreateWithFlags(&s.e_free[q], hipEventDisableTiming) != hipSuccess)
+                    return node_fail(GNUAIS_E_HIP, "node_run_iq_host: staging events");
+        }
+        if (!s.in_iq) {
+            if (hipStreamSynchronize(s.s_in) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_iq_host: drain");
+            for (int q = 0; q < 2; ++q) {
+                if (s.d_in[q]) (void) hipFree(s.d_in[q]);
+                s.d_in[q] = nullptr;
+            }
+            for (int q = 0; q < 2; ++q)
+                if (hipMalloc((void **) &s.d_in[q], sizeof(int16_t) * 2 * (size_t) max_len * (size_t) s.n) != hipSuccess)
+                    return node_fail(GNUAIS_E_HIP, "node_run_iq_host: staging allocation");
+            s.in_iq = true;
+        }
+        const int q = (int) (s.host_calls & 1);
+        if (s.host_calls >= 2 && hipEventSynchronize(s.e_free[q]) != hipSuccess)
+            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: wait for the staging slab");
+        if (hipMemcpy2DAsync(s.d_in[q], sizeof(int16_t) * 2 * (size_t) s.n, h_iq + 2 * (size_t) s.first,
+                             sizeof(int16_t) * 2 * (size_t) N, sizeof(int16_t) * 2 * (size_t) s.n, (size_t) len,
+                             hipMemcpyHostToDevice, s.s_in) != hipSuccess)
+            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: host -> device copy");
+        const int rc = gnuais_batch_run_iq(s.b, s.d_in[q], len, s.s_in);
+        (void) hipEventRecord(s.e_free[q], s.s_in);
+        s.host_calls++;
+        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
+            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: copy");
         return rc;
     });
 }

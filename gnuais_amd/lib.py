@@ -33,6 +33,9 @@ SYMBOLS = {
     "gnuais_batch_run": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_host": (_I, [_P, _P, _I]),
     "gnuais_batch_run_host_async": (_I, [_P, _P, _I]),
+    "gnuais_batch_run_iq": (_I, [_P, _P, _I, _P]),
+    "gnuais_batch_run_iq_host": (_I, [_P, _P, _I]),
+    "gnuais_batch_discriminate": (_I, [_P, _P, _I, _P, _P]),
     "gnuais_wav_open": (_I, [C.POINTER(_P), C.c_char_p, _I]),
     "gnuais_wav_channels": (_I, [_P]),
     "gnuais_wav_rate": (_I, [_P]),
@@ -94,6 +97,8 @@ SYMBOLS = {
     "gnuais_node_shard": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_P)]),
     "gnuais_node_run_host": (_I, [_P, _P, _I]),
     "gnuais_node_run": (_I, [_P, _P, _I, _P]),
+    "gnuais_node_run_iq_host": (_I, [_P, _P, _I]),
+    "gnuais_node_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_node_sync": (_I, [_P]),
     "gnuais_node_pending_frames": (_I, [_P, C.POINTER(_I)]),
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),

@@ -79,6 +79,41 @@ class ReceiverBatch:
             assert x.ndim == 2 and x.shape[1] == self.n_channels
             check(self._lib.gnuais_batch_run_host(self._h, x.ctypes.data, int(x.shape[0])))
 
+    def run_iq(self, samples, stream: Optional[int] = None, sync: bool = True):
+        """Complex baseband in (gnuais_batch_run_iq): samples int16 [len][n_channels][2] = (I, Q) pairs; the
+        discriminator defined in include/gnuais_hip.h turns them into the audio run() takes, on the device.  A CUDA/HIP
+        torch tensor is used in place, asynchronously on `stream` or torch's current stream; a numpy array goes through
+        gnuais_batch_run_iq_host (copy, run, sync)."""
+        if _is_torch(samples):
+            import torch
+            assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
+            assert samples.dim() == 3 and samples.shape[1] == self.n_channels and samples.shape[2] == 2
+            if stream is None:
+                stream = torch.cuda.current_stream(samples.device).cuda_stream
+            check(self._lib.gnuais_batch_run_iq(self._h, samples.data_ptr(), int(samples.shape[0]),
+                                                C.c_void_p(stream)))
+            if sync:
+                self.sync()
+        else:
+            x = np.ascontiguousarray(samples, dtype=np.int16)
+            assert x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2
+            check(self._lib.gnuais_batch_run_iq_host(self._h, x.ctypes.data, int(x.shape[0])))
+
+    def discriminate(self, samples):
+        """The discriminator alone (gnuais_batch_discriminate): int16 [len][n_channels][2] -> torch int16
+        [len][n_channels] on the device; advances the I/Q carry and nothing else."""
+        import torch
+        if not _is_torch(samples):
+            samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16)).to(f"cuda:{self.device}")
+        assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
+        assert samples.dim() == 3 and samples.shape[1] == self.n_channels and samples.shape[2] == 2
+        out = torch.empty(tuple(samples.shape[:2]), dtype=torch.int16, device=samples.device)
+        stream = torch.cuda.current_stream(samples.device)
+        check(self._lib.gnuais_batch_discriminate(self._h, samples.data_ptr(), int(samples.shape[0]),
+                                                  out.data_ptr(), C.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        return out
+
     def run_host_async(self, samples: np.ndarray):
         """Host input without waiting for the device: pinned double-buffered staging inside the
         library (gnuais_batch_run_host_async); results after sync()."""

@@ -70,6 +70,23 @@ class ReceiverNode:
         assert x.ndim == 2 and x.shape[1] == self.n_channels
         self._raise(self._lib.gnuais_node_run_host(self._h, x.ctypes.data, int(x.shape[0])))
 
+    def run_iq_host(self, samples):
+        """Complex baseband in (gnuais_node_run_iq_host): one host array int16 [len][n_channels][2] of (I, Q) pairs."""
+        x = self._np.ascontiguousarray(samples, dtype=self._np.int16)
+        assert x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2
+        self._raise(self._lib.gnuais_node_run_iq_host(self._h, x.ctypes.data, int(x.shape[0])))
+
+    def run_iq(self, slabs, streams=None):
+        """slabs: one CUDA/HIP int16 tensor [len][n_i][2] of (I, Q) pairs per shard, each on its shard's device."""
+        C = self._C
+        assert len(slabs) == len(self.shards)
+        ln = int(slabs[0].shape[0])
+        for t, (d, f, n) in zip(slabs, self.shards):
+            assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == (ln, n, 2) and t.device.index == d
+        ptrs = (C.c_void_p * len(slabs))(*[t.data_ptr() for t in slabs])
+        st = None if streams is None else (C.c_void_p * len(slabs))(*streams)
+        self._raise(self._lib.gnuais_node_run_iq(self._h, ptrs, ln, st))
+
     def run(self, slabs, streams=None):
         """slabs: one CUDA/HIP int16 tensor [len][n_i] per shard, each on its shard's device."""
         C = self._C

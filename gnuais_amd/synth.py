@@ -120,6 +120,42 @@ def make_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int = 5
     return np.clip(x, -32768, 32767).astype(np.int16), placed
 
 
+def make_iq_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int = 5,
+                   amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
+                   payloads=None, bt: float = 0.4):
+    """One channel of synthetic complex baseband: what an SDR front end or a channeliser hands over.
+
+    The same bursts as make_stream() (slots, training, flags, NRZI, Gaussian shaping) as h = 0.5 GMSK: the phase is the
+    running sum of (pi/2/sps) * the shaped level, from a random initial phase; I/Q = amplitude * (cos, sin) + white
+    Gaussian noise of `sigma` on each, rounded and clamped to int16.  Its own random sequence (make_stream's is left as
+    it is).  Returns (int16[n_samples][2], list of (slot, payload bytes) actually placed).
+    """
+    rng = np.random.default_rng([seed, channel, 0x4951])
+    slot_len = SLOT_BITS * sps
+    n_slots = (n_samples + slot_len - 1) // slot_len
+    level = np.zeros(n_slots * slot_len + 64 * sps, dtype=np.float64)
+    placed = []
+    for slot in range(n_slots):
+        if payloads is not None:
+            payload = payloads(rng, slot)
+        else:
+            payload = random_position_report(rng) if rng.random() < occupancy else None
+        if payload is None:
+            continue
+        bits = hdlc_frame_bits(payload)
+        lev = np.repeat(nrzi_levels(bits, start_level=int(rng.integers(0, 2))), sps)
+        start = slot * slot_len + START_OFFSET_BITS * sps
+        end = min(start + lev.size, level.size)
+        level[start:end] = lev[: end - start]
+        placed.append((slot, payload))
+    shaped = np.convolve(level, gaussian_kernel(sps, bt), mode="same")[:n_samples]
+    phase = rng.uniform(-np.pi, np.pi) + np.cumsum(shaped * (np.pi / 2.0 / sps))
+    iq = np.stack([amplitude * np.cos(phase), amplitude * np.sin(phase)], axis=1)
+    if sigma > 0:
+        iq += rng.normal(0.0, sigma, iq.shape)
+    return np.clip(np.rint(iq), -32768, 32767).astype(np.int16), placed
+
+
 def make_base_streams(n_base: int, n_samples: int, **kw):
     """[n_base][n_samples] int16 + per-stream placed payload lists."""
     streams = np.empty((n_base, n_samples), dtype=np.int16)

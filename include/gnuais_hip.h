@@ -127,6 +127,37 @@ int  gnuais_batch_run_host(gnuais_batch *b, const int16_t *h_samples, int len);
 int  gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int len);
 int  gnuais_batch_sync(gnuais_batch *b);
 
+/* ---- complex baseband in: an FM discriminator on the device in front of the chain ----------------------------
+ * Not in the reference (it reads discriminator audio from a sound card); for SDR front ends and channelisers that
+ * give I/Q pairs.  Per channel, a stream of int16 pairs (I, Q) at the chain's sample rate (48 kHz for the default
+ * table, 192 kHz with the 144-tap table and its pllinc) becomes the int16 audio sample out[n], which enters the
+ * chain exactly as if it had been passed to gnuais_batch_run().  Carried per channel: the previous pair (Ip, Qp),
+ * (0, 0) after gnuais_batch_create() and gnuais_batch_reset().  Audio run calls neither read nor change it; the
+ * two kinds of call may be mixed on one batch, and the carry is always the last pair an I/Q call saw.
+ *
+ * fp32, IEEE round-to-nearest-even at every operation, no fused multiply-add, int16 -> fp32 exact:
+ *   re = (I*Ip) + (Q*Qp)      im = (Q*Ip) - (I*Qp)        each product rounded, then the sum rounded
+ *   ax = |re|  ay = |im|  mx = max(ax, ay)  mn = min(ax, ay)
+ *   t  = (mx == 0) ? 0 : mn / mx                         correctly rounded division
+ *   s  = t*t
+ *   p  = t * (A1 + s*(A3 + s*(A5 + s*(A7 + s*A9))))      in exactly this order (Abramowitz & Stegun 4.4.49)
+ *   if (ay > ax) p = HALF_PI - p
+ *   if (re < 0)  p = PI - p                              ordered compares: -0.0 is not < 0
+ *   if (im < 0)  p = -p
+ *   out = clamp(rint(p * G), -32768, 32767)              rint = round half to even
+ * with the fp32 constants (bit patterns)  A1 0x3f7ff738 (0.9998660)  A3 0xbea91d04 (-0.3302995)
+ *   A5 0x3e3876e2 (0.1801410)  A7 0xbdae5a36 (-0.0851330)  A9 0x3caaae5f (0.0208351)
+ *   PI 0x40490fdb  HALF_PI 0x3fc90fdb  G 0x4622f983 (32768/pi).
+ * out is the phase step from one pair to the next in units of pi/32768 (only +pi clips, to 32767); there is no gain.
+ * The AIS deviation of +-2.4 kHz reads about +-3277 at 48 kHz and +-819 at 192 kHz.  The slicer uses only the sign of
+ * the filtered value; gnuais_batch_maxval() (the level log's value) reads out in these units. */
+/* d_iq = DEVICE int16 [len][n_channels][2] (I, Q), i.e. a 2N-channel interleaved stream; runs the discriminator then
+ * the receive chain on its output; asynchronous as gnuais_batch_run (the discriminator runs on `stream`; a change of
+ * stream between two calls synchronises the previous one first) */
+int  gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *stream);
+/* the same from a HOST buffer; synchronous (copy, run, sync) */
+int  gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len);
+
 /* ---- input side, row f2: sample files -> interleaved int16 frames (src/ais.c:173-182,214-217) ---
  * raw_channels > 0: the file is a bare stream of little-endian int16 frames of that many channels,
  *   header and all, exactly as the reference reads a sound file; 0: parse RIFF/WAVE (16-bit PCM,
@@ -146,6 +177,10 @@ int  gnuais_batch_filter(gnuais_batch *b, const int16_t *d_samples, int len,
 /* the same from and to HOST memory (plain-C callers: gnuais_amd/csrc/protodec_hip.c): h_samples int16
  * [len][n_channels], h_out float [len][n_channels]; synchronous */
 int  gnuais_batch_filter_host(gnuais_batch *b, const int16_t *h_samples, int len, float *h_out);
+/* the discriminator only (definition above gnuais_batch_run_iq): d_iq DEVICE int16 [len][n_channels][2], d_out =
+ * DEVICE int16 [len][n_channels] (must not overlap d_iq); advances the I/Q carry and nothing else.  Asynchronous on
+ * `stream`. */
+int  gnuais_batch_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream);
 /* protodec_decode(in, count, d), src/protodec.c:988-1122, for every channel:
  * h_bits = HOST uint8 [n_channels][stride], one byte per bit; h_count[n_channels] */
 int  gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
@@ -396,6 +431,11 @@ int  gnuais_node_run_host(gnuais_node *nd, const int16_t *h_samples, int len);
 /* the same with the samples already on the devices: d_samples[i] = shard i's DEVICE slab, interleaved
  * int16 [len][n_channels of shard i]; streams[i] (or NULL) as in gnuais_batch_run().  Asynchronous. */
 int  gnuais_node_run(gnuais_node *nd, const int16_t *const *d_samples, int len, void *const *streams);
+/* complex baseband in (gnuais_batch_run_iq): one HOST buffer int16 [len][N][2]; every shard copies its columns (a 2-D
+ * copy, 4 bytes per channel) and runs discriminator and chain; returns when the buffer may be reused */
+int  gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len);
+/* the same with the pairs already on the devices: d_iq[i] = shard i's DEVICE slab int16 [len][n_channels of shard i][2] */
+int  gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams);
 int  gnuais_node_sync(gnuais_node *nd);
 /* merged results: records of every device, channel = global index, reference order (channel, then time) */
 int  gnuais_node_pending_frames(gnuais_node *nd, int *n_out);
