@@ -211,6 +211,18 @@ struct gnuais_batch {
     int16_t *iq_audio = nullptr;
     hipStream_t iq_stream = nullptr;            // the stream of the last discriminator launch
     bool iq_used = false;                       // a discriminator has been launched since create / reset
+    // wideband in (gnuais_batch_channeliser / _run_wideband, channeliser.hip): the configuration, the device tables, the
+    // carry (the last T-1 wide samples of each stream, double-buffered: a launch reads one and writes the other), the
+    // wide-sample count n and the narrowband I/Q it writes for the discriminator, [max_len][N][2] (allocated on first use).
+    int ch_K = 0, ch_D = 0, ch_T = 0, ch_R = 0, ch_NA = 0;  // ch_K == 0: not configured
+    int ch_per[CHAN_MAX_K] = {}, ch_off[CHAN_MAX_K] = {};
+    uint32_t *ch_mix = nullptr, *ch_poly = nullptr, *ch_hist[2] = {nullptr, nullptr};
+    int16_t *ch_taps = nullptr;
+    int ch_cur = 0;
+    unsigned long long ch_n = 0;
+    int16_t *ch_iq = nullptr;
+    hipStream_t ch_stream = nullptr;            // the stream of the last channeliser launch
+    bool ch_used = false;
 };
 
 static int set_device(const gnuais_batch *b)
@@ -277,7 +289,7 @@ void gnuais_batch_destroy(gnuais_batch *b)
     void *ptrs[] = {b->hist[0], b->hist[1], b->hist[2], b->hist[3], b->pll, b->lastbit, b->prev, b->ctl, b->cand,
                     b->frame_count, b->counters, b->maxval[0], b->maxval[1], b->maxval[2], b->maxval[3], b->frames, b->d_taps, b->d_mfma,
                     b->stage_x, b->d_seq[0], b->d_seq[1], b->d_text, b->nmea_scratch, b->d_msg, b->d_word, b->stage_f, b->vt, b->vt_fslot,
-                    b->iq_prev, b->iq_audio};
+                    b->iq_prev, b->iq_audio, b->ch_mix, b->ch_poly, b->ch_hist[0], b->ch_hist[1], b->ch_taps, b->ch_iq};
     for (void *p : ptrs)
         if (p) (void) hipFree(p);
     for (auto &set : b->evr)
@@ -617,6 +629,18 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     return rc;
 }
 
+// the channeliser's carry and sample count (configuration kept)
+static int chan_zero_state(gnuais_batch *b)
+{
+    if (b->ch_K)
+        for (auto p : b->ch_hist)
+            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) (b->ch_T - 1) * (size_t) (b->N / b->ch_K)));
+    b->ch_cur = 0;
+    b->ch_n = 0;
+    b->ch_used = false;
+    return GNUAIS_OK;
+}
+
 int gnuais_batch_reset(gnuais_batch *b)
 {
     if (!b) return fail(GNUAIS_E_ARG, "reset: NULL batch");
@@ -648,6 +672,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     HIP_TRY(launch_hdlc_reset(b->ctl, b->N, nullptr));                // protodec.c:87-100
     HIP_TRY(hipMemset(b->iq_prev, 0, sizeof(int16_t) * 2 * N));       // the discriminator's previous pair: (0, 0)
     b->iq_used = false;
+    if (int rc = chan_zero_state(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
     return GNUAIS_OK;
@@ -1251,6 +1276,259 @@ int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
     if (int rc = ensure_stage(b, bytes)) return rc;
     HIP_TRY(hipMemcpy(b->stage_x, h_iq, bytes, hipMemcpyHostToDevice));
     if (int rc = gnuais_batch_run_iq(b, b->stage_x, len, nullptr)) return rc;
+    return gnuais_batch_sync(b);
+}
+
+// ---- wideband in (include/gnuais_hip.h): the channeliser (channeliser.hip) in front of the discriminator ----
+
+static long long rnd_away(double x) { return lround(x); }
+
+static int chan_default_taps(int D, std::vector<int16_t> &h)
+{
+    const int T = 16 * D + 1;
+    std::vector<double> g((size_t) T);
+    double G = 0.0;
+    for (int j = 0; j < T; ++j) {
+        const double w = 0.42 - 0.5 * cos(2.0 * M_PI * j / (T - 1)) + 0.08 * cos(4.0 * M_PI * j / (T - 1));
+        const double x = 0.75 * (j - 8 * D) / D;
+        const double s = (x == 0.0) ? 1.0 : sin(M_PI * x) / (M_PI * x);
+        g[(size_t) j] = w * s;
+        G += g[(size_t) j];
+    }
+    h.resize((size_t) T);
+    for (int j = 0; j < T; ++j) h[(size_t) j] = (int16_t) rnd_away(g[(size_t) j] * 32768.0 / G);
+    return T;
+}
+
+static long long gcd_ll(long long a, long long b)
+{
+    while (b) { const long long t = a % b; a = b; b = t; }
+    return a;
+}
+
+// the period of offset f at rate R, or 0 if it exceeds 2^20
+static int chan_period(int R, int f)
+{
+    const long long g = gcd_ll(std::llabs((long long) f), (long long) R);
+    const long long P = (long long) R / g;
+    return P > (1LL << 20) ? 0 : (int) P;
+}
+
+static void chan_mixer(int R, int f, int P, int16_t *cs)
+{
+    for (int p = 0; p < P; ++p) {
+        long long q = ((long long) f * p) % R;
+        if (q < 0) q += R;
+        const double th = 2.0 * M_PI * (double) q / (double) R;
+        cs[2 * p] = (int16_t) rnd_away(32767.0 * cos(th));
+        cs[2 * p + 1] = (int16_t) rnd_away(32767.0 * sin(th));
+    }
+}
+
+int gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps)
+{
+    if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser_default_taps: decim must be 1..64");
+    std::vector<int16_t> h;
+    const int T = chan_default_taps(decim, h);
+    if (n_taps) *n_taps = T;
+    if (!out) return GNUAIS_OK;
+    if (cap < T) return fail(GNUAIS_E_ARG, "channeliser_default_taps: cap < 16*decim + 1");
+    memcpy(out, h.data(), sizeof(int16_t) * (size_t) T);
+    return GNUAIS_OK;
+}
+
+int gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period)
+{
+    if (in_rate_hz <= 0) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: in_rate_hz must be > 0");
+    const int P = chan_period(in_rate_hz, offset_hz);
+    if (!P) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: the offset's mixer period R / gcd(|f|, R) exceeds 2^20");
+    if (period) *period = P;
+    if (!out) return GNUAIS_OK;
+    if (cap < P) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: cap < period");
+    chan_mixer(in_rate_hz, offset_hz, P, out);
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                             const int16_t *taps, int n_taps)
+{
+    if (!b || !offsets_hz) return fail(GNUAIS_E_ARG, "channeliser: NULL argument");
+    if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser: decim must be 1..64");
+    if (in_rate_hz <= 0) return fail(GNUAIS_E_ARG, "channeliser: in_rate_hz must be > 0");
+    if (n_offsets < 1 || n_offsets > CHAN_MAX_K) return fail(GNUAIS_E_ARG, "channeliser: n_offsets must be 1..32");
+    if (b->N % n_offsets) return fail(GNUAIS_E_ARG, "channeliser: the batch's channel count is not a multiple of n_offsets");
+    std::vector<int16_t> h;
+    if (!taps || n_taps == 0) {
+        chan_default_taps(decim, h);
+    } else {
+        if (n_taps < 1 || n_taps > 1025) return fail(GNUAIS_E_ARG, "channeliser: n_taps must be 1..1025");
+        h.assign(taps, taps + n_taps);
+    }
+    const int T = (int) h.size();
+    long long sum = 0;
+    for (int16_t v : h) {
+        if (v == -32768) return fail(GNUAIS_E_ARG, "channeliser: a tap is -32768 (|h| <= 32767)");
+        sum += std::abs((int) v);
+    }
+    if (sum > 65535) return fail(GNUAIS_E_ARG, "channeliser: sum |h| exceeds 65535");
+    const int K = n_offsets;
+    int per[CHAN_MAX_K], off[CHAN_MAX_K];
+    int total = 0;
+    for (int k = 0; k < K; ++k) {
+        per[k] = chan_period(in_rate_hz, offsets_hz[k]);
+        if (!per[k]) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "channeliser: offset %d Hz at %d Hz has a mixer period above 2^20", (int) offsets_hz[k],
+                     in_rate_hz);
+            return fail(GNUAIS_E_ARG, msg);
+        }
+        off[k] = total;
+        total += per[k];
+    }
+    // host tables: mixer words (C lo, S hi); the fast form's tap pairs POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q])
+    std::vector<int16_t> mix(2 * (size_t) total);
+    for (int k = 0; k < K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], per[k], mix.data() + 2 * (size_t) off[k]);
+    const int D = decim;
+    const int NA = channeliser_fast_na(K, T, D);
+    std::vector<uint32_t> poly;
+    if (NA) {
+        const int NP = (D + 1) / 2;
+        poly.assign((size_t) NP * NA, 0u);
+        auto tap = [&](int a, int r) -> int {
+            if (r >= D) return 0;
+            const int j = a * D + D - 1 - r;
+            return j < T ? h[(size_t) j] : 0;
+        };
+        for (int q = 0; q < NP; ++q)
+            for (int a = 0; a < NA; ++a)
+                poly[(size_t) q * NA + a] = (uint32_t) (uint16_t) tap(a, 2 * q) | ((uint32_t) (uint16_t) tap(a, 2 * q + 1) << 16);
+    }
+    if (int rc = set_device(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (uint32_t **p : {&b->ch_mix, &b->ch_poly, &b->ch_hist[0], &b->ch_hist[1]})
+        if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
+    if (b->ch_taps) { HIP_TRY(hipFree(b->ch_taps)); b->ch_taps = nullptr; }
+    b->ch_K = 0;
+    const size_t M = (size_t) (b->N / K);
+    HIP_TRY(hipMalloc((void **) &b->ch_mix, sizeof(uint32_t) * (size_t) total));
+    HIP_TRY(hipMemcpy(b->ch_mix, mix.data(), sizeof(uint32_t) * (size_t) total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void **) &b->ch_taps, sizeof(int16_t) * (size_t) T));
+    HIP_TRY(hipMemcpy(b->ch_taps, h.data(), sizeof(int16_t) * (size_t) T, hipMemcpyHostToDevice));
+    if (NA) {
+        HIP_TRY(hipMalloc((void **) &b->ch_poly, sizeof(uint32_t) * poly.size()));
+        HIP_TRY(hipMemcpy(b->ch_poly, poly.data(), sizeof(uint32_t) * poly.size(), hipMemcpyHostToDevice));
+    }
+    if (T > 1)
+        for (auto &p : b->ch_hist) HIP_TRY(hipMalloc((void **) &p, sizeof(uint32_t) * (size_t) (T - 1) * M));
+    b->ch_K = K;
+    b->ch_D = D;
+    b->ch_T = T;
+    b->ch_R = in_rate_hz;
+    b->ch_NA = NA;
+    for (int k = 0; k < K; ++k) { b->ch_per[k] = per[k]; b->ch_off[k] = off[k]; }
+    if (int rc = chan_zero_state(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return GNUAIS_OK;
+}
+
+static int chan_check(gnuais_batch *b, const int16_t *d_wide, int len, const char *who)
+{
+    char msg[200];
+    if (!b || !d_wide) {
+        snprintf(msg, sizeof msg, "%s: NULL argument", who);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    if (!b->ch_K) {
+        snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
+        snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
+                 len, b->ch_D, b->ch_D);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    if (reinterpret_cast<uintptr_t>(d_wide) % 4) {
+        snprintf(msg, sizeof msg, "%s: the wide samples must be 4-byte aligned", who);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    return GNUAIS_OK;
+}
+
+// The carry goes from launch to launch in stream order; a channeliser on another stream than the last one waits for that
+// one on the host first (as iq_discriminate does).
+static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, hipStream_t s)
+{
+    if (b->ch_used && s != b->ch_stream) HIP_TRY(hipStreamSynchronize(b->ch_stream));
+    ChanLaunch a{};
+    a.in = reinterpret_cast<const uint32_t *>(d_wide);
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.hist = b->ch_hist[b->ch_cur];
+    a.mix = b->ch_mix;
+    a.poly = b->ch_poly;
+    a.taps = b->ch_taps;
+    a.M = b->N / b->ch_K;
+    a.K = b->ch_K;
+    a.D = b->ch_D;
+    a.T = b->ch_T;
+    a.len = len;
+    // the fast form stores K words per lane as one vector: the output must be aligned to it (else the direct form)
+    const unsigned vec = a.K == 2 ? 8u : a.K == 4 ? 16u : 4u;
+    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : b->ch_NA;
+    if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(GNUAIS_E_ARG, "channelise: the output must be 4-byte aligned");
+    for (int k = 0; k < a.K; ++k) {
+        a.per[k] = b->ch_per[k];
+        a.off[k] = b->ch_off[k];
+        a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
+    }
+    HIP_TRY(launch_channeliser(a, b->ch_hist[b->ch_cur ^ 1], s));
+    if (b->ch_T > 1) b->ch_cur ^= 1;
+    b->ch_n += (unsigned long long) len;
+    b->ch_stream = s;
+    b->ch_used = true;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream)
+{
+    if (int rc = chan_check(b, d_wide, len, "channelise")) return rc;
+    if (!d_out) return fail(GNUAIS_E_ARG, "channelise: NULL argument");
+    if (int rc = set_device(b)) return rc;
+    return chan_launch(b, d_wide, len, d_out, (hipStream_t) stream);
+}
+
+int gnuais_batch_run_wideband(gnuais_batch *b, const int16_t *d_wide, int len, void *stream)
+{
+    if (int rc = chan_check(b, d_wide, len, "run_wideband")) return rc;
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s0 = (hipStream_t) stream;
+    if (!b->ch_iq) {
+        const size_t need = sizeof(int16_t) * 2 * (size_t) b->max_len * (size_t) b->N;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "run_wideband: the channeliser's I/Q for %d channels x %d samples needs %.2f GB of "
+                     "device memory, device %d has %.2f GB free of %.2f", b->N, b->max_len, need / 1e9, b->device,
+                     free_b / 1e9, total_b / 1e9);
+            return fail(GNUAIS_E_HIP, msg);
+        }
+        HIP_TRY(hipMalloc((void **) &b->ch_iq, need));
+    }
+    // The I/Q buffer's only reader is the discriminator of the same call, on the same stream.  On another stream the
+    // previous call's discriminator (and FIR) may still run: drain it before this channeliser overwrites the buffer.
+    if (b->calls > 0 && s0 != b->last_stream) HIP_TRY(hipStreamSynchronize(b->last_stream));
+    if (b->iq_used && s0 != b->iq_stream) HIP_TRY(hipStreamSynchronize(b->iq_stream));
+    if (int rc = chan_launch(b, d_wide, len, b->ch_iq, s0)) return rc;
+    return gnuais_batch_run_iq(b, b->ch_iq, len / b->ch_D, stream);
+}
+
+int gnuais_batch_run_wideband_host(gnuais_batch *b, const int16_t *h_wide, int len)
+{
+    if (int rc = chan_check(b, h_wide, len, "run_wideband_host")) return rc;
+    if (int rc = set_device(b)) return rc;
+    const size_t bytes = sizeof(int16_t) * 2 * (size_t) len * (size_t) (b->N / b->ch_K);
+    if (int rc = ensure_stage(b, bytes)) return rc;
+    HIP_TRY(hipMemcpy(b->stage_x, h_wide, bytes, hipMemcpyHostToDevice));
+    if (int rc = gnuais_batch_run_wideband(b, b->stage_x, len, nullptr)) return rc;
     return gnuais_batch_sync(b);
 }
 

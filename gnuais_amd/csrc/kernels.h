@@ -132,6 +132,26 @@ hipError_t launch_crc16_bits(const uint8_t *bits, int n_bytes, uint16_t *crc, ui
 constexpr int IQ_DISC_ROWS = 64;     // rows per thread (a segment); each segment reads one row more
 hipError_t launch_iq_discriminator(const int16_t *iq, int16_t *out, int16_t *carry, int N, int len, hipStream_t stream);
 
+// ---- wideband in: the channeliser (channeliser.hip) -------------------------------------
+// in [len][M][2] int16 -> out [len/D][M*K][2] int16, the definition in include/gnuais_hip.h.  hist [T-1][M] words is the
+// carry (the last T-1 wide samples), read here; the launch writes the next one into hist_out (another buffer).
+constexpr int CHAN_MAX_K = 32;       // offsets per stream
+struct ChanLaunch {
+    const uint32_t *in;    // [len][M] (I lo, Q hi)
+    uint32_t *out;         // [len/D][M*K]
+    const uint32_t *hist;  // [T-1][M]
+    const uint32_t *mix;   // mixer tables, (C lo, S hi), offset k's at mix + off[k], per[k] entries
+    const uint32_t *poly;  // fast form: [(D+1)/2][NA] tap pairs (channeliser.hip)
+    const int16_t *taps;   // direct form: [T]
+    int M, K, D, T, len;
+    int NA;                // fast form's accumulators per offset (channeliser_fast_na), 0 = direct form
+    int n_groups, seg_rows;                // set by launch_channeliser
+    int per[CHAN_MAX_K], off[CHAN_MAX_K];
+    int ph0[CHAN_MAX_K];   // (n mod per[k]) of the call's first wide sample
+};
+int channeliser_fast_na(int K, int T, int D);    // 0: no fast form for this shape
+hipError_t launch_channeliser(const ChanLaunch &a, uint32_t *hist_out, hipStream_t stream);
+
 // K1s evaluates the NC = 12 central taps in direct form with symmetric pre-adds (fir_slice.hip); the
 // host's error bound for y_c follows the same order of operations (gnuais_capi.hip)
 constexpr bool K1S_DIRECT(int nc) { return nc <= 12; }

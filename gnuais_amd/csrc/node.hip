@@ -102,6 +102,8 @@ struct Shard {
     gnuais_batch *b = nullptr;
     int16_t *d_in[2] = {nullptr, nullptr};      // run_host: the shard's [len][n] slab, double-buffered
     bool in_iq = false;                         // run_iq_host has widened the slabs to [max_len][n][2]
+    int16_t *d_wide = nullptr;                  // run_wideband_host: the shard's wide streams [D*max_len][n/K][2]
+    size_t wide_bytes = 0;
     hipStream_t s_in = nullptr;
     hipEvent_t e_free[2] = {nullptr, nullptr};  // the FIR that read d_in[q] is done (recorded behind the run on s_in)
     unsigned long long host_calls = 0;
@@ -167,6 +169,7 @@ void pin_to_device_node(Shard &s)
 
 struct gnuais_node {
     int N = 0, max_len = 0;
+    int ch_K = 0, ch_D = 0;         // gnuais_node_channeliser (0: not configured)
     std::vector<Shard *> shards;
     std::vector<gnuais_frame> scratch;
     std::string warnings;           // what create could not do without failing (one line per shard)
@@ -203,6 +206,7 @@ void gnuais_node_destroy(gnuais_node *nd)
                     if (s->d_in[q]) (void) hipFree(s->d_in[q]);
                     if (s->e_free[q]) (void) hipEventDestroy(s->e_free[q]);
                 }
+                if (s->d_wide) (void) hipFree(s->d_wide);
                 if (s->s_in) (void) hipStreamDestroy(s->s_in);
                 return GNUAIS_OK;
             });
@@ -401,6 +405,74 @@ int gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len)
         s.host_calls++;
         if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
             return node_fail(GNUAIS_E_HIP, "node_run_iq_host: copy");
+        return rc;
+    });
+}
+
+int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                            const int16_t *taps, int n_taps)
+{
+    if (!nd || !offsets_hz) return node_fail(GNUAIS_E_ARG, "node_channeliser: NULL argument");
+    if (n_offsets < 1) return node_fail(GNUAIS_E_ARG, "node_channeliser: n_offsets must be >= 1");
+    for (size_t i = 0; i < nd->shards.size(); ++i) {
+        const Shard &s = *nd->shards[i];
+        if (s.first % n_offsets || s.n % n_offsets) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "node_channeliser: shard %zu (channels %d..%d) does not start and end on a multiple of "
+                     "n_offsets = %d", i, s.first, s.first + s.n - 1, n_offsets);
+            return node_fail(GNUAIS_E_ARG, msg);
+        }
+    }
+    nd->ch_K = 0;
+    const int rc = run_all(nd, [=](Shard &s) {
+        return gnuais_batch_channeliser(s.b, decim, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
+    });
+    if (rc == GNUAIS_OK) {
+        nd->ch_K = n_offsets;
+        nd->ch_D = decim;
+    }
+    return rc;
+}
+
+// every shard copies the columns of its own streams into a device slab of its own on its input stream, then runs the
+// channeliser on that stream; the next call's copy is ordered behind this call's channeliser, the only reader of the slab
+int gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len)
+{
+    if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: NULL argument");
+    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: no channeliser configured (gnuais_node_channeliser)");
+    const int K = nd->ch_K, D = nd->ch_D, M = nd->N / K, max_len = nd->max_len;
+    if (len <= 0 || len % D || len / D > max_len)
+        return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: len must be a positive multiple of the decimation, at most "
+                                       "decim * max_len");
+    return run_all(nd, [=](Shard &s) -> int {
+        const double t0 = wall_ms();
+        if (s.m_calls++ == 0) s.m_first = t0;
+        struct Stop { Shard &s; double t0; ~Stop() { s.m_submit_ms += wall_ms() - t0; } } stop{s, t0};
+        if (hipSetDevice(s.device) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: hipSetDevice");
+        if (!s.s_in) {
+            if (hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess)
+                return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: stream");
+            for (int q = 0; q < 2; ++q)
+                if (hipEventCreateWithFlags(&s.e_free[q], hipEventDisableTiming) != hipSuccess)
+                    return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: staging events");
+        }
+        const size_t ms = (size_t) (s.n / K);
+        const size_t need = sizeof(int16_t) * 2 * (size_t) D * (size_t) max_len * ms;
+        if (s.wide_bytes < need) {                // s_in is drained at the end of every call: the old slab is free
+            if (s.d_wide) (void) hipFree(s.d_wide);
+            s.d_wide = nullptr;
+            s.wide_bytes = 0;
+            if (hipMalloc((void **) &s.d_wide, need) != hipSuccess)
+                return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: staging allocation");
+            s.wide_bytes = need;
+        }
+        if (hipMemcpy2DAsync(s.d_wide, sizeof(int16_t) * 2 * ms, h_wide + 2 * (size_t) (s.first / K),
+                             sizeof(int16_t) * 2 * (size_t) M, sizeof(int16_t) * 2 * ms, (size_t) len, hipMemcpyHostToDevice,
+                             s.s_in) != hipSuccess)
+            return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: host -> device copy");
+        const int rc = gnuais_batch_run_wideband(s.b, s.d_wide, len, s.s_in);
+        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
+            return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: copy");
         return rc;
     });
 }

@@ -36,6 +36,12 @@ SYMBOLS = {
     "gnuais_batch_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_iq_host": (_I, [_P, _P, _I]),
     "gnuais_batch_discriminate": (_I, [_P, _P, _I, _P, _P]),
+    "gnuais_batch_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
+    "gnuais_batch_run_wideband": (_I, [_P, _P, _I, _P]),
+    "gnuais_batch_run_wideband_host": (_I, [_P, _P, _I]),
+    "gnuais_batch_channelise": (_I, [_P, _P, _I, _P, _P]),
+    "gnuais_channeliser_default_taps": (_I, [_I, _P, _I, C.POINTER(_I)]),
+    "gnuais_channeliser_mixer_table": (_I, [_I, _I, _P, _I, C.POINTER(_I)]),
     "gnuais_wav_open": (_I, [C.POINTER(_P), C.c_char_p, _I]),
     "gnuais_wav_channels": (_I, [_P]),
     "gnuais_wav_rate": (_I, [_P]),
@@ -99,6 +105,8 @@ SYMBOLS = {
     "gnuais_node_run": (_I, [_P, _P, _I, _P]),
     "gnuais_node_run_iq_host": (_I, [_P, _P, _I]),
     "gnuais_node_run_iq": (_I, [_P, _P, _I, _P]),
+    "gnuais_node_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
+    "gnuais_node_run_wideband_host": (_I, [_P, _P, _I]),
     "gnuais_node_sync": (_I, [_P]),
     "gnuais_node_pending_frames": (_I, [_P, C.POINTER(_I)]),
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),

@@ -114,6 +114,60 @@ class ReceiverBatch:
         stream.synchronize()
         return out
 
+    def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
+        """Configure the wideband channeliser (gnuais_batch_channeliser, defined in include/gnuais_hip.h): the batch's
+        n_channels receivers become n_channels / K wide streams x K offsets (receiver s*K + k = stream s at
+        offsets_hz[k]), decimated by `decim` from `in_rate_hz`.  taps: int16 sequence, or None for the default design.
+        Zeroes the channeliser's carry and sample count."""
+        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        assert off.ndim == 1 and off.size >= 1
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
+        check(self._lib.gnuais_batch_channeliser(self._h, int(decim), int(in_rate_hz), off.ctypes.data, int(off.size),
+                                                 None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
+        self._chan = (int(decim), int(off.size))
+
+    def _wide_shape_ok(self, x, n_rows):
+        if not hasattr(self, "_chan"):                  # not configured: the library says so
+            return x.ndim == 3 and x.shape[2] == 2
+        d, k = self._chan
+        return x.ndim == 3 and x.shape[1] * k == self.n_channels and x.shape[2] == 2 and n_rows % d == 0
+
+    def run_wideband(self, samples, stream: Optional[int] = None, sync: bool = True):
+        """Wideband in (gnuais_batch_run_wideband): samples int16 [len][n_channels / K][2] = (I, Q) of the wide streams,
+        len a multiple of the decimation; channeliser, discriminator and chain on the device.  A CUDA/HIP torch tensor is
+        used in place, asynchronously on `stream` or torch's current stream; a numpy array goes through
+        gnuais_batch_run_wideband_host (copy, run, sync)."""
+        if _is_torch(samples):
+            import torch
+            assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
+            assert self._wide_shape_ok(samples, int(samples.shape[0]))
+            if stream is None:
+                stream = torch.cuda.current_stream(samples.device).cuda_stream
+            check(self._lib.gnuais_batch_run_wideband(self._h, samples.data_ptr(), int(samples.shape[0]),
+                                                      C.c_void_p(stream)))
+            if sync:
+                self.sync()
+        else:
+            x = np.ascontiguousarray(samples, dtype=np.int16)
+            assert self._wide_shape_ok(x, int(x.shape[0]))
+            check(self._lib.gnuais_batch_run_wideband_host(self._h, x.ctypes.data, int(x.shape[0])))
+
+    def channelise(self, samples):
+        """The channeliser alone (gnuais_batch_channelise): int16 [len][n_channels / K][2] -> torch int16
+        [len / D][n_channels][2] on the device; advances the channeliser's state and nothing else."""
+        import torch
+        if not _is_torch(samples):
+            samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16)).to(f"cuda:{self.device}")
+        assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
+        assert self._wide_shape_ok(samples, int(samples.shape[0]))
+        d = getattr(self, "_chan", (1, 1))[0]
+        out = torch.empty((int(samples.shape[0]) // d, self.n_channels, 2), dtype=torch.int16, device=samples.device)
+        stream = torch.cuda.current_stream(samples.device)
+        check(self._lib.gnuais_batch_channelise(self._h, samples.data_ptr(), int(samples.shape[0]), out.data_ptr(),
+                                                C.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        return out
+
     def run_host_async(self, samples: np.ndarray):
         """Host input without waiting for the device: pinned double-buffered staging inside the
         library (gnuais_batch_run_host_async); results after sync()."""

@@ -76,6 +76,22 @@ class ReceiverNode:
         assert x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2
         self._raise(self._lib.gnuais_node_run_iq_host(self._h, x.ctypes.data, int(x.shape[0])))
 
+    def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
+        """Wideband in (gnuais_node_channeliser): ReceiverBatch.channeliser on every shard; every shard's first channel
+        and channel count must be multiples of len(offsets_hz)."""
+        np = self._np
+        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
+        self._raise(self._lib.gnuais_node_channeliser(self._h, int(decim), int(in_rate_hz), off.ctypes.data, int(off.size),
+                                                      None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
+        self._chan_k = int(off.size)
+
+    def run_wideband_host(self, samples):
+        """Wideband in (gnuais_node_run_wideband_host): one host array int16 [len][n_channels / K][2] of wide streams."""
+        x = self._np.ascontiguousarray(samples, dtype=self._np.int16)
+        assert x.ndim == 3 and x.shape[1] * getattr(self, "_chan_k", 1) == self.n_channels and x.shape[2] == 2
+        self._raise(self._lib.gnuais_node_run_wideband_host(self._h, x.ctypes.data, int(x.shape[0])))
+
     def run_iq(self, slabs, streams=None):
         """slabs: one CUDA/HIP int16 tensor [len][n_i][2] of (I, Q) pairs per shard, each on its shard's device."""
         C = self._C

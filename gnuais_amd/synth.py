@@ -156,6 +156,30 @@ def make_iq_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int 
     return np.clip(np.rint(iq), -32768, 32767).astype(np.int16), placed
 
 
+def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz, seed: int = SEED, stream: int = 0,
+                         amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5):
+    """One wide complex stream as an SDR records it: a channel of AIS at each of `offsets_hz` (Hz from the tuned
+    frequency) at `in_rate_hz`, for a channeliser that decimates by `decim` to the chain's rate.
+
+    Offset k carries noise-free make_iq_stream() bursts at sps = 5 * decim from a seed of its own, shifted by
+    e^{+j 2 pi f_k n / R}; the offsets are summed, white Gaussian noise of `sigma` is added to I and Q, and the result is
+    rounded and clamped to int16.  Returns (int16[n_samples][2], [placed payloads of offset k, for each k]).
+    """
+    n = np.arange(n_samples, dtype=np.float64)
+    acc = np.zeros(n_samples, dtype=np.complex128)
+    placed = []
+    for k, f in enumerate(offsets_hz):
+        iq, pl = make_iq_stream(n_samples, seed=seed + 65537 * (k + 1), channel=stream, sps=5 * decim,
+                                amplitude=amplitude, sigma=0.0, occupancy=occupancy)
+        z = iq[:, 0].astype(np.float64) + 1j * iq[:, 1].astype(np.float64)
+        acc += z * np.exp(2j * np.pi * float(f) * n / float(in_rate_hz))
+        placed.append(pl)
+    out = np.stack([acc.real, acc.imag], axis=1)
+    if sigma > 0:
+        out += np.random.default_rng([seed, stream, 0x5744]).normal(0.0, sigma, out.shape)
+    return np.clip(np.rint(out), -32768, 32767).astype(np.int16), placed
+
+
 def make_base_streams(n_base: int, n_samples: int, **kw):
     """[n_base][n_samples] int16 + per-stream placed payload lists."""
     streams = np.empty((n_base, n_samples), dtype=np.int16)

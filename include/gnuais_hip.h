@@ -158,6 +158,55 @@ int  gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *st
 /* the same from a HOST buffer; synchronous (copy, run, sync) */
 int  gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len);
 
+/* ---- wideband in: a channeliser on the device in front of the discriminator ----------------------------------
+ * Not in the reference.  For SDR front ends that record both AIS channels in one complex stream (e.g. tuned to
+ * 162.000 MHz: 87B at -25 kHz, 88B at +25 kHz).  Everything is integer, so the result does not depend on the order of
+ * any sum.
+ *   Shape: the batch's N receivers are M = N/K wide streams times K offsets (N % K == 0, 1 <= K <= 32); the input is
+ *   int16 [len][M][2] (I, Q); receiver c = s*K + k is stream s tuned to offset k.  R = input rate (Hz), D = decimation,
+ *   1 <= D <= 64.  n counts wide samples since the last reset or configuration, across calls.  A call's len is a
+ *   multiple of D and at most D*max_len.
+ *   Mixer of offset f_k (Hz, signed): period P_k = R / gcd(|f_k|, R) (f_k = 0: 1), refused if P_k > 2^20;
+ *     q = (f_k * p) mod R   (exact int64, result in [0, R))
+ *     C_k[p] = rnd(32767.0 * cos(2.0 * pi * q / R)),  S_k[p] = rnd(32767.0 * sin(2.0 * pi * q / R))
+ *   in double (the angle as written, left to right), rnd = round half away from zero (C lround); on the host, once per
+ *   configuration.
+ *   Mix, p = n mod P_k (multiplication by e^{-j theta}):
+ *     u = I*C + Q*S,  v = Q*C - I*S                            exact in int32
+ *     mr = sat16((u + 16384) >> 15),  mi = sat16((v + 16384) >> 15)   >> arithmetic (floor), sat16 clamps to int16
+ *   Filter and decimate with int16 taps h[0..T-1]: narrowband row m of the call is
+ *     acc = sum_j h[j] * mr[m*D + D-1-j]   (mr before the first sample since reset / configuration = 0)
+ *     out_re = sat16((acc + 16384) >> 15), the same for mi -> out_im
+ *   so a call of len wide samples gives len/D rows, the last ending on the call's last sample.
+ *   Taps: 1 <= T <= 1025, |h[j]| <= 32767, sum |h[j]| <= 65535 (else GNUAIS_E_ARG).  Then |u|, |v| <= 2*32768*32767
+ *   < 2^31 and |acc| + 16384 <= 32768*65535 + 16384 < 2^31: every int32 order gives the same bits.
+ *   Default taps (taps == NULL or n_taps == 0): a Blackman-windowed sinc, T = 16D + 1, cutoff 0.375 of the output rate:
+ *     w[j] = 0.42 - 0.5 * cos(2.0 * pi * j / (T-1)) + 0.08 * cos(4.0 * pi * j / (T-1))
+ *     x[j] = 0.75 * (j - 8D) / D;   s[j] = (x[j] == 0) ? 1.0 : sin(pi * x[j]) / (pi * x[j])
+ *     g[j] = w[j] * s[j];   G = g[0] + g[1] + ... + g[T-1] (in that order);   h[j] = rnd(g[j] * 32768.0 / G)
+ *   in double, each expression as written, left to right.  Flat to 10 kHz, -6 dB at 18 kHz and below -66 dB from
+ *   26 kHz at 48 kHz out; sum |h| is about 49 000.
+ * The rows (out_re, out_im) of receiver c then go through the discriminator above (a wideband call is an I/Q call for
+ * its carry) and into the unchanged chain.  Carried per stream: the last T-1 wide samples; per batch: n.  Both are zero
+ * after configuration and gnuais_batch_reset() (which keeps the configuration).  Audio and run_iq calls leave them
+ * alone; all three kinds of call may be mixed on one batch.  A wideband call before gnuais_batch_channeliser() is
+ * GNUAIS_E_ARG. */
+/* configure (synchronises the device): offsets_hz[n_offsets] (n_offsets = K), taps[n_taps] or NULL / 0 = default */
+int  gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                              const int16_t *taps, int n_taps);
+/* d_wide = DEVICE int16 [len][M][2]: channeliser, discriminator and chain; asynchronous on `stream` as gnuais_batch_run_iq
+ * (its narrowband I/Q goes into a batch scratch buffer [max_len][N][2]; a change of stream drains the previous one) */
+int  gnuais_batch_run_wideband(gnuais_batch *b, const int16_t *d_wide, int len, void *stream);
+/* the same from a HOST buffer; synchronous (copy, run, sync) */
+int  gnuais_batch_run_wideband_host(gnuais_batch *b, const int16_t *h_wide, int len);
+/* the channeliser only (a parity tap): d_out DEVICE int16 [len/D][N][2] (must not overlap d_wide); advances the
+ * channeliser's state and nothing else.  Asynchronous on `stream`. */
+int  gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream);
+/* host only, no batch: the default taps for decim into out[cap] (*n_taps = 16*decim + 1), and offset_hz's mixer
+ * table at in_rate_hz, out[cap][2] = (C, S), *period = P */
+int  gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps);
+int  gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period);
+
 /* ---- input side, row f2: sample files -> interleaved int16 frames (src/ais.c:173-182,214-217) ---
  * raw_channels > 0: the file is a bare stream of little-endian int16 frames of that many channels,
  *   header and all, exactly as the reference reads a sound file; 0: parse RIFF/WAVE (16-bit PCM,
@@ -436,6 +485,13 @@ int  gnuais_node_run(gnuais_node *nd, const int16_t *const *d_samples, int len, 
 int  gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len);
 /* the same with the pairs already on the devices: d_iq[i] = shard i's DEVICE slab int16 [len][n_channels of shard i][2] */
 int  gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams);
+/* wideband in (gnuais_batch_channeliser): configures every shard; a shard whose first channel or channel count is not a
+ * multiple of n_offsets is GNUAIS_E_ARG (the message names it) */
+int  gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                             const int16_t *taps, int n_taps);
+/* one HOST buffer int16 [len][N/K][2] of wide streams; every shard copies the columns of its own streams,
+ * [first/K, (first+n)/K), and runs channeliser, discriminator and chain; returns when the buffer may be reused */
+int  gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len);
 int  gnuais_node_sync(gnuais_node *nd);
 /* merged results: records of every device, channel = global index, reference order (channel, then time) */
 int  gnuais_node_pending_frames(gnuais_node *nd, int *n_out);

@@ -3,6 +3,9 @@
   python scripts/decode_file.py capture.wav            # RIFF/WAVE, any channel count
   python scripts/decode_file.py capture.raw --raw 2    # bare int16 frames, as the reference reads them
   python scripts/decode_file.py iq.wav --iq           # complex baseband: 2N channels = N receivers' (I, Q) pairs
+  python scripts/decode_file.py sdr.wav --wideband 6 --offsets -25000,25000
+                                                      # wide I/Q (2M channels = M streams) at R = 6 x 48 kHz, each
+                                                      # stream channelised on the device to one receiver per offset
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -17,12 +20,22 @@ def main():
     ap.add_argument("--text", action="store_true")
     ap.add_argument("--iq", action="store_true", help="the channels are (I, Q) pairs: 2N channels decode as N receivers "
                                                       "through the device's FM discriminator")
-    ap.add_argument("--call", type=int, default=48000, help="frames per device call")
+    ap.add_argument("--wideband", type=int, default=0, metavar="D",
+                    help="the (I, Q) pairs are wide streams at D times the chain's rate: tune to every --offsets, "
+                         "decimate by D on the device, one receiver per stream and offset (receiver s*K + k)")
+    ap.add_argument("--offsets", default="-25000,25000", help="--wideband: offsets in Hz from the tuned frequency")
+    ap.add_argument("--rate", type=int, default=0, help="--wideband with --raw: the input rate in Hz")
+    ap.add_argument("--call", type=int, default=48000, help="frames per device call (at the chain's rate)")
     a = ap.parse_args()
     import torch
     from gnuais_amd import ReceiverBatch, io, messages_from_frames
-    x = io.read_raw(a.path, a.raw) if a.raw else io.read_wav(a.path)[1]
+    if a.raw:
+        rate, x = a.rate, io.read_raw(a.path, a.raw)
+    else:
+        rate, x = io.read_wav(a.path)
     n_ch = x.shape[1]
+    if a.wideband:
+        return decode_wideband(a, rate, x)
     if a.iq:
         if n_ch % 2:
             sys.exit(f"{a.path}: --iq needs an even channel count (I, Q per receiver), the file has {n_ch}")
@@ -41,6 +54,30 @@ def main():
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
+
+
+def decode_wideband(a, rate, x):
+    import torch
+    from gnuais_amd import ReceiverBatch, io, messages_from_frames
+    D = a.wideband
+    offsets = [int(v) for v in a.offsets.split(",") if v.strip()]
+    if x.shape[1] % 2:
+        sys.exit(f"{a.path}: --wideband needs an even channel count (I, Q per stream), the file has {x.shape[1]}")
+    if rate <= 0 or rate % D or rate // D != 48000:
+        sys.exit(f"{a.path}: input rate {rate} Hz / {D} is not the chain's 48000 Hz (--rate for raw files)")
+    M = x.shape[1] // 2
+    n_ch = M * len(offsets)
+    x = x[: x.shape[0] // D * D].reshape(-1, M, 2)
+    b = ReceiverBatch(n_ch, max_len=a.call)
+    b.channeliser(D, rate, offsets)
+    seq = np.zeros(n_ch, dtype=np.uint8)
+    for part in io.chunks(x, a.call * D):
+        b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda())
+        nmea, text = messages_from_frames(b.drain_frames(), seq)
+        sys.stdout.write((text if a.text else nmea).decode("ascii", "replace"))
+    c = b.counters()
+    sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
+                     f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
 
 
 if __name__ == "__main__":
