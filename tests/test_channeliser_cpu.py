@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import chan_cases
 import chan_ref
 import iq_ref
 from gnuais_amd import synth
@@ -204,3 +205,106 @@ def test_channeliser_build_is_checked_and_uses_dot2():
     if os.path.exists(s_path):
         isa = open(s_path).read()
         assert "v_dot2c_i32_i16" in isa or "v_dot2_i32_i16" in isa
+
+
+# ---- the configuration matrix (tests/chan_cases.py) and the references the device is held to ----
+
+def test_the_matrix_picks_the_forms_it_names():
+    """fast_na restates channeliser_fast_na(): buckets 4 / 8 / 17, 33 for K <= 2, else 0 = the direct form"""
+    assert [chan_ref.fast_na(1, T, 1) for T in (1, 4, 5, 8, 9, 17, 18, 33, 34)] == [4, 4, 8, 8, 17, 17, 33, 33, 0]
+    assert [chan_ref.fast_na(3, T, 1) for T in (17, 18)] == [17, 0]
+    assert chan_ref.fast_na(5, 1, 1) == 0 and chan_ref.fast_na(0, 1, 1) == 0
+    for c in chan_cases.CASES:
+        assert chan_ref.fast_na(c.K, c.T, c.D) == c.na, c.name
+        assert (c.na == 0) == bool(c.direct_reason), c.name
+        assert c.taps.size == c.T and np.abs(c.taps.astype(np.int64)).sum() <= 65535, c.name
+        assert all(chan_ref.period(c.R, f) <= 1 << 20 for f in c.offsets), c.name
+    got = {(c.K, c.na) for c in chan_cases.CASES if c.na}
+    assert got == {(K, na) for K in (1, 2, 3, 4) for na in (4, 8, 17, 33) if na != 33 or K <= 2}
+    assert {c.direct_reason for c in chan_cases.CASES} == {"", "K>4", "ceil(T/D)>33", "ceil(T/D)>17,K>2"}
+    assert {c.D for c in chan_cases.CASES} >= {1, 2, 3, 5, 7, 9, 16, 32, 63, 64}
+    assert {c.M for c in chan_cases.CASES} >= {1, 63, 64, 65, 4096}
+    assert max(c.T for c in chan_cases.CASES) == 1025
+    top = {c.T // c.D for c in chan_cases.CASES if c.T % c.D == 0}                # T = b*D: ceil(T/D) = b
+    bottom = {(c.T - 1) // c.D for c in chan_cases.CASES if (c.T - 1) % c.D == 0}   # T = b*D + 1: b + 1
+    assert {4, 8, 17, 33} <= top and {4, 8, 17, 33} <= bottom, (top, bottom)
+
+
+def test_the_matrix_reaches_every_instance_in_the_build():
+    """Every channeliser_kernel<K, NA> the build holds is reached by a case of the matrix, and the direct and carry
+    kernels are there: a new bucket or instance fails here until the matrix tests it."""
+    import re
+    s_path = os.path.join(ROOT, "gnuais_amd", "csrc", "build", "channeliser.s")
+    if not os.path.exists(s_path):
+        pytest.skip("channeliser.s not built (make -C gnuais_amd/csrc)")
+    isa = open(s_path).read()
+    built = {(int(k), int(na)) for k, na in re.findall(r"channeliser_kernelILi(\d+)ELi(\d+)EEEv", isa)}
+    assert len(built) == 14, sorted(built)
+    assert built == {(c.K, c.na) for c in chan_cases.CASES if c.na}
+    assert "channeliser_direct_kernel" in isa and "channeliser_carry_kernel" in isa
+    assert {c.direct_reason for c in chan_cases.CASES if not c.na} == {"K>4", "ceil(T/D)>33", "ceil(T/D)>17,K>2"}
+
+
+@pytest.mark.parametrize("case", chan_cases.CASES, ids=chan_cases.CASE_IDS)
+def test_restatement_within_the_bound_of_float64_math(case):
+    """chan_ref over ragged calls against chan_ref.ideal() over the whole stream in float64 with no rounding.  Where
+    nothing saturates, each component is within chan_cases.ideal_bound(h) = 1.5 sum |h| / 32768 + 0.5 of the ideal:
+    the mixer table's C and S are each within 0.5 of 32767 cos, 32767 sin, so u = I C + Q S is within
+    0.5 (|I| + |Q|) <= 32768 of 32767 (I cos + Q sin), 1.0 after the division by 32768; rounding the mix adds 0.5; the
+    filter sums those errors weighted by |h[j]| / 32768 and rounds once more (0.5).  A wrong tap orientation, row
+    phase (the last row ends on the call's last sample) or phase across calls is off by thousands.  The errors are
+    rounding errors of both signs: their mean is near zero."""
+    M = min(case.M, 2)
+    h = case.taps
+    x = chan_cases.unsaturated_wide(np.random.default_rng(case.T * 7 + case.D), sum(case.chunks), M, h)
+    ch = chan_ref.Channeliser(M, case.D, case.R, case.offsets, taps=h)
+    parts, pos = [], 0
+    for n in case.chunks:
+        parts.append(ch.run(x[pos:pos + n]))
+        pos += n
+    err = chan_cases.ideal_errors(np.concatenate(parts), chan_ref.ideal(x, case.D, case.R, case.offsets, h))
+    bound = chan_cases.ideal_bound(h)
+    assert np.abs(err).max() <= bound, (case.name, np.abs(err).max(), bound)
+    assert abs(err.mean()) < 0.05, (case.name, err.mean())
+    if err.size > 20000:
+        assert np.abs(err).max() > 0.5                  # the check sees rounding at all
+
+
+def test_ideal_bound_catches_a_reversed_filter_and_a_late_row():
+    """the float64 check would fail if the restatement read its taps backwards or ended a row one sample late"""
+    D, R, offs = 5, 240000, (-25000, 25000)
+    h = chan_cases.make_taps("asym", 40, D, seed=1)
+    x = chan_cases.unsaturated_wide(np.random.default_rng(2), D * 200, 2, h)
+    y = chan_ref.ideal(x, D, R, offs, h)
+    bound = chan_cases.ideal_bound(h)
+    rev = chan_ref.Channeliser(2, D, R, offs, taps=h[::-1].copy()).run(x)
+    assert np.abs(chan_cases.ideal_errors(rev, y)).max() > 10 * bound
+    late = chan_ref.Channeliser(2, D, R, offs, taps=h).run(np.concatenate([np.zeros((1, 2, 2), np.int16), x[:-1]]))
+    assert np.abs(chan_cases.ideal_errors(late, chan_ref.ideal(x, D, R, offs, h))).max() > 10 * bound
+
+
+@pytest.mark.parametrize("name", ["k1_na4_T1", "k2_na4", "k3_na17_top", "k4_na8", "k5_direct", "k32_direct"])
+def test_torch_reference_equals_the_restatement(name):
+    """chan_ref.torch_channelise (the W3 test's reference on the device) against chan_ref on the CPU, one call from
+    reset, with chunks smaller than M"""
+    import torch
+    c = {c.name: c for c in chan_cases.CASES}[name]
+    M = min(c.M, 5)
+    x = chan_cases.hard_wide(np.random.default_rng(c.T), c.D * 60, M)
+    want = chan_ref.Channeliser(M, c.D, c.R, c.offsets, taps=c.taps).run(x)
+    got = chan_ref.torch_channelise(torch.from_numpy(x), c.D, c.R, c.offsets, c.taps, chunk=2)
+    assert got.dtype == torch.int16 and np.array_equal(got.numpy(), want)
+
+
+def test_rounding_ties_go_up_in_both_stages():
+    """(x + 16384) >> 15 rounds a tie towards +infinity: offset 0 (C = 32767, S = 0) makes I = 16384 a tie in the
+    mix (16383.5 -> 16384) and I = -16384 one (-16383.5 -> -16383); taps [16384] make every odd mixed value a tie of
+    the filter (mr / 2)"""
+    ch = chan_ref.Channeliser(1, 1, 48000, [0], taps=np.array([16384], dtype=np.int16))
+    I = np.array([16384, -16384, 3, -3, 1, -1, 32767, -32768, 5, -5], dtype=np.int16)
+    x = np.stack([I, -I], axis=1)[:, None, :]
+    mr, mi = ch.mix(x, 0)
+    assert list(mr[:2, 0, 0]) == [16384, -16383]
+    out = ch.run(x)[:, 0, :].astype(np.int64)
+    assert np.array_equal(out[:, 0], (mr[:, 0, 0] + 1) // 2) and np.array_equal(out[:, 1], (mi[:, 0, 0] + 1) // 2)
+    assert (mr[:, 0, 0] % 2 == 1).any() and ((mr[:, 0, 0] % 2 == 1) & (mr[:, 0, 0] < 0)).any()

@@ -221,7 +221,8 @@ def test_node_two_shards_equal_one_batch_and_misaligned_shards_are_refused():
 
 def test_w3_shape_in_one_call():
     """8192 streams x K = 2 x D = 6, 288 000 wide samples in one call (C3's 16 384 x 48 000 out); 16 sampled streams
-    bit for bit against the restatement."""
+    bit for bit against the restatement, and all 8192 x 2 against chan_ref.torch_channelise, the same definition in
+    torch's int64 operations on the device (pinned to the restatement by test_channeliser_cpu.py)."""
     import torch
     from gnuais_amd import ReceiverBatch
     M, K, D, n = 8192, 2, 6, 288000
@@ -238,6 +239,13 @@ def test_w3_shape_in_one_call():
     cols = (pick[:, None] * K + np.arange(K)[None, :]).reshape(-1)
     got = out[:, torch.from_numpy(cols).to(out.device)].cpu().numpy()
     assert np.array_equal(got, want)
+    del got, sub
+    full = chan_ref.torch_channelise(xd, D, 48000 * D, [-25000, 25000], chan_ref.default_taps(D), chunk=512)
+    assert full.shape == out.shape
+    bad = int((full != out).sum())
+    del full, out, xd
+    torch.cuda.empty_cache()
+    assert bad == 0, bad
 
 
 def test_decode_file_wideband_equals_the_iq_path(tmp_path):
