@@ -54,6 +54,12 @@ static const double k_tap_half[18] = {
     2.5280e-24, 2.0934e-20, 7.6339e-17, 1.2259e-13, 8.6690e-11, 2.6996e-08,
     3.7020e-06, 2.2355e-04, 5.9448e-03, 6.9616e-02, 3.5899e-01, 8.1522e-01};
 
+// The stages a call may pass through, in launch order: the channeliser, the discriminator, the chain (K1 .. K3)
+enum Stage { CHAN, DISC, CHAIN, N_STAGES };
+
+// The input forms (include/gnuais_hip.h): audio [len][N], I/Q [len][N][2], wideband [len][N/K][2]
+enum FormId { AUDIO, IQ, WIDE };
+
 struct gnuais_batch {
     int device = 0;
     int N = 0, NT = 0, NE = 0, d = 0;
@@ -198,7 +204,13 @@ struct gnuais_batch {
     unsigned long long timed_calls = 0;
     int last_k = 0;
     bool timed_last = false;
-    hipStream_t last_stream = nullptr;
+    // The drain rule: each stage keeps the stream of its last launch here (last[CHAIN].s is also the stream that
+    // gnuais_batch_sync drains).  Before a call launches anything on stream s, it drains the recorded stream of every
+    // stage it passes through, when that stream is not s (drain()).  This covers two hazards.  A stage's carry goes
+    // from launch to launch in stream order: the channeliser's history, the discriminator's previous pair, the chain's
+    // FIR history and peaks.  And a stage in front of the chain overwrites an intermediate buffer whose reader is the
+    // next stage of the previous call, on that call's stream: ch_iq is read by the discriminator, iq_audio by K1.
+    struct { hipStream_t s = nullptr; bool used = false; } last[N_STAGES];
     int last_len = 0;
     // K3 on the deframer's stream: at ring lag 1 the two never overlap (deframer(i) -> K3(i) -> deframer(i+1)), so the two
     // cross-stream event waits per call in the loop that sets the period become stream order: 20-step 0.550 -> 0.544,
@@ -206,11 +218,8 @@ struct gnuais_batch {
     int k3_same = 1;
     // complex baseband in (gnuais_batch_run_iq / _discriminate, iq_disc.hip): the discriminator's carry -- the last (I, Q)
     // pair an I/Q call saw, per channel -- and the audio it writes for the chain, [max_len][N] (allocated on first use).
-    // The audio's only reader is K1 of the same call, on the same stream (see e_in_hook).
     int16_t *iq_prev = nullptr;                 // [N][2]
     int16_t *iq_audio = nullptr;
-    hipStream_t iq_stream = nullptr;            // the stream of the last discriminator launch
-    bool iq_used = false;                       // a discriminator has been launched since create / reset
     // wideband in (gnuais_batch_channeliser / _run_wideband, channeliser.hip): the configuration, the device tables, the
     // carry (the last T-1 wide samples of each stream, double-buffered: a launch reads one and writes the other), the
     // wide-sample count n and the narrowband I/Q it writes for the discriminator, [max_len][N][2] (allocated on first use).
@@ -221,9 +230,65 @@ struct gnuais_batch {
     int ch_cur = 0;
     unsigned long long ch_n = 0;
     int16_t *ch_iq = nullptr;
-    hipStream_t ch_stream = nullptr;            // the stream of the last channeliser launch
-    bool ch_used = false;
 };
+
+// Per chain row, `rows` input rows of `cols` columns of `bytes` bytes each; `stages`: bit s = the call passes stage s
+struct Form {
+    int bytes, cols, rows;
+    unsigned stages;
+    size_t bytes_of(int in_rows) const { return (size_t) bytes * (size_t) cols * (size_t) in_rows; }
+};
+
+static Form form(const gnuais_batch *b, FormId f)
+{
+    switch (f) {
+    case AUDIO: return {2, b->N, 1, 1u << CHAIN};
+    case IQ: return {4, b->N, 1, 1u << DISC | 1u << CHAIN};
+    default: return {4, b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | 1u << DISC | 1u << CHAIN};
+    }
+}
+
+// The drain rule (gnuais_batch::last): drains the recorded stream of each stage in `stages` that is not s.  The
+// stage's earlier launches are then done, so s stands for them from here on.
+static int drain(gnuais_batch *b, unsigned stages, hipStream_t s)
+{
+    for (int q = 0; q < N_STAGES; ++q) {
+        auto &l = b->last[q];
+        if (!(stages >> q & 1u) || !l.used || l.s == s) continue;
+        HIP_TRY(hipStreamSynchronize(l.s));
+        l.s = s;
+    }
+    return GNUAIS_OK;
+}
+
+// Device scratch that grows on demand: when `need` exceeds the `have` bytes it holds, it is freed and allocated anew
+// with `need + slack` bytes
+template <class T>
+static int grow(T *&p, size_t &have, size_t need, size_t slack = 0)
+{
+    if (have >= need) return GNUAIS_OK;
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    have = 0;
+    HIP_TRY(hipMalloc((void **) &p, need + slack));
+    have = need + slack;
+    return GNUAIS_OK;
+}
+
+// An intermediate buffer of `bytes`, allocated on first use once the device has room for it: `what` of N x max_len
+static int alloc_checked(gnuais_batch *b, int16_t *&p, size_t bytes, const char *who, const char *what)
+{
+    if (p) return GNUAIS_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: %s for %d channels x %d samples needs %.2f GB of device memory, device %d has %.2f "
+                 "GB free of %.2f", who, what, b->N, b->max_len, bytes / 1e9, b->device, free_b / 1e9, total_b / 1e9);
+        return fail(GNUAIS_E_HIP, msg);
+    }
+    HIP_TRY(hipMalloc((void **) &p, bytes));
+    return GNUAIS_OK;
+}
 
 static int set_device(const gnuais_batch *b)
 {
@@ -637,7 +702,7 @@ static int chan_zero_state(gnuais_batch *b)
             if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) (b->ch_T - 1) * (size_t) (b->N / b->ch_K)));
     b->ch_cur = 0;
     b->ch_n = 0;
-    b->ch_used = false;
+    b->last[CHAN].used = false;
     return GNUAIS_OK;
 }
 
@@ -656,6 +721,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     for (int k = 0; k < b->sets_alloc; ++k)
         HIP_TRY(hipMemset(b->segcnt[k], 0, sizeof(uint32_t) * N * (size_t) b->n_seg));
     b->calls = 0;
+    b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
     for (int q = 0; q < gnuais_batch::HB; ++q) HIP_TRY(hipMemset(b->maxval[q], 0, sizeof(int) * N));
@@ -671,7 +737,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->stream_calls = 0;
     HIP_TRY(launch_hdlc_reset(b->ctl, b->N, nullptr));                // protodec.c:87-100
     HIP_TRY(hipMemset(b->iq_prev, 0, sizeof(int16_t) * 2 * N));       // the discriminator's previous pair: (0, 0)
-    b->iq_used = false;
+    b->last[DISC].used = false;
     if (int rc = chan_zero_state(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
@@ -944,9 +1010,8 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
         // depth 3, where this wait IS the loop: ONE wait packet on the caller's stream instead, the host held back only
         // by that call's FIR launch -- 0.583 against 0.542 ms per step, profiles/r04_k3_on_the_deframers_stream.txt.)
         if (reuse) HIP_TRY(hipEventSynchronize(b->e_done[4][k]));
-        // K1 carries the FIR history and the peak buffers from call to call in stream order: a caller
-        // that changes streams between calls gets the old stream drained first
-        if (b->calls > 0 && s0 != b->last_stream) HIP_TRY(hipStreamSynchronize(b->last_stream));
+        // K1 carries the FIR history and the peak buffers from call to call in stream order (the drain rule)
+        if (int rc = drain(b, 1u << CHAIN, s0)) return rc;
         hipStream_t sF = s0;
         if (tm) HIP_TRY(hipEventRecord(ev[0], sF));
         if (b->stage_mask & 1)
@@ -971,7 +1036,7 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
 
     b->timed_last = tm;
     if (tm) b->timed_calls++;
-    b->last_stream = s0;
+    b->last[CHAIN] = {s0, true};
     b->last_len = len;
     b->last_k = k;
     b->calls++;
@@ -1081,19 +1146,8 @@ int gnuais_batch_sync(gnuais_batch *b)
 {
     if (!b) return fail(GNUAIS_E_ARG, "sync: NULL batch");
     if (int rc = set_device(b)) return rc;
-    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    HIP_TRY(hipStreamSynchronize(b->last[CHAIN].s));
     for (auto &st : b->s_k) HIP_TRY(hipStreamSynchronize(st));
-    return GNUAIS_OK;
-}
-
-static int ensure_stage(gnuais_batch *b, size_t bytes)
-{
-    if (b->stage_bytes >= bytes) return GNUAIS_OK;
-    if (b->stage_x) HIP_TRY(hipFree(b->stage_x));
-    b->stage_x = nullptr;
-    b->stage_bytes = 0;
-    HIP_TRY(hipMalloc((void **) &b->stage_x, bytes));
-    b->stage_bytes = bytes;
     return GNUAIS_OK;
 }
 
@@ -1166,18 +1220,6 @@ int gnuais_batch_autotune_delivery(gnuais_batch *b, const int16_t *d_samples, in
     return gnuais_batch_reset(b);
 }
 
-int gnuais_batch_run_host(gnuais_batch *b, const int16_t *h_samples, int len)
-{
-    if (!b || !h_samples) return fail(GNUAIS_E_ARG, "run_host: NULL argument");
-    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_host: len out of range");
-    if (int rc = set_device(b)) return rc;
-    const size_t bytes = sizeof(int16_t) * (size_t) len * (size_t) b->N;
-    if (int rc = ensure_stage(b, bytes)) return rc;
-    HIP_TRY(hipMemcpy(b->stage_x, h_samples, bytes, hipMemcpyHostToDevice));
-    if (int rc = gnuais_batch_run(b, b->stage_x, len, nullptr)) return rc;
-    return gnuais_batch_sync(b);
-}
-
 int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int len)
 {
     if (!b || !h_samples) return fail(GNUAIS_E_ARG, "run_host_async: NULL argument");
@@ -1222,14 +1264,10 @@ int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int l
 
 // ---- complex baseband in (include/gnuais_hip.h): the discriminator (iq_disc.hip) in front of the unchanged chain ----
 
-// The carry goes from launch to launch in stream order; a discriminator on another stream than the last one waits for
-// that one on the host first (as gnuais_batch_run does for the chain's own carries).
-static int iq_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s)
+static int disc_launch(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s)
 {
-    if (b->iq_used && s != b->iq_stream) HIP_TRY(hipStreamSynchronize(b->iq_stream));
     HIP_TRY(launch_iq_discriminator(d_iq, d_out, b->iq_prev, b->N, len, s));
-    b->iq_stream = s;
-    b->iq_used = true;
+    b->last[DISC] = {s, true};
     return GNUAIS_OK;
 }
 
@@ -1238,45 +1276,8 @@ int gnuais_batch_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int
     if (!b || !d_iq || !d_out) return fail(GNUAIS_E_ARG, "discriminate: NULL argument");
     if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "discriminate: len out of range (max_len)");
     if (int rc = set_device(b)) return rc;
-    return iq_discriminate(b, d_iq, len, d_out, (hipStream_t) stream);
-}
-
-int gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *stream)
-{
-    if (!b || !d_iq) return fail(GNUAIS_E_ARG, "run_iq: NULL argument");
-    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_iq: len out of range (max_len)");
-    if (int rc = set_device(b)) return rc;
-    hipStream_t s0 = (hipStream_t) stream;
-    if (!b->iq_audio) {
-        const size_t need = sizeof(int16_t) * (size_t) b->max_len * (size_t) b->N;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-            char msg[256];
-            snprintf(msg, sizeof msg, "run_iq: the discriminator's audio for %d channels x %d samples needs %.2f GB of device "
-                     "memory, device %d has %.2f GB free of %.2f", b->N, b->max_len, need / 1e9, b->device, free_b / 1e9,
-                     total_b / 1e9);
-            return fail(GNUAIS_E_HIP, msg);
-        }
-        HIP_TRY(hipMalloc((void **) &b->iq_audio, need));
-    }
-    // One audio buffer serves every call: its reader, K1, runs on the stream of its call, so the next discriminator on
-    // that stream is ordered behind it.  On ANOTHER stream it is not -- and gnuais_batch_run drains the previous stream
-    // only once it is entered, after this discriminator would have overwritten the audio -- so drain it here.
-    if (b->calls > 0 && s0 != b->last_stream) HIP_TRY(hipStreamSynchronize(b->last_stream));
-    if (int rc = iq_discriminate(b, d_iq, len, b->iq_audio, s0)) return rc;
-    return gnuais_batch_run(b, b->iq_audio, len, stream);
-}
-
-int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
-{
-    if (!b || !h_iq) return fail(GNUAIS_E_ARG, "run_iq_host: NULL argument");
-    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_iq_host: len out of range");
-    if (int rc = set_device(b)) return rc;
-    const size_t bytes = sizeof(int16_t) * 2 * (size_t) len * (size_t) b->N;
-    if (int rc = ensure_stage(b, bytes)) return rc;
-    HIP_TRY(hipMemcpy(b->stage_x, h_iq, bytes, hipMemcpyHostToDevice));
-    if (int rc = gnuais_batch_run_iq(b, b->stage_x, len, nullptr)) return rc;
-    return gnuais_batch_sync(b);
+    if (int rc = drain(b, 1u << DISC, (hipStream_t) stream)) return rc;
+    return disc_launch(b, d_iq, len, d_out, (hipStream_t) stream);
 }
 
 // ---- wideband in (include/gnuais_hip.h): the channeliser (channeliser.hip) in front of the discriminator ----
@@ -1431,34 +1432,31 @@ int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const i
     return GNUAIS_OK;
 }
 
-static int chan_check(gnuais_batch *b, const int16_t *d_wide, int len, const char *who)
+// The checks of the entries that take a form's input, in the name of the entry `who` (the device entries of the
+// narrowband forms add "(max_len)" to the len message, as gnuais_batch_run does)
+static int check_input(const gnuais_batch *b, FormId id, const int16_t *x, int len, const char *who, bool host)
 {
     char msg[200];
-    if (!b || !d_wide) {
+    if (!b || !x) {
         snprintf(msg, sizeof msg, "%s: NULL argument", who);
-        return fail(GNUAIS_E_ARG, msg);
-    }
-    if (!b->ch_K) {
+    } else if (id != WIDE) {
+        if (len > 0 && len <= b->max_len) return GNUAIS_OK;
+        snprintf(msg, sizeof msg, "%s: len out of range%s", who, host ? "" : " (max_len)");
+    } else if (!b->ch_K) {
         snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
-        return fail(GNUAIS_E_ARG, msg);
-    }
-    if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
+    } else if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
         snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
                  len, b->ch_D, b->ch_D);
-        return fail(GNUAIS_E_ARG, msg);
-    }
-    if (reinterpret_cast<uintptr_t>(d_wide) % 4) {
+    } else if (reinterpret_cast<uintptr_t>(x) % 4) {
         snprintf(msg, sizeof msg, "%s: the wide samples must be 4-byte aligned", who);
-        return fail(GNUAIS_E_ARG, msg);
+    } else {
+        return GNUAIS_OK;
     }
-    return GNUAIS_OK;
+    return fail(GNUAIS_E_ARG, msg);
 }
 
-// The carry goes from launch to launch in stream order; a channeliser on another stream than the last one waits for that
-// one on the host first (as iq_discriminate does).
 static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, hipStream_t s)
 {
-    if (b->ch_used && s != b->ch_stream) HIP_TRY(hipStreamSynchronize(b->ch_stream));
     ChanLaunch a{};
     a.in = reinterpret_cast<const uint32_t *>(d_wide);
     a.out = reinterpret_cast<uint32_t *>(d_out);
@@ -1483,53 +1481,86 @@ static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t 
     HIP_TRY(launch_channeliser(a, b->ch_hist[b->ch_cur ^ 1], s));
     if (b->ch_T > 1) b->ch_cur ^= 1;
     b->ch_n += (unsigned long long) len;
-    b->ch_stream = s;
-    b->ch_used = true;
+    b->last[CHAN] = {s, true};
     return GNUAIS_OK;
 }
 
 int gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream)
 {
-    if (int rc = chan_check(b, d_wide, len, "channelise")) return rc;
+    if (int rc = check_input(b, WIDE, d_wide, len, "channelise", false)) return rc;
     if (!d_out) return fail(GNUAIS_E_ARG, "channelise: NULL argument");
     if (int rc = set_device(b)) return rc;
+    if (int rc = drain(b, 1u << CHAN, (hipStream_t) stream)) return rc;
     return chan_launch(b, d_wide, len, d_out, (hipStream_t) stream);
+}
+
+// ---- one run path and one host path for every input form ----
+
+// gnuais_batch_run_iq / _run_wideband: on the caller's stream, the stages in front of the chain, each into the
+// intermediate buffer that the next one reads, then gnuais_batch_run on the audio
+static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void *stream, const char *who)
+{
+    if (int rc = check_input(b, id, x, len, who, false)) return rc;
+    if (int rc = set_device(b)) return rc;
+    const Form f = form(b, id);
+    const bool chan = f.stages >> CHAN & 1u, disc = f.stages >> DISC & 1u;
+    hipStream_t s = (hipStream_t) stream;
+    if (int rc = drain(b, f.stages, s)) return rc;
+    // the channeliser writes max_len rows of the I/Q form, the discriminator max_len rows of the audio form
+    if (chan)
+        if (int rc = alloc_checked(b, b->ch_iq, form(b, IQ).bytes_of(b->max_len), who, "the channeliser's I/Q")) return rc;
+    if (disc)
+        if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the discriminator's audio"))
+            return rc;
+    if (chan) {
+        if (int rc = chan_launch(b, x, len, b->ch_iq, s)) return rc;
+        x = b->ch_iq;
+    }
+    len /= f.rows;
+    if (disc) {
+        if (int rc = disc_launch(b, x, len, b->iq_audio, s)) return rc;
+        x = b->iq_audio;
+    }
+    return gnuais_batch_run(b, x, len, stream);
+}
+
+// gnuais_batch_run_host / _run_iq_host / _run_wideband_host: the host input staged in stage_x, then `run`, the
+// device entry of the same form, on the NULL stream, then a sync
+static int run_staged(gnuais_batch *b, FormId id, const int16_t *h, int len, const char *who,
+                      int (*run)(gnuais_batch *, const int16_t *, int, void *))
+{
+    if (int rc = check_input(b, id, h, len, who, true)) return rc;
+    if (int rc = set_device(b)) return rc;
+    const size_t bytes = form(b, id).bytes_of(len);
+    if (int rc = grow(b->stage_x, b->stage_bytes, bytes)) return rc;
+    HIP_TRY(hipMemcpy(b->stage_x, h, bytes, hipMemcpyHostToDevice));
+    if (int rc = run(b, b->stage_x, len, nullptr)) return rc;
+    return gnuais_batch_sync(b);
+}
+
+int gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *stream)
+{
+    return run_form(b, IQ, d_iq, len, stream, "run_iq");
 }
 
 int gnuais_batch_run_wideband(gnuais_batch *b, const int16_t *d_wide, int len, void *stream)
 {
-    if (int rc = chan_check(b, d_wide, len, "run_wideband")) return rc;
-    if (int rc = set_device(b)) return rc;
-    hipStream_t s0 = (hipStream_t) stream;
-    if (!b->ch_iq) {
-        const size_t need = sizeof(int16_t) * 2 * (size_t) b->max_len * (size_t) b->N;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-            char msg[256];
-            snprintf(msg, sizeof msg, "run_wideband: the channeliser's I/Q for %d channels x %d samples needs %.2f GB of "
-                     "device memory, device %d has %.2f GB free of %.2f", b->N, b->max_len, need / 1e9, b->device,
-                     free_b / 1e9, total_b / 1e9);
-            return fail(GNUAIS_E_HIP, msg);
-        }
-        HIP_TRY(hipMalloc((void **) &b->ch_iq, need));
-    }
-    // The I/Q buffer's only reader is the discriminator of the same call, on the same stream.  On another stream the
-    // previous call's discriminator (and FIR) may still run: drain it before this channeliser overwrites the buffer.
-    if (b->calls > 0 && s0 != b->last_stream) HIP_TRY(hipStreamSynchronize(b->last_stream));
-    if (b->iq_used && s0 != b->iq_stream) HIP_TRY(hipStreamSynchronize(b->iq_stream));
-    if (int rc = chan_launch(b, d_wide, len, b->ch_iq, s0)) return rc;
-    return gnuais_batch_run_iq(b, b->ch_iq, len / b->ch_D, stream);
+    return run_form(b, WIDE, d_wide, len, stream, "run_wideband");
+}
+
+int gnuais_batch_run_host(gnuais_batch *b, const int16_t *h_samples, int len)
+{
+    return run_staged(b, AUDIO, h_samples, len, "run_host", gnuais_batch_run);
+}
+
+int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
+{
+    return run_staged(b, IQ, h_iq, len, "run_iq_host", gnuais_batch_run_iq);
 }
 
 int gnuais_batch_run_wideband_host(gnuais_batch *b, const int16_t *h_wide, int len)
 {
-    if (int rc = chan_check(b, h_wide, len, "run_wideband_host")) return rc;
-    if (int rc = set_device(b)) return rc;
-    const size_t bytes = sizeof(int16_t) * 2 * (size_t) len * (size_t) (b->N / b->ch_K);
-    if (int rc = ensure_stage(b, bytes)) return rc;
-    HIP_TRY(hipMemcpy(b->stage_x, h_wide, bytes, hipMemcpyHostToDevice));
-    if (int rc = gnuais_batch_run_wideband(b, b->stage_x, len, nullptr)) return rc;
-    return gnuais_batch_sync(b);
+    return run_staged(b, WIDE, h_wide, len, "run_wideband_host", gnuais_batch_run_wideband);
 }
 
 int gnuais_batch_filter(gnuais_batch *b, const int16_t *d_samples, int len, float *d_out,
@@ -1541,7 +1572,7 @@ int gnuais_batch_filter(gnuais_batch *b, const int16_t *d_samples, int len, floa
     hipStream_t s = (hipStream_t) stream;
     if (int rc = gnuais_batch_sync(b)) return rc;       // the sign-word scratch is shared
     if (int rc = run_fir(b, d_samples, len, d_out, s, (int) (b->calls % (unsigned) b->nbuf))) return rc;
-    b->last_stream = s;
+    b->last[CHAIN].s = s;
     b->timed_last = false;
     return GNUAIS_OK;
 }
@@ -1554,20 +1585,8 @@ int gnuais_batch_filter_host(gnuais_batch *b, const int16_t *h_samples, int len,
     if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "filter_host: len out of range");
     if (int rc = set_device(b)) return rc;
     const size_t n = (size_t) len * (size_t) b->N;
-    if (b->stage_bytes < n * sizeof(int16_t)) {
-        if (b->stage_x) HIP_TRY(hipFree(b->stage_x));
-        b->stage_x = nullptr;
-        b->stage_bytes = 0;
-        HIP_TRY(hipMalloc((void **) &b->stage_x, n * sizeof(int16_t)));
-        b->stage_bytes = n * sizeof(int16_t);
-    }
-    if (b->stage_f_bytes < n * sizeof(float)) {
-        if (b->stage_f) HIP_TRY(hipFree(b->stage_f));
-        b->stage_f = nullptr;
-        b->stage_f_bytes = 0;
-        HIP_TRY(hipMalloc((void **) &b->stage_f, n * sizeof(float)));
-        b->stage_f_bytes = n * sizeof(float);
-    }
+    if (int rc = grow(b->stage_x, b->stage_bytes, n * sizeof(int16_t))) return rc;
+    if (int rc = grow(b->stage_f, b->stage_f_bytes, n * sizeof(float))) return rc;
     HIP_TRY(hipMemcpy(b->stage_x, h_samples, n * sizeof(int16_t), hipMemcpyHostToDevice));
     if (int rc = gnuais_batch_filter(b, b->stage_x, len, b->stage_f, nullptr)) return rc;
     if (int rc = gnuais_batch_sync(b)) return rc;
@@ -1612,7 +1631,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
     }
-    b->last_stream = nullptr;
+    b->last[CHAIN].s = nullptr;
     return GNUAIS_OK;
 }
 
@@ -1646,21 +1665,8 @@ int gnuais_batch_last_bits(gnuais_batch *b, uint8_t *h_bits, int stride, int32_t
 static int ensure_post_buffers(gnuais_batch *b, uint32_t have)
 {
     const size_t need_text = (size_t) have * 164, need_scratch = nmea_scratch_bytes((int) have);
-    if (b->d_text_bytes < need_text) {
-        if (b->d_text) (void) hipFree(b->d_text);
-        b->d_text = nullptr;
-        b->d_text_bytes = 0;
-        HIP_TRY(hipMalloc((void **) &b->d_text, need_text));
-        b->d_text_bytes = need_text;
-    }
-    if (b->nmea_scratch_bytes < need_scratch) {
-        if (b->nmea_scratch) (void) hipFree(b->nmea_scratch);
-        b->nmea_scratch = nullptr;
-        b->nmea_scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&b->nmea_scratch, need_scratch));
-        b->nmea_scratch_bytes = need_scratch;
-    }
-    return GNUAIS_OK;
+    if (int rc = grow(b->d_text, b->d_text_bytes, need_text)) return rc;
+    return grow(b->nmea_scratch, b->nmea_scratch_bytes, need_scratch);
 }
 
 // drain: records and / or sentences of everything queued, consumed once
@@ -1744,13 +1750,7 @@ int gnuais_batch_drain_messages(gnuais_batch *b, uint8_t *seqnr, const char *cha
         if (int rc = ensure_post_buffers(b, have)) return rc;
         // lines at a fixed stride, their lengths and offsets, the packed text, two info words, the channel names
         const size_t need = (size_t) have * line * 2 + (size_t) have * 8 + 256 + N + 256;
-        if (b->d_msg_bytes < need) {
-            if (b->d_msg) (void) hipFree(b->d_msg);
-            b->d_msg = nullptr;
-            b->d_msg_bytes = 0;
-            HIP_TRY(hipMalloc((void **) &b->d_msg, need + need / 4));
-            b->d_msg_bytes = need + need / 4;
-        }
+        if (int rc = grow(b->d_msg, b->d_msg_bytes, need, need / 4)) return rc;
         char *lines = b->d_msg, *packed = lines + (size_t) have * line;
         uint32_t *len = reinterpret_cast<uint32_t *>(packed + (size_t) have * line), *off = len + have;
         uint32_t *info2 = off + have;
@@ -1852,7 +1852,7 @@ int gnuais_batch_vessel_table_update(gnuais_batch *b)
     if (!b || !b->vt) return fail(GNUAIS_E_STATE, "vessel_table_update: no table (gnuais_batch_vessel_table_enable)");
     if (b->streaming) return fail(GNUAIS_E_STATE, "vessel_table_update: a streaming batch updates its table by itself");
     if (int rc = gnuais_batch_sync(b)) return rc;             // a drain-type call: waits for the chain like the drains do
-    hipStream_t s = b->pipeline ? k3_stream(b) : b->last_stream;
+    hipStream_t s = b->pipeline ? k3_stream(b) : b->last[CHAIN].s;
     HIP_TRY(vessel_table_update_enqueue(b->frames, b->frame_count, b->frame_cap, b->vt, b->vt_slots, b->vt_fslot, s));
     return GNUAIS_OK;
 }
@@ -1863,7 +1863,7 @@ int gnuais_batch_vessel_table(gnuais_batch *b, gnuais_vessel *vessels, int cap, 
     *n_vessels = 0;
     if (!b->vt) return fail(GNUAIS_E_STATE, "vessel_table: no table (gnuais_batch_vessel_table_enable)");
     if (int rc = set_device(b)) return rc;
-    hipStream_t s = b->streaming ? b->s_post : (b->pipeline ? k3_stream(b) : b->last_stream);
+    hipStream_t s = b->streaming ? b->s_post : (b->pipeline ? k3_stream(b) : b->last[CHAIN].s);
     uint32_t info[4] = {0, 0, 0, 0};
     int n = 0;
     HIP_TRY(vessel_table_fetch(b->vt, b->vt_slots, vessels, cap, &n, info, s));
@@ -1962,13 +1962,7 @@ int gnuais_batch_stream_nmea(gnuais_batch *b, const char **text, size_t *len, in
         if (const char *v = getenv("GNUAIS_COPY_WGS")) b->copy_wgs = std::max(1, atoi(v));
         if (const char *v = getenv("GNUAIS_COPY_ON_K3")) b->copy_on_k3 = atoi(v) != 0;
         const size_t need_scratch = nmea_scratch_bytes(b->frame_cap, b->n_chunks);
-        if (b->nmea_scratch_bytes < need_scratch) {
-            if (b->nmea_scratch) HIP_TRY(hipFree(b->nmea_scratch));
-            b->nmea_scratch = nullptr;
-            b->nmea_scratch_bytes = 0;
-            HIP_TRY(hipMalloc(&b->nmea_scratch, need_scratch));
-            b->nmea_scratch_bytes = need_scratch;
-        }
+        if (int rc = grow(b->nmea_scratch, b->nmea_scratch_bytes, need_scratch)) return rc;
         if (!b->s_copy) {
             // The formatter's kernels go onto K3's stream: they are small, K3's stream is idle most of a call,
             // and every further stream is one more tenant for the few hardware queues (a formatter stream
@@ -1990,7 +1984,7 @@ int gnuais_batch_stream_nmea(gnuais_batch *b, const char **text, size_t *len, in
         HIP_TRY(hipDeviceSynchronize());
         b->streaming = true;
     }
-    hipStream_t sD = b->pipeline ? k3_stream(b) : b->last_stream;
+    hipStream_t sD = b->pipeline ? k3_stream(b) : b->last[CHAIN].s;
     const int c = b->ring_cur;
     // (1) ring c: everything K3 has been asked to append so far
     HIP_TRY(hipEventRecord(b->e_fill[c], sD));

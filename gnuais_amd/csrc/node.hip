@@ -100,13 +100,9 @@ struct Worker {
 struct Shard {
     int device = 0, first = 0, n = 0;
     gnuais_batch *b = nullptr;
-    int16_t *d_in[2] = {nullptr, nullptr};      // run_host: the shard's [len][n] slab, double-buffered
-    bool in_iq = false;                         // run_iq_host has widened the slabs to [max_len][n][2]
-    int16_t *d_wide = nullptr;                  // run_wideband_host: the shard's wide streams [D*max_len][n/K][2]
-    size_t wide_bytes = 0;
+    void *d_in = nullptr;                       // the host entries' slab (run_staged), in_bytes long
+    size_t in_bytes = 0;
     hipStream_t s_in = nullptr;
-    hipEvent_t e_free[2] = {nullptr, nullptr};  // the FIR that read d_in[q] is done (recorded behind the run on s_in)
-    unsigned long long host_calls = 0;
     // where the shard's host thread runs: the NUMA node of its device (sysfs, via the device's PCI address) and how many
     // CPUs of that node the thread was pinned to (0: not pinned -- no sysfs entry, one node only, or GNUAIS_NODE_PIN=0)
     int numa_node = -1, pinned_cpus = 0;
@@ -117,6 +113,19 @@ struct Shard {
     double m_submit_ms = 0.0, m_first = 0.0, m_last_sync = 0.0;
     Worker w;
 };
+
+// Books one submission into the shard's statistics: a call, and the host time until the booking goes out of scope
+struct Booking {
+    Shard &s;
+    double t0 = wall_ms();
+    explicit Booking(Shard &sh) : s(sh) { if (s.m_calls++ == 0) s.m_first = t0; }
+    ~Booking() { s.m_submit_ms += wall_ms() - t0; }
+};
+
+// The input forms (include/gnuais_hip.h) as one shard sees them: a row of the caller's host array holds `cols` columns
+// of `bytes` bytes each, of which the shard owns [c0, c0 + nc); a chain row takes `rows` input rows
+struct Form { int bytes, cols, c0, nc, rows; };
+enum FormId { AUDIO, IQ, WIDE };
 
 // "0-15,32-47" -> CPUs set in `set`; returns how many
 int parse_cpulist(const char *text, cpu_set_t *set)
@@ -179,9 +188,19 @@ extern "C" {
 
 const char *gnuais_node_last_error(void) { return g_node_err.c_str(); }
 
-static int run_all(gnuais_node *nd, const std::function<int(Shard &)> &f)
+static Form form(const gnuais_node *nd, const Shard &s, FormId f)
 {
-    for (Shard *s : nd->shards) s->w.submit([s, &f] { return f(*s); });
+    const int K = f == WIDE ? nd->ch_K : 1;
+    return {f == AUDIO ? 2 : 4, nd->N / K, s.first / K, s.n / K, f == WIDE ? nd->ch_D : 1};
+}
+
+// f(shard, its index) on every shard's own thread at once; the first failure is reported with the shard it came from
+static int run_all(gnuais_node *nd, const std::function<int(Shard &, size_t)> &f)
+{
+    for (size_t i = 0; i < nd->shards.size(); ++i) {
+        Shard *s = nd->shards[i];
+        s->w.submit([s, i, &f] { return f(*s, i); });
+    }
     int rc = GNUAIS_OK;
     for (Shard *s : nd->shards) {
         const int r = s->w.wait();
@@ -202,11 +221,7 @@ void gnuais_node_destroy(gnuais_node *nd)
             s->w.submit([s] {
                 (void) hipSetDevice(s->device);
                 if (s->b) gnuais_batch_destroy(s->b);
-                for (int q = 0; q < 2; ++q) {
-                    if (s->d_in[q]) (void) hipFree(s->d_in[q]);
-                    if (s->e_free[q]) (void) hipEventDestroy(s->e_free[q]);
-                }
-                if (s->d_wide) (void) hipFree(s->d_wide);
+                if (s->d_in) (void) hipFree(s->d_in);
                 if (s->s_in) (void) hipStreamDestroy(s->s_in);
                 return GNUAIS_OK;
             });
@@ -250,7 +265,7 @@ int gnuais_node_create(gnuais_node **out, const int *devices, int n_devices, int
         s->w.th = std::thread([s] { pin_to_device_node(*s); s->w.loop(); });
         nd->shards.push_back(s);
     }
-    const int rc = run_all(nd, [&](Shard &s) {
+    const int rc = run_all(nd, [&](Shard &s, size_t) {
         return gnuais_batch_create(&s.b, s.device, s.n, taps, n_taps, pllinc, max_len, frame_capacity_per_device);
     });
     if (rc != GNUAIS_OK) {
@@ -293,120 +308,75 @@ int gnuais_node_shard(const gnuais_node *nd, int i, int *device, int *first_chan
 int gnuais_node_reset(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_reset: NULL");
-    return run_all(nd, [](Shard &s) { return gnuais_batch_reset(s.b); });
+    return run_all(nd, [](Shard &s, size_t) { return gnuais_batch_reset(s.b); });
+}
+
+// gnuais_node_run / _run_iq: shard i runs `run`, the batch entry of the form, on its device slab slabs[i] and streams[i]
+static int run_slabs(gnuais_node *nd, const int16_t *const *slabs, int len, void *const *streams, const char *who,
+                     int (*run)(gnuais_batch *, const int16_t *, int, void *))
+{
+    if (!nd || !slabs) return node_fail(GNUAIS_E_ARG, std::string(who) + ": NULL argument");
+    if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, std::string(who) + ": len out of range");
+    return run_all(nd, [&](Shard &s, size_t i) {
+        Booking book(s);
+        return run(s.b, slabs[i], len, streams ? streams[i] : nullptr);
+    });
+}
+
+// The host entries: on the shard's input stream s_in, the shard's columns of the caller's host array go into the
+// shard's slab by one strided 2-D copy, then `run`, the batch entry of the form, reads them there.  Everything that
+// reads the slab runs on s_in (K1, the discriminator, the channeliser), and every call syncs s_in before it returns,
+// so the slab is free again between calls: one slab serves every form, sized for max_len chain rows of the widest one.
+static int run_staged(gnuais_node *nd, FormId id, const int16_t *h, int len, const char *who,
+                      int (*run)(gnuais_batch *, const int16_t *, int, void *))
+{
+    return run_all(nd, [=](Shard &s, size_t) -> int {
+        Booking book(s);
+        auto hip_fail = [&](const char *what) { return node_fail(GNUAIS_E_HIP, std::string(who) + ": " + what); };
+        const Form f = form(nd, s, id);
+        if (hipSetDevice(s.device) != hipSuccess) return hip_fail("hipSetDevice");
+        if (!s.s_in && hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess) return hip_fail("stream");
+        const size_t row = (size_t) f.bytes * (size_t) f.nc, need = row * (size_t) f.rows * (size_t) nd->max_len;
+        if (s.in_bytes < need) {
+            if (s.d_in) (void) hipFree(s.d_in);
+            s.d_in = nullptr;
+            s.in_bytes = 0;
+            if (hipMalloc(&s.d_in, need) != hipSuccess) return hip_fail("staging allocation");
+            s.in_bytes = need;
+        }
+        const char *src = (const char *) h + (size_t) f.bytes * (size_t) f.c0;
+        if (hipMemcpy2DAsync(s.d_in, row, src, (size_t) f.bytes * (size_t) f.cols, row, (size_t) len, hipMemcpyHostToDevice,
+                             s.s_in) != hipSuccess)
+            return hip_fail("host -> device copy");
+        const int rc = run(s.b, (const int16_t *) s.d_in, len, s.s_in);
+        // the caller's buffer is borrowed for the call only (src/ais.c:216 reuses it): the copy out of it must be done
+        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK) return hip_fail("copy");
+        return rc;
+    });
 }
 
 int gnuais_node_run(gnuais_node *nd, const int16_t *const *d_samples, int len, void *const *streams)
 {
-    if (!nd || !d_samples) return node_fail(GNUAIS_E_ARG, "node_run: NULL argument");
-    if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run: len out of range");
-    std::vector<Shard *> &sh = nd->shards;
-    return run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
-        const double t0 = wall_ms();
-        const int rc = gnuais_batch_run(s.b, d_samples[i], len, streams ? streams[i] : nullptr);
-        if (s.m_calls++ == 0) s.m_first = t0;
-        s.m_submit_ms += wall_ms() - t0;
-        return rc;
-    });
+    return run_slabs(nd, d_samples, len, streams, "node_run", gnuais_batch_run);
+}
+
+int gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams)
+{
+    return run_slabs(nd, d_iq, len, streams, "node_run_iq", gnuais_batch_run_iq);
 }
 
 int gnuais_node_run_host(gnuais_node *nd, const int16_t *h_samples, int len)
 {
     if (!nd || !h_samples) return node_fail(GNUAIS_E_ARG, "node_run_host: NULL argument");
     if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run_host: len out of range");
-    const int N = nd->N, max_len = nd->max_len;
-    return run_all(nd, [=](Shard &s) -> int {
-        const double t0 = wall_ms();
-        if (s.m_calls++ == 0) s.m_first = t0;
-        struct Stop { Shard &s; double t0; ~Stop() { s.m_submit_ms += wall_ms() - t0; } } stop{s, t0};
-        if (hipSetDevice(s.device) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_host: hipSetDevice");
-        if (!s.s_in) {
-            if (hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess)
-                return node_fail(GNUAIS_E_HIP, "node_run_host: stream");
-            for (int q = 0; q < 2; ++q) {
-                if (hipMalloc((void **) &s.d_in[q], sizeof(int16_t) * (size_t) max_len * (size_t) s.n) != hipSuccess ||
-                    hipEventCreateWithFlags(&s.e_free[q], hipEventDisableTiming) != hipSuccess)
-                    return node_fail(GNUAIS_E_HIP, "node_run_host: staging allocation");
-            }
-        }
-        const int q = (int) (s.host_calls & 1);
-        if (s.host_calls >= 2 && hipEventSynchronize(s.e_free[q]) != hipSuccess)
-            return node_fail(GNUAIS_E_HIP, "node_run_host: wait for the staging slab");
-        // the shard's columns of the interleaved buffer: a strided 2-D copy, rows of n channels out of N
-        if (hipMemcpy2DAsync(s.d_in[q], sizeof(int16_t) * (size_t) s.n, h_samples + s.first,
-                             sizeof(int16_t) * (size_t) N, sizeof(int16_t) * (size_t) s.n, (size_t) len,
-                             hipMemcpyHostToDevice, s.s_in) != hipSuccess)
-            return node_fail(GNUAIS_E_HIP, "node_run_host: host -> device copy");
-        const int rc = gnuais_batch_run(s.b, s.d_in[q], len, s.s_in);
-        (void) hipEventRecord(s.e_free[q], s.s_in);
-        s.host_calls++;
-        // the caller's buffer is borrowed for the call only (src/ais.c:216 reuses it): the copy out of it must be done
-        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
-            return node_fail(GNUAIS_E_HIP, "node_run_host: copy");
-        return rc;
-    });
+    return run_staged(nd, AUDIO, h_samples, len, "node_run_host", gnuais_batch_run);
 }
 
-int gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams)
-{
-    if (!nd || !d_iq) return node_fail(GNUAIS_E_ARG, "node_run_iq: NULL argument");
-    if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run_iq: len out of range");
-    std::vector<Shard *> &sh = nd->shards;
-    return run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
-        const double t0 = wall_ms();
-        const int rc = gnuais_batch_run_iq(s.b, d_iq[i], len, streams ? streams[i] : nullptr);
-        if (s.m_calls++ == 0) s.m_first = t0;
-        s.m_submit_ms += wall_ms() - t0;
-        return rc;
-    });
-}
-
-// gnuais_node_run_host with (I, Q) pairs: the staging slabs are twice as wide (allocated so on first use, or widened once,
-// after the shard's input stream -- the only user of a slab -- has drained)
 int gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len)
 {
     if (!nd || !h_iq) return node_fail(GNUAIS_E_ARG, "node_run_iq_host: NULL argument");
     if (len <= 0 || len > nd->max_len) return node_fail(GNUAIS_E_ARG, "node_run_iq_host: len out of range");
-    const int N = nd->N, max_len = nd->max_len;
-    return run_all(nd, [=](Shard &s) -> int {
-        const double t0 = wall_ms();
-        if (s.m_calls++ == 0) s.m_first = t0;
-        struct Stop { Shard &s; double t0; ~Stop() { s.m_submit_ms += wall_ms() - t0; } } stop{s, t0};
-        if (hipSetDevice(s.device) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_iq_host: hipSetDevice");
-        if (!s.s_in) {
-            if (hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess)
-                return node_fail(GNUAIS_E_HIP, "node_run_iq_host: stream");
-            for (int q = 0; q < 2; ++q)
-                if (hipEventCreateWithFlags(&s.e_free[q], hipEventDisableTiming) != hipSuccess)
-                    return node_fail(GNUAIS_E_HIP, "node_run_iq_host: staging events");
-        }
-        if (!s.in_iq) {
-            if (hipStreamSynchronize(s.s_in) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_iq_host: drain");
-            for (int q = 0; q < 2; ++q) {
-                if (s.d_in[q]) (void) hipFree(s.d_in[q]);
-                s.d_in[q] = nullptr;
-            }
-            for (int q = 0; q < 2; ++q)
-                if (hipMalloc((void **) &s.d_in[q], sizeof(int16_t) * 2 * (size_t) max_len * (size_t) s.n) != hipSuccess)
-                    return node_fail(GNUAIS_E_HIP, "node_run_iq_host: staging allocation");
-            s.in_iq = true;
-        }
-        const int q = (int) (s.host_calls & 1);
-        if (s.host_calls >= 2 && hipEventSynchronize(s.e_free[q]) != hipSuccess)
-            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: wait for the staging slab");
-        if (hipMemcpy2DAsync(s.d_in[q], sizeof(int16_t) * 2 * (size_t) s.n, h_iq + 2 * (size_t) s.first,
-                             sizeof(int16_t) * 2 * (size_t) N, sizeof(int16_t) * 2 * (size_t) s.n, (size_t) len,
-                             hipMemcpyHostToDevice, s.s_in) != hipSuccess)
-            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: host -> device copy");
-        const int rc = gnuais_batch_run_iq(s.b, s.d_in[q], len, s.s_in);
-        (void) hipEventRecord(s.e_free[q], s.s_in);
-        s.host_calls++;
-        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
-            return node_fail(GNUAIS_E_HIP, "node_run_iq_host: copy");
-        return rc;
-    });
+    return run_staged(nd, IQ, h_iq, len, "node_run_iq_host", gnuais_batch_run_iq);
 }
 
 int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
@@ -424,7 +394,7 @@ int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const in
         }
     }
     nd->ch_K = 0;
-    const int rc = run_all(nd, [=](Shard &s) {
+    const int rc = run_all(nd, [=](Shard &s, size_t) {
         return gnuais_batch_channeliser(s.b, decim, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
     });
     if (rc == GNUAIS_OK) {
@@ -434,53 +404,20 @@ int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const in
     return rc;
 }
 
-// every shard copies the columns of its own streams into a device slab of its own on its input stream, then runs the
-// channeliser on that stream; the next call's copy is ordered behind this call's channeliser, the only reader of the slab
 int gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len)
 {
     if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: NULL argument");
     if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: no channeliser configured (gnuais_node_channeliser)");
-    const int K = nd->ch_K, D = nd->ch_D, M = nd->N / K, max_len = nd->max_len;
-    if (len <= 0 || len % D || len / D > max_len)
+    if (len <= 0 || len % nd->ch_D || len / nd->ch_D > nd->max_len)
         return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: len must be a positive multiple of the decimation, at most "
                                        "decim * max_len");
-    return run_all(nd, [=](Shard &s) -> int {
-        const double t0 = wall_ms();
-        if (s.m_calls++ == 0) s.m_first = t0;
-        struct Stop { Shard &s; double t0; ~Stop() { s.m_submit_ms += wall_ms() - t0; } } stop{s, t0};
-        if (hipSetDevice(s.device) != hipSuccess) return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: hipSetDevice");
-        if (!s.s_in) {
-            if (hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess)
-                return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: stream");
-            for (int q = 0; q < 2; ++q)
-                if (hipEventCreateWithFlags(&s.e_free[q], hipEventDisableTiming) != hipSuccess)
-                    return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: staging events");
-        }
-        const size_t ms = (size_t) (s.n / K);
-        const size_t need = sizeof(int16_t) * 2 * (size_t) D * (size_t) max_len * ms;
-        if (s.wide_bytes < need) {                // s_in is drained at the end of every call: the old slab is free
-            if (s.d_wide) (void) hipFree(s.d_wide);
-            s.d_wide = nullptr;
-            s.wide_bytes = 0;
-            if (hipMalloc((void **) &s.d_wide, need) != hipSuccess)
-                return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: staging allocation");
-            s.wide_bytes = need;
-        }
-        if (hipMemcpy2DAsync(s.d_wide, sizeof(int16_t) * 2 * ms, h_wide + 2 * (size_t) (s.first / K),
-                             sizeof(int16_t) * 2 * (size_t) M, sizeof(int16_t) * 2 * ms, (size_t) len, hipMemcpyHostToDevice,
-                             s.s_in) != hipSuccess)
-            return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: host -> device copy");
-        const int rc = gnuais_batch_run_wideband(s.b, s.d_wide, len, s.s_in);
-        if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK)
-            return node_fail(GNUAIS_E_HIP, "node_run_wideband_host: copy");
-        return rc;
-    });
+    return run_staged(nd, WIDE, h_wide, len, "node_run_wideband_host", gnuais_batch_run_wideband);
 }
 
 int gnuais_node_sync(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_sync: NULL");
-    return run_all(nd, [](Shard &s) {
+    return run_all(nd, [](Shard &s, size_t) {
         const int rc = gnuais_batch_sync(s.b);
         s.m_last_sync = wall_ms();
         return rc;
@@ -492,7 +429,7 @@ int gnuais_node_sync(gnuais_node *nd)
 int gnuais_node_mark(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_mark: NULL");
-    return run_all(nd, [](Shard &s) {
+    return run_all(nd, [](Shard &s, size_t) {
         s.m_calls = 0;
         s.m_submit_ms = s.m_first = s.m_last_sync = 0.0;
         return GNUAIS_OK;
@@ -520,11 +457,7 @@ int gnuais_node_pending_frames(gnuais_node *nd, int *n_out)
 {
     if (!nd || !n_out) return node_fail(GNUAIS_E_ARG, "node_pending_frames: argument");
     std::vector<int> n(nd->shards.size(), 0);
-    std::vector<Shard *> &sh = nd->shards;
-    const int rc = run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
-        return gnuais_batch_pending_frames(s.b, &n[i]);
-    });
+    const int rc = run_all(nd, [&](Shard &s, size_t i) { return gnuais_batch_pending_frames(s.b, &n[i]); });
     long long t = 0;
     for (int v : n) t += v;
     *n_out = (int) std::min<long long>(t, 0x7fffffff);
@@ -545,18 +478,14 @@ int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int 
     std::vector<int> cnt(sh.size(), 0), off(sh.size(), 0);
     {
         std::vector<int> pend(sh.size(), 0);
-        const int rc = run_all(nd, [&](Shard &s) {
-            const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
-            return gnuais_batch_pending_frames(s.b, &pend[i]);
-        });
+        const int rc = run_all(nd, [&](Shard &s, size_t i) { return gnuais_batch_pending_frames(s.b, &pend[i]); });
         if (rc) return rc;
         int o = 0;
         for (size_t i = 0; i < sh.size(); ++i) { off[i] = o; o += pend[i]; }
         if (o > max) return node_fail(GNUAIS_E_ARG, "node_drain_frames: frame buffer too small");
         cnt = pend;
     }
-    const int rc = run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
+    const int rc = run_all(nd, [&](Shard &s, size_t i) {
         int got = 0;
         const int r = gnuais_batch_drain_frames(s.b, h_out + off[i], cnt[i], &got);
         for (int k = 0; k < got; ++k) h_out[off[i] + k].channel += (uint32_t) s.first;
@@ -582,8 +511,7 @@ int gnuais_node_stream_nmea(gnuais_node *nd, const char **texts, size_t *lens, i
     std::vector<Shard *> &sh = nd->shards;
     std::vector<int> ns(sh.size(), 0), nf(sh.size(), -1);
     for (size_t i = 0; i < sh.size(); ++i) { texts[i] = nullptr; lens[i] = 0; }    // a shard that fails leaves nothing stale
-    const int rc = run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
+    const int rc = run_all(nd, [&](Shard &s, size_t i) {
         return gnuais_batch_stream_nmea(s.b, &texts[i], &lens[i], &ns[i], &nf[i]);
     });
     int sent = 0, frames = 0;
@@ -600,24 +528,20 @@ int gnuais_node_stream_nmea(gnuais_node *nd, const char **texts, size_t *lens, i
 int gnuais_node_discard_frames(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_discard_frames: NULL");
-    return run_all(nd, [](Shard &s) { return gnuais_batch_discard_frames(s.b, nullptr); });
+    return run_all(nd, [](Shard &s, size_t) { return gnuais_batch_discard_frames(s.b, nullptr); });
 }
 
 int gnuais_node_counters(gnuais_node *nd, gnuais_counters *h_out)
 {
     if (!nd || !h_out) return node_fail(GNUAIS_E_ARG, "node_counters: argument");
-    return run_all(nd, [&](Shard &s) { return gnuais_batch_counters(s.b, h_out + s.first); });
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_counters(s.b, h_out + s.first); });
 }
 
 int gnuais_node_total_received(gnuais_node *nd, long long *total)
 {
     if (!nd || !total) return node_fail(GNUAIS_E_ARG, "node_total_received: argument");
-    std::vector<Shard *> &sh = nd->shards;
-    std::vector<long long> t(sh.size(), 0);
-    const int rc = run_all(nd, [&](Shard &s) {
-        const size_t i = (size_t) (std::find(sh.begin(), sh.end(), &s) - sh.begin());
-        return gnuais_batch_total_received(s.b, &t[i]);
-    });
+    std::vector<long long> t(nd->shards.size(), 0);
+    const int rc = run_all(nd, [&](Shard &s, size_t i) { return gnuais_batch_total_received(s.b, &t[i]); });
     *total = 0;
     for (long long v : t) *total += v;
     return rc;
@@ -626,19 +550,19 @@ int gnuais_node_total_received(gnuais_node *nd, long long *total)
 int gnuais_node_maxval(gnuais_node *nd, int16_t *h_out)
 {
     if (!nd || !h_out) return node_fail(GNUAIS_E_ARG, "node_maxval: argument");
-    return run_all(nd, [&](Shard &s) { return gnuais_batch_maxval(s.b, h_out + s.first); });
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_maxval(s.b, h_out + s.first); });
 }
 
 int gnuais_node_pll_state(gnuais_node *nd, gnuais_pll_state *h_out)
 {
     if (!nd || !h_out) return node_fail(GNUAIS_E_ARG, "node_pll_state: argument");
-    return run_all(nd, [&](Shard &s) { return gnuais_batch_pll_state(s.b, h_out + s.first); });
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_pll_state(s.b, h_out + s.first); });
 }
 
 int gnuais_node_set_option(gnuais_node *nd, const char *name, int value)
 {
     if (!nd || !name) return node_fail(GNUAIS_E_ARG, "node_set_option: argument");
-    return run_all(nd, [&](Shard &s) { return gnuais_batch_set_option(s.b, name, value); });
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_set_option(s.b, name, value); });
 }
 
 int gnuais_node_autotune(gnuais_node *nd, const int16_t *const *d_samples, int len, void *const *streams,

@@ -64,53 +64,49 @@ class ReceiverBatch:
         """samples: interleaved int16 [len][n_channels]; a CUDA/HIP torch tensor
         (used in place, asynchronous on `stream` or torch's current stream) or a
         numpy array (copied host->device, synchronous)."""
-        if _is_torch(samples):
-            import torch
-            assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
-            assert samples.dim() == 2 and samples.shape[1] == self.n_channels
-            if stream is None:
-                stream = torch.cuda.current_stream(samples.device).cuda_stream
-            check(self._lib.gnuais_batch_run(self._h, samples.data_ptr(), int(samples.shape[0]),
-                                             C.c_void_p(stream)))
-            if sync:
-                self.sync()
-        else:
-            x = np.ascontiguousarray(samples, dtype=np.int16)
-            assert x.ndim == 2 and x.shape[1] == self.n_channels
-            check(self._lib.gnuais_batch_run_host(self._h, x.ctypes.data, int(x.shape[0])))
+        self._run(samples, stream, sync, lambda x: x.ndim == 2 and x.shape[1] == self.n_channels,
+                  self._lib.gnuais_batch_run, self._lib.gnuais_batch_run_host)
 
     def run_iq(self, samples, stream: Optional[int] = None, sync: bool = True):
         """Complex baseband in (gnuais_batch_run_iq): samples int16 [len][n_channels][2] = (I, Q) pairs; the
         discriminator defined in include/gnuais_hip.h turns them into the audio run() takes, on the device.  A CUDA/HIP
         torch tensor is used in place, asynchronously on `stream` or torch's current stream; a numpy array goes through
         gnuais_batch_run_iq_host (copy, run, sync)."""
+        self._run(samples, stream, sync, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
+                  self._lib.gnuais_batch_run_iq, self._lib.gnuais_batch_run_iq_host)
+
+    def _run(self, samples, stream, sync, shape_ok, run, run_host):
+        """run / run_iq / run_wideband: `run` on a CUDA/HIP torch tensor in place, else `run_host` on a host copy"""
         if _is_torch(samples):
             import torch
             assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
-            assert samples.dim() == 3 and samples.shape[1] == self.n_channels and samples.shape[2] == 2
+            assert shape_ok(samples)
             if stream is None:
                 stream = torch.cuda.current_stream(samples.device).cuda_stream
-            check(self._lib.gnuais_batch_run_iq(self._h, samples.data_ptr(), int(samples.shape[0]),
-                                                C.c_void_p(stream)))
+            check(run(self._h, samples.data_ptr(), int(samples.shape[0]), C.c_void_p(stream)))
             if sync:
                 self.sync()
         else:
             x = np.ascontiguousarray(samples, dtype=np.int16)
-            assert x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2
-            check(self._lib.gnuais_batch_run_iq_host(self._h, x.ctypes.data, int(x.shape[0])))
+            assert shape_ok(x)
+            check(run_host(self._h, x.ctypes.data, int(x.shape[0])))
 
     def discriminate(self, samples):
         """The discriminator alone (gnuais_batch_discriminate): int16 [len][n_channels][2] -> torch int16
         [len][n_channels] on the device; advances the I/Q carry and nothing else."""
+        return self._stage(samples, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
+                           lambda n: (n, self.n_channels), self._lib.gnuais_batch_discriminate)
+
+    def _stage(self, samples, shape_ok, out_shape, fn):
+        """discriminate / channelise: `fn` alone on the device, into a new tensor of out_shape(len); synchronous"""
         import torch
         if not _is_torch(samples):
             samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16)).to(f"cuda:{self.device}")
         assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
-        assert samples.dim() == 3 and samples.shape[1] == self.n_channels and samples.shape[2] == 2
-        out = torch.empty(tuple(samples.shape[:2]), dtype=torch.int16, device=samples.device)
+        assert shape_ok(samples)
+        out = torch.empty(out_shape(int(samples.shape[0])), dtype=torch.int16, device=samples.device)
         stream = torch.cuda.current_stream(samples.device)
-        check(self._lib.gnuais_batch_discriminate(self._h, samples.data_ptr(), int(samples.shape[0]),
-                                                  out.data_ptr(), C.c_void_p(stream.cuda_stream)))
+        check(fn(self._h, samples.data_ptr(), int(samples.shape[0]), out.data_ptr(), C.c_void_p(stream.cuda_stream)))
         stream.synchronize()
         return out
 
@@ -137,36 +133,15 @@ class ReceiverBatch:
         len a multiple of the decimation; channeliser, discriminator and chain on the device.  A CUDA/HIP torch tensor is
         used in place, asynchronously on `stream` or torch's current stream; a numpy array goes through
         gnuais_batch_run_wideband_host (copy, run, sync)."""
-        if _is_torch(samples):
-            import torch
-            assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
-            assert self._wide_shape_ok(samples, int(samples.shape[0]))
-            if stream is None:
-                stream = torch.cuda.current_stream(samples.device).cuda_stream
-            check(self._lib.gnuais_batch_run_wideband(self._h, samples.data_ptr(), int(samples.shape[0]),
-                                                      C.c_void_p(stream)))
-            if sync:
-                self.sync()
-        else:
-            x = np.ascontiguousarray(samples, dtype=np.int16)
-            assert self._wide_shape_ok(x, int(x.shape[0]))
-            check(self._lib.gnuais_batch_run_wideband_host(self._h, x.ctypes.data, int(x.shape[0])))
+        self._run(samples, stream, sync, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
+                  self._lib.gnuais_batch_run_wideband, self._lib.gnuais_batch_run_wideband_host)
 
     def channelise(self, samples):
         """The channeliser alone (gnuais_batch_channelise): int16 [len][n_channels / K][2] -> torch int16
         [len / D][n_channels][2] on the device; advances the channeliser's state and nothing else."""
-        import torch
-        if not _is_torch(samples):
-            samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16)).to(f"cuda:{self.device}")
-        assert samples.is_cuda and samples.dtype == torch.int16 and samples.is_contiguous()
-        assert self._wide_shape_ok(samples, int(samples.shape[0]))
         d = getattr(self, "_chan", (1, 1))[0]
-        out = torch.empty((int(samples.shape[0]) // d, self.n_channels, 2), dtype=torch.int16, device=samples.device)
-        stream = torch.cuda.current_stream(samples.device)
-        check(self._lib.gnuais_batch_channelise(self._h, samples.data_ptr(), int(samples.shape[0]), out.data_ptr(),
-                                                C.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-        return out
+        return self._stage(samples, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
+                           lambda n: (n // d, self.n_channels, 2), self._lib.gnuais_batch_channelise)
 
     def run_host_async(self, samples: np.ndarray):
         """Host input without waiting for the device: pinned double-buffered staging inside the

@@ -66,15 +66,12 @@ class ReceiverNode:
     __del__ = close
 
     def run_host(self, samples):
-        x = self._np.ascontiguousarray(samples, dtype=self._np.int16)
-        assert x.ndim == 2 and x.shape[1] == self.n_channels
-        self._raise(self._lib.gnuais_node_run_host(self._h, x.ctypes.data, int(x.shape[0])))
+        self._run_host(samples, lambda x: x.ndim == 2 and x.shape[1] == self.n_channels, self._lib.gnuais_node_run_host)
 
     def run_iq_host(self, samples):
         """Complex baseband in (gnuais_node_run_iq_host): one host array int16 [len][n_channels][2] of (I, Q) pairs."""
-        x = self._np.ascontiguousarray(samples, dtype=self._np.int16)
-        assert x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2
-        self._raise(self._lib.gnuais_node_run_iq_host(self._h, x.ctypes.data, int(x.shape[0])))
+        self._run_host(samples, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
+                       self._lib.gnuais_node_run_iq_host)
 
     def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
         """Wideband in (gnuais_node_channeliser): ReceiverBatch.channeliser on every shard; every shard's first channel
@@ -88,31 +85,34 @@ class ReceiverNode:
 
     def run_wideband_host(self, samples):
         """Wideband in (gnuais_node_run_wideband_host): one host array int16 [len][n_channels / K][2] of wide streams."""
+        k = getattr(self, "_chan_k", 1)
+        self._run_host(samples, lambda x: x.ndim == 3 and x.shape[1] * k == self.n_channels and x.shape[2] == 2,
+                       self._lib.gnuais_node_run_wideband_host)
+
+    def _run_host(self, samples, shape_ok, fn):
+        """run_host / run_iq_host / run_wideband_host: `fn` on one host array"""
         x = self._np.ascontiguousarray(samples, dtype=self._np.int16)
-        assert x.ndim == 3 and x.shape[1] * getattr(self, "_chan_k", 1) == self.n_channels and x.shape[2] == 2
-        self._raise(self._lib.gnuais_node_run_wideband_host(self._h, x.ctypes.data, int(x.shape[0])))
+        assert shape_ok(x)
+        self._raise(fn(self._h, x.ctypes.data, int(x.shape[0])))
 
     def run_iq(self, slabs, streams=None):
         """slabs: one CUDA/HIP int16 tensor [len][n_i][2] of (I, Q) pairs per shard, each on its shard's device."""
-        C = self._C
-        assert len(slabs) == len(self.shards)
-        ln = int(slabs[0].shape[0])
-        for t, (d, f, n) in zip(slabs, self.shards):
-            assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == (ln, n, 2) and t.device.index == d
-        ptrs = (C.c_void_p * len(slabs))(*[t.data_ptr() for t in slabs])
-        st = None if streams is None else (C.c_void_p * len(slabs))(*streams)
-        self._raise(self._lib.gnuais_node_run_iq(self._h, ptrs, ln, st))
+        self._run_slabs(slabs, streams, (2,), self._lib.gnuais_node_run_iq)
 
     def run(self, slabs, streams=None):
         """slabs: one CUDA/HIP int16 tensor [len][n_i] per shard, each on its shard's device."""
+        self._run_slabs(slabs, streams, (), self._lib.gnuais_node_run)
+
+    def _run_slabs(self, slabs, streams, tail, fn):
+        """run / run_iq: `fn` on one device slab [len][n_i] + tail per shard"""
         C = self._C
         assert len(slabs) == len(self.shards)
         ln = int(slabs[0].shape[0])
         for t, (d, f, n) in zip(slabs, self.shards):
-            assert t.is_cuda and t.is_contiguous() and t.shape == (ln, n) and t.device.index == d
+            assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == (ln, n) + tail and t.device.index == d
         ptrs = (C.c_void_p * len(slabs))(*[t.data_ptr() for t in slabs])
         st = None if streams is None else (C.c_void_p * len(slabs))(*streams)
-        self._raise(self._lib.gnuais_node_run(self._h, ptrs, ln, st))
+        self._raise(fn(self._h, ptrs, ln, st))
 
     def autotune(self, slabs, streams=None) -> float:
         C = self._C

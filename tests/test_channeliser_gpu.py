@@ -200,13 +200,19 @@ def test_node_two_shards_equal_one_batch_and_misaligned_shards_are_refused():
     M, D = 50, 6
     n = 8 * 1280 * D
     x, _ = wide_streams(M, n)
+    iq = chan_ref.Channeliser(M, D, 48000 * D, [-25000, 25000]).run(x)
+    audio = iq_ref.discriminate(iq)[0]
     nd = ReceiverNode(2 * M, devices=[0, 0], max_len=2000)
     b = ReceiverBatch(2 * M, max_len=2000)
     nd.channeliser(D, 48000 * D, [-25000, 25000])
     b.channeliser(D, 48000 * D, [-25000, 25000])
-    for lo in range(0, n, D * 2000):
-        nd.run_wideband_host(x[lo:lo + D * 2000])
-        b.run_wideband(x[lo:lo + D * 2000])
+    # audio, I/Q and wideband calls in turn, narrowest first, so that the node's staging slab grows across the forms
+    forms = ((nd.run_host, b.run, audio, 1), (nd.run_iq_host, b.run_iq, iq, 1),
+             (nd.run_wideband_host, b.run_wideband, x, D))
+    for i, lo in enumerate(range(0, n // D, 2000)):
+        run_node, run_batch, src, rows = forms[i % 3]
+        run_node(src[lo * rows:(lo + 2000) * rows])
+        run_batch(src[lo * rows:(lo + 2000) * rows])
     nd.sync()
     assert nd.drain_frames().tobytes() == b.drain_frames().tobytes()
     assert nd.counters().tobytes() == b.counters().tobytes()

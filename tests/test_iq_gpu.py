@@ -181,19 +181,27 @@ def test_c3_shape_discriminate_and_run_iq():
 
 
 def test_node_run_iq_host_equals_one_batch():
+    """gnuais_node_run_iq_host from one host array and, in a second pass, gnuais_node_run_iq from device slabs, against
+    one batch"""
     from gnuais_amd import ReceiverBatch, ReceiverNode
     n_ch, total = 203, 10 * 1280
     x, _ = iq_streams(n_ch, total)
     nd = ReceiverNode(n_ch, devices=[0, 0, 0, 0], max_len=5000)
     b = ReceiverBatch(n_ch, max_len=5000)
-    for lo in range(0, total, 5000):
-        nd.run_iq_host(x[lo:lo + 5000])
-        b.run_iq(x[lo:lo + 5000])
-    nd.sync()
-    assert nd.drain_frames().tobytes() == b.drain_frames().tobytes()
-    assert nd.counters().tobytes() == b.counters().tobytes()
-    assert nd.pll_state().tobytes() == b.pll_state().tobytes()
-    assert b.counters()["receivedframes"].sum() > 200
+    for mode in ("host", "device"):
+        for lo in range(0, total, 5000):
+            if mode == "host":
+                nd.run_iq_host(x[lo:lo + 5000])
+            else:
+                nd.run_iq([dev(x[lo:lo + 5000, f:f + n], d) for d, f, n in nd.shards])
+            b.run_iq(x[lo:lo + 5000])
+        nd.sync()
+        assert nd.drain_frames().tobytes() == b.drain_frames().tobytes()
+        assert nd.counters().tobytes() == b.counters().tobytes()
+        assert nd.pll_state().tobytes() == b.pll_state().tobytes()
+        assert b.counters()["receivedframes"].sum() > 200
+        nd.reset()
+        b.reset()
     nd.close()
 
 
