@@ -54,8 +54,9 @@ static const double k_tap_half[18] = {
     2.5280e-24, 2.0934e-20, 7.6339e-17, 1.2259e-13, 8.6690e-11, 2.6996e-08,
     3.7020e-06, 2.2355e-04, 5.9448e-03, 6.9616e-02, 3.5899e-01, 8.1522e-01};
 
-// The stages a call may pass through, in launch order: the channeliser, the discriminator, the chain (K1 .. K3)
-enum Stage { CHAN, DISC, CHAIN, N_STAGES };
+// The stages a call may pass through, in launch order: the channeliser, the discriminator, the carrier-error stage
+// (gnuais_batch_afc, when it is on), the chain (K1 .. K3)
+enum Stage { CHAN, DISC, AFC, CHAIN, N_STAGES };
 
 // The input forms (include/gnuais_hip.h): audio [len][N], I/Q [len][N][2], wideband [len][N/K][2]
 enum FormId { AUDIO, IQ, WIDE };
@@ -209,7 +210,8 @@ struct gnuais_batch {
     // stage it passes through, when that stream is not s (drain()).  This covers two hazards.  A stage's carry goes
     // from launch to launch in stream order: the channeliser's history, the discriminator's previous pair, the chain's
     // FIR history and peaks.  And a stage in front of the chain overwrites an intermediate buffer whose reader is the
-    // next stage of the previous call, on that call's stream: ch_iq is read by the discriminator, iq_audio by K1.
+    // next stage of the previous call, on that call's stream: ch_iq is read by the discriminator, iq_audio by K1 or the
+    // AFC stage, afc_audio by K1.  The AFC stage's delay line, block sums and estimates are carries of the first kind.
     struct { hipStream_t s = nullptr; bool used = false; } last[N_STAGES];
     int last_len = 0;
     // K3 on the deframer's stream: at ring lag 1 the two never overlap (deframer(i) -> K3(i) -> deframer(i+1)), so the two
@@ -230,6 +232,14 @@ struct gnuais_batch {
     int ch_cur = 0;
     unsigned long long ch_n = 0;
     int16_t *ch_iq = nullptr;
+    // the carrier-error stage (gnuais_batch_afc, afc.hip; 0 = off): the window W, the rows n it has taken, the ring of
+    // block sums [afc_nb][N][2], the delay line [W/2][N], the estimates of the last call [max_len/64 + 2][N] with the row
+    // that serves the last output row (-1: none yet), and the corrected audio it writes for the chain, [max_len][N]
+    // (allocated on first use)
+    int afc_W = 0, afc_nb = 0, afc_est_row = -1;
+    unsigned long long afc_n = 0;
+    int64_t *afc_blk = nullptr;
+    int16_t *afc_delay = nullptr, *afc_est = nullptr, *afc_audio = nullptr;
 };
 
 // Per chain row, `rows` input rows of `cols` columns of `bytes` bytes each; `stages`: bit s = the call passes stage s
@@ -243,8 +253,8 @@ static Form form(const gnuais_batch *b, FormId f)
 {
     switch (f) {
     case AUDIO: return {2, b->N, 1, 1u << CHAIN};
-    case IQ: return {4, b->N, 1, 1u << DISC | 1u << CHAIN};
-    default: return {4, b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | 1u << DISC | 1u << CHAIN};
+    case IQ: return {4, b->N, 1, 1u << DISC | (b->afc_W ? 1u << AFC : 0u) | 1u << CHAIN};
+    default: return {4, b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages};
     }
 }
 
@@ -276,7 +286,8 @@ static int grow(T *&p, size_t &have, size_t need, size_t slack = 0)
 }
 
 // An intermediate buffer of `bytes`, allocated on first use once the device has room for it: `what` of N x max_len
-static int alloc_checked(gnuais_batch *b, int16_t *&p, size_t bytes, const char *who, const char *what)
+template <class T>
+static int alloc_checked(gnuais_batch *b, T *&p, size_t bytes, const char *who, const char *what)
 {
     if (p) return GNUAIS_OK;
     size_t free_b = 0, total_b = 0;
@@ -354,7 +365,8 @@ void gnuais_batch_destroy(gnuais_batch *b)
     void *ptrs[] = {b->hist[0], b->hist[1], b->hist[2], b->hist[3], b->pll, b->lastbit, b->prev, b->ctl, b->cand,
                     b->frame_count, b->counters, b->maxval[0], b->maxval[1], b->maxval[2], b->maxval[3], b->frames, b->d_taps, b->d_mfma,
                     b->stage_x, b->d_seq[0], b->d_seq[1], b->d_text, b->nmea_scratch, b->d_msg, b->d_word, b->stage_f, b->vt, b->vt_fslot,
-                    b->iq_prev, b->iq_audio, b->ch_mix, b->ch_poly, b->ch_hist[0], b->ch_hist[1], b->ch_taps, b->ch_iq};
+                    b->iq_prev, b->iq_audio, b->ch_mix, b->ch_poly, b->ch_hist[0], b->ch_hist[1], b->ch_taps, b->ch_iq,
+                    b->afc_blk, b->afc_delay, b->afc_est, b->afc_audio};
     for (void *p : ptrs)
         if (p) (void) hipFree(p);
     for (auto &set : b->evr)
@@ -706,6 +718,20 @@ static int chan_zero_state(gnuais_batch *b)
     return GNUAIS_OK;
 }
 
+// the AFC stage's carry: row count, delay line, block sums (window kept)
+static int afc_zero_state(gnuais_batch *b)
+{
+    if (b->afc_W) {
+        const size_t N = (size_t) b->N;
+        HIP_TRY(hipMemset(b->afc_delay, 0, sizeof(int16_t) * N * (size_t) (b->afc_W / 2)));
+        HIP_TRY(hipMemset(b->afc_blk, 0, sizeof(int64_t) * 2 * N * (size_t) b->afc_nb));
+    }
+    b->afc_n = 0;
+    b->afc_est_row = -1;
+    b->last[AFC].used = false;
+    return GNUAIS_OK;
+}
+
 int gnuais_batch_reset(gnuais_batch *b)
 {
     if (!b) return fail(GNUAIS_E_ARG, "reset: NULL batch");
@@ -739,6 +765,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     HIP_TRY(hipMemset(b->iq_prev, 0, sizeof(int16_t) * 2 * N));       // the discriminator's previous pair: (0, 0)
     b->last[DISC].used = false;
     if (int rc = chan_zero_state(b)) return rc;
+    if (int rc = afc_zero_state(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
     return GNUAIS_OK;
@@ -1264,9 +1291,13 @@ int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int l
 
 // ---- complex baseband in (include/gnuais_hip.h): the discriminator (iq_disc.hip) in front of the unchanged chain ----
 
-static int disc_launch(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s)
+// afc: the launch also takes the block sums of the rows from afc_n on (afc_launch follows on the same stream)
+static int disc_launch(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s, bool afc = false)
 {
-    HIP_TRY(launch_iq_discriminator(d_iq, d_out, b->iq_prev, b->N, len, s));
+    if (afc)
+        HIP_TRY(launch_iq_discriminator_afc(d_iq, d_out, b->iq_prev, b->N, len, b->afc_blk, b->afc_nb, b->afc_n, s));
+    else
+        HIP_TRY(launch_iq_discriminator(d_iq, d_out, b->iq_prev, b->N, len, s));
     b->last[DISC] = {s, true};
     return GNUAIS_OK;
 }
@@ -1278,6 +1309,82 @@ int gnuais_batch_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int
     if (int rc = set_device(b)) return rc;
     if (int rc = drain(b, 1u << DISC, (hipStream_t) stream)) return rc;
     return disc_launch(b, d_iq, len, d_out, (hipStream_t) stream);
+}
+
+// ---- the carrier-error stage (include/gnuais_hip.h, afc.hip) between the discriminator and the chain ----
+
+int gnuais_batch_afc(gnuais_batch *b, int window)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "afc: NULL batch");
+    if (window && (window < AFC_MIN_WINDOW || window > AFC_MAX_WINDOW || window % (2 * AFC_BLOCK)))
+        return fail(GNUAIS_E_ARG, "afc: the window must be 0 (off) or a multiple of 128 from 128 to 16384");
+    if (int rc = set_device(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (void *p : {(void *) b->afc_blk, (void *) b->afc_delay, (void *) b->afc_est})
+        if (p) HIP_TRY(hipFree(p));
+    b->afc_blk = nullptr;
+    b->afc_delay = b->afc_est = nullptr;
+    b->afc_W = 0;
+    if (window) {
+        const size_t N = (size_t) b->N;
+        const int call_blocks = (b->max_len + AFC_BLOCK - 1) / AFC_BLOCK + 1;      // a call that starts inside a block
+        // the blocks of the oldest window a call reads up to the last one it writes
+        b->afc_nb = window / AFC_BLOCK + call_blocks + 1;
+        if (int rc = alloc_checked(b, b->afc_blk, sizeof(int64_t) * 2 * N * (size_t) b->afc_nb, "afc", "the block sums")) return rc;
+        if (int rc = alloc_checked(b, b->afc_delay, sizeof(int16_t) * N * (size_t) (window / 2), "afc", "the delay line")) return rc;
+        if (int rc = alloc_checked(b, b->afc_est, sizeof(int16_t) * N * (size_t) call_blocks, "afc", "the estimates")) return rc;
+        b->afc_W = window;
+    }
+    if (int rc = afc_zero_state(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return GNUAIS_OK;
+}
+
+// behind disc_launch(.., afc = true) on s: the estimates of the blocks this call's output rows need, then the corrected
+// audio of its len rows
+static int afc_launch(gnuais_batch *b, const int16_t *d_audio, int len, int16_t *d_out, hipStream_t s)
+{
+    const unsigned long long n0 = b->afc_n, n1 = n0 + (unsigned long long) len, L = (unsigned long long) (b->afc_W / 2);
+    long long j_lo = 0;
+    if (n1 > L) {                                // row n1 - 1 has m >= 0: blocks (max(n0 - L, 0)) / 64 .. (n1 - 1 - L) / 64
+        j_lo = (long long) ((n0 > L ? n0 - L : 0) / AFC_BLOCK);
+        const int n_est = (int) ((long long) ((n1 - 1 - L) / AFC_BLOCK) - j_lo) + 1;
+        HIP_TRY(launch_afc_estimate(b->afc_blk, b->afc_nb, b->N, b->afc_est, j_lo, n_est, b->afc_W, s));
+        b->afc_est_row = n_est - 1;
+    }
+    HIP_TRY(launch_afc_apply(d_audio, b->afc_delay, b->afc_est, j_lo, d_out, b->N, len, b->afc_W, n0, s));
+    b->afc_n = n1;
+    b->last[AFC] = {s, true};
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_afc_apply(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream)
+{
+    if (!b || !d_iq || !d_out) return fail(GNUAIS_E_ARG, "afc_apply: NULL argument");
+    if (!b->afc_W) return fail(GNUAIS_E_STATE, "afc_apply: the AFC is off (gnuais_batch_afc)");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "afc_apply: len out of range (max_len)");
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s = (hipStream_t) stream;
+    if (int rc = drain(b, 1u << DISC | 1u << AFC, s)) return rc;
+    if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), "afc_apply", "the discriminator's audio"))
+        return rc;
+    if (int rc = disc_launch(b, d_iq, len, b->iq_audio, s, true)) return rc;
+    return afc_launch(b, b->iq_audio, len, d_out, s);
+}
+
+int gnuais_batch_afc_estimate(gnuais_batch *b, int16_t *h_out)
+{
+    if (!b || !h_out) return fail(GNUAIS_E_ARG, "afc_estimate: NULL argument");
+    if (!b->afc_W) return fail(GNUAIS_E_STATE, "afc_estimate: the AFC is off (gnuais_batch_afc)");
+    if (int rc = set_device(b)) return rc;
+    if (b->afc_est_row < 0) {
+        memset(h_out, 0, sizeof(int16_t) * (size_t) b->N);
+        return GNUAIS_OK;
+    }
+    if (b->last[AFC].used) HIP_TRY(hipStreamSynchronize(b->last[AFC].s));
+    HIP_TRY(hipMemcpy(h_out, b->afc_est + (size_t) b->afc_est_row * (size_t) b->N, sizeof(int16_t) * (size_t) b->N,
+                      hipMemcpyDeviceToHost));
+    return GNUAIS_OK;
 }
 
 // ---- wideband in (include/gnuais_hip.h): the channeliser (channeliser.hip) in front of the discriminator ----
@@ -1503,23 +1610,29 @@ static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void 
     if (int rc = check_input(b, id, x, len, who, false)) return rc;
     if (int rc = set_device(b)) return rc;
     const Form f = form(b, id);
-    const bool chan = f.stages >> CHAN & 1u, disc = f.stages >> DISC & 1u;
+    const bool chan = f.stages >> CHAN & 1u, disc = f.stages >> DISC & 1u, afc = f.stages >> AFC & 1u;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = drain(b, f.stages, s)) return rc;
-    // the channeliser writes max_len rows of the I/Q form, the discriminator max_len rows of the audio form
+    // the channeliser writes max_len rows of the I/Q form, the discriminator and the AFC max_len rows of the audio form
     if (chan)
         if (int rc = alloc_checked(b, b->ch_iq, form(b, IQ).bytes_of(b->max_len), who, "the channeliser's I/Q")) return rc;
     if (disc)
         if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the discriminator's audio"))
             return rc;
+    if (afc)
+        if (int rc = alloc_checked(b, b->afc_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the AFC's audio")) return rc;
     if (chan) {
         if (int rc = chan_launch(b, x, len, b->ch_iq, s)) return rc;
         x = b->ch_iq;
     }
     len /= f.rows;
     if (disc) {
-        if (int rc = disc_launch(b, x, len, b->iq_audio, s)) return rc;
+        if (int rc = disc_launch(b, x, len, b->iq_audio, s, afc)) return rc;
         x = b->iq_audio;
+    }
+    if (afc) {
+        if (int rc = afc_launch(b, x, len, b->afc_audio, s)) return rc;
+        x = b->afc_audio;
     }
     return gnuais_batch_run(b, x, len, stream);
 }
@@ -2262,6 +2375,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "n_effective_taps")) *value = b->NE;
     else if (!strcmp(name, "compute_units")) *value = b->n_cu;
     else if (!strcmp(name, "device")) *value = b->device;
+    else if (!strcmp(name, "afc_window")) *value = b->afc_W;
     else if (!strcmp(name, "segments")) *value = b->n_seg;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now

@@ -132,6 +132,22 @@ hipError_t launch_crc16_bits(const uint8_t *bits, int n_bytes, uint16_t *crc, ui
 constexpr int IQ_DISC_ROWS = 64;     // rows per thread (a segment); each segment reads one row more
 hipError_t launch_iq_discriminator(const int16_t *iq, int16_t *out, int16_t *carry, int N, int len, hipStream_t stream);
 
+// ---- the carrier-error stage behind the discriminator (AFC: afc.hip, definition in include/gnuais_hip.h) ----
+// n0 = rows the stage has taken before this call.  Three launches on one stream, in this order:
+//   launch_iq_discriminator_afc  the discriminator, which also sums r and i over the blocks of AFC_BLOCK rows of n into
+//                                blk [nb][N][2] int64 (block j in slot j % nb; nb >= W/64 + max_len/64 + 2);
+//   launch_afc_estimate          e_j from the window sums, for the n_est blocks from j_lo on, into est [n_est][N];
+//   launch_afc_apply             out[n] = a[n - W/2] - e, a from delay [W/2][N] (a[m] in row m % (W/2)) or from `audio`,
+//                                est row 0 = block j_lo; then the call's last W/2 audio rows go into delay.
+constexpr int AFC_BLOCK = 64;
+constexpr int AFC_MIN_WINDOW = 128, AFC_MAX_WINDOW = 16384;
+hipError_t launch_iq_discriminator_afc(const int16_t *iq, int16_t *out, int16_t *carry, int N, int len, int64_t *blk,
+                                       int nb, unsigned long long n0, hipStream_t stream);
+hipError_t launch_afc_estimate(const int64_t *blk, int nb, int N, int16_t *est, long long j_lo, int n_est, int W,
+                               hipStream_t stream);
+hipError_t launch_afc_apply(const int16_t *audio, int16_t *delay, const int16_t *est, long long j_lo, int16_t *out, int N,
+                            int len, int W, unsigned long long n0, hipStream_t stream);
+
 // ---- wideband in: the channeliser (channeliser.hip) -------------------------------------
 // in [len][M][2] int16 -> out [len/D][M*K][2] int16, the definition in include/gnuais_hip.h.  hist [T-1][M] words is the
 // carry (the last T-1 wide samples), read here; the launch writes the next one into hist_out (another buffer).

@@ -404,6 +404,12 @@ int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const in
     return rc;
 }
 
+int gnuais_node_afc(gnuais_node *nd, int window)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_afc: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_afc(s.b, window); });
+}
+
 int gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len)
 {
     if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: NULL argument");

@@ -36,6 +36,9 @@ SYMBOLS = {
     "gnuais_batch_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_iq_host": (_I, [_P, _P, _I]),
     "gnuais_batch_discriminate": (_I, [_P, _P, _I, _P, _P]),
+    "gnuais_batch_afc": (_I, [_P, _I]),
+    "gnuais_batch_afc_estimate": (_I, [_P, _P]),
+    "gnuais_batch_afc_apply": (_I, [_P, _P, _I, _P, _P]),
     "gnuais_batch_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gnuais_batch_run_wideband": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_wideband_host": (_I, [_P, _P, _I]),
@@ -107,6 +110,7 @@ SYMBOLS = {
     "gnuais_node_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_node_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gnuais_node_run_wideband_host": (_I, [_P, _P, _I]),
+    "gnuais_node_afc": (_I, [_P, _I]),
     "gnuais_node_sync": (_I, [_P]),
     "gnuais_node_pending_frames": (_I, [_P, C.POINTER(_I)]),
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),

@@ -110,6 +110,26 @@ class ReceiverBatch:
         stream.synchronize()
         return out
 
+    def afc(self, window: int):
+        """Carrier-error correction of I/Q input (gnuais_batch_afc, defined in include/gnuais_hip.h): window = 0 switches
+        it off (the default), else the estimator's window in samples (a multiple of 128, 128 .. 16384; 2048 suits 48 kHz,
+        8192 192 kHz).  From then on run_iq / run_wideband subtract each channel's estimated carrier error before the
+        chain, which sees the audio W/2 samples late.  Clears the AFC state."""
+        check(self._lib.gnuais_batch_afc(self._h, int(window)))
+
+    def afc_estimate(self) -> np.ndarray:
+        """int16 [n_channels]: each channel's carrier-error estimate at the last output row, in discriminator units
+        (Hz = e * rate / 65536); zeros before there is an output row."""
+        out = np.zeros(self.n_channels, dtype=np.int16)
+        check(self._lib.gnuais_batch_afc_estimate(self._h, out.ctypes.data))
+        return out
+
+    def afc_apply(self, samples):
+        """Discriminator and AFC alone (gnuais_batch_afc_apply): int16 [len][n_channels][2] -> torch int16
+        [len][n_channels] on the device, the audio the chain would see; advances the I/Q carry and the AFC state."""
+        return self._stage(samples, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
+                           lambda n: (n, self.n_channels), self._lib.gnuais_batch_afc_apply)
+
     def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
         """Configure the wideband channeliser (gnuais_batch_channeliser, defined in include/gnuais_hip.h): the batch's
         n_channels receivers become n_channels / K wide streams x K offsets (receiver s*K + k = stream s at

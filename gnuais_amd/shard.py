@@ -83,6 +83,10 @@ class ReceiverNode:
                                                       None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
         self._chan_k = int(off.size)
 
+    def afc(self, window: int):
+        """Carrier-error correction of I/Q input (gnuais_node_afc): ReceiverBatch.afc on every shard."""
+        self._raise(self._lib.gnuais_node_afc(self._h, int(window)))
+
     def run_wideband_host(self, samples):
         """Wideband in (gnuais_node_run_wideband_host): one host array int16 [len][n_channels / K][2] of wide streams."""
         k = getattr(self, "_chan_k", 1)

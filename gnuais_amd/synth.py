@@ -122,18 +122,23 @@ def make_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int = 5
 
 def make_iq_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int = 5,
                    amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
-                   payloads=None, bt: float = 0.4):
+                   payloads=None, bt: float = 0.4, offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False):
     """One channel of synthetic complex baseband: what an SDR front end or a channeliser hands over.
 
     The same bursts as make_stream() (slots, training, flags, NRZI, Gaussian shaping) as h = 0.5 GMSK: the phase is the
     running sum of (pi/2/sps) * the shaped level, from a random initial phase; I/Q = amplitude * (cos, sin) + white
     Gaussian noise of `sigma` on each, rounded and clamped to int16.  Its own random sequence (make_stream's is left as
-    it is).  Returns (int16[n_samples][2], list of (slot, payload bytes) actually placed).
+    it is).  offset_hz: a carrier error, the phase advances by 2 pi offset_hz / rate_hz more per sample (an SDR's
+    oscillator).  gated: the carrier is on only from 2 bits before a burst to 2 bits after it, as on a real channel,
+    which holds noise between bursts (otherwise an unmodulated carrier stays on).  Neither draws a random number: with
+    the defaults the output is what it was before they existed.
+    Returns (int16[n_samples][2], list of (slot, payload bytes) actually placed).
     """
     rng = np.random.default_rng([seed, channel, 0x4951])
     slot_len = SLOT_BITS * sps
     n_slots = (n_samples + slot_len - 1) // slot_len
     level = np.zeros(n_slots * slot_len + 64 * sps, dtype=np.float64)
+    on = np.zeros(level.size, dtype=bool)
     placed = []
     for slot in range(n_slots):
         if payloads is not None:
@@ -147,30 +152,38 @@ def make_iq_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int 
         start = slot * slot_len + START_OFFSET_BITS * sps
         end = min(start + lev.size, level.size)
         level[start:end] = lev[: end - start]
+        on[max(start - 2 * sps, 0):end + 2 * sps] = True
         placed.append((slot, payload))
     shaped = np.convolve(level, gaussian_kernel(sps, bt), mode="same")[:n_samples]
     phase = rng.uniform(-np.pi, np.pi) + np.cumsum(shaped * (np.pi / 2.0 / sps))
+    if offset_hz:
+        phase = phase + (2.0 * np.pi * float(offset_hz) / float(rate_hz)) * np.arange(n_samples, dtype=np.float64)
     iq = np.stack([amplitude * np.cos(phase), amplitude * np.sin(phase)], axis=1)
+    if gated:
+        iq[~on[:n_samples]] = 0.0
     if sigma > 0:
         iq += rng.normal(0.0, sigma, iq.shape)
     return np.clip(np.rint(iq), -32768, 32767).astype(np.int16), placed
 
 
 def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz, seed: int = SEED, stream: int = 0,
-                         amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5):
+                         amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
+                         offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False):
     """One wide complex stream as an SDR records it: a channel of AIS at each of `offsets_hz` (Hz from the tuned
     frequency) at `in_rate_hz`, for a channeliser that decimates by `decim` to the chain's rate.
 
     Offset k carries noise-free make_iq_stream() bursts at sps = 5 * decim from a seed of its own, shifted by
     e^{+j 2 pi f_k n / R}; the offsets are summed, white Gaussian noise of `sigma` is added to I and Q, and the result is
-    rounded and clamped to int16.  Returns (int16[n_samples][2], [placed payloads of offset k, for each k]).
+    rounded and clamped to int16.  offset_hz: a carrier error of the whole stream (every channel lies that much off its
+    nominal offset); rate_hz: the narrowband rate (the wide one is rate_hz * decim); gated as in make_iq_stream.  Returns (int16[n_samples][2], [placed payloads of offset k, for each k]).
     """
     n = np.arange(n_samples, dtype=np.float64)
     acc = np.zeros(n_samples, dtype=np.complex128)
     placed = []
     for k, f in enumerate(offsets_hz):
         iq, pl = make_iq_stream(n_samples, seed=seed + 65537 * (k + 1), channel=stream, sps=5 * decim,
-                                amplitude=amplitude, sigma=0.0, occupancy=occupancy)
+                                amplitude=amplitude, sigma=0.0, occupancy=occupancy, offset_hz=offset_hz,
+                                rate_hz=float(rate_hz) * decim, gated=gated)
         z = iq[:, 0].astype(np.float64) + 1j * iq[:, 1].astype(np.float64)
         acc += z * np.exp(2j * np.pi * float(f) * n / float(in_rate_hz))
         placed.append(pl)

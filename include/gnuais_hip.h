@@ -207,6 +207,40 @@ int  gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, in
 int  gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps);
 int  gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period);
 
+/* ---- carrier frequency error of I/Q input: an AFC stage on the device between the discriminator and the chain ----
+ * Not in the reference (a sound card is AC coupled).  A carrier error of f Hz adds the constant f * 65536 / rate to
+ * every discriminator output; an SDR's oscillator is off by several kHz at 162 MHz, more than the AIS deviation, and
+ * the slicer decides on the sign alone.  With a window W set, every I/Q-type call (gnuais_batch_run_iq,
+ * gnuais_batch_run_wideband, their host forms, gnuais_batch_afc_apply) estimates each channel's error over a centred
+ * window and subtracts it; the chain sees the corrected audio delayed by W/2 samples.  Off by default: with W = 0 every
+ * call launches the kernels and gives the bits it gives without this section.
+ *   W = window in samples, a multiple of 128, 128 <= W <= 16384.  B = 64, Wb = W/64 (even), L = W/2.
+ *   Suggested: 2048 at 48 kHz, 8192 at 192 kHz (43 ms; DESIGN.md 4.10 has the decode counts of 512, 1024 and 2048).
+ *   n counts the rows that I/Q-type calls have passed to the discriminator since gnuais_batch_afc() or
+ *   gnuais_batch_reset().  Per channel, everything integer except the phase of a window sum:
+ *     (I, Q) = pair n, (Ip, Qp) = pair n-1, exactly the discriminator's carry ((0, 0) at the start)
+ *     r[n] = I*Ip + Q*Qp,  i[n] = Q*Ip - I*Qp           exact integers (r reaches 2^31: wider than int32)
+ *     a[n] = the discriminator's output, definition above, unchanged
+ *     R_j = sum of r[n], I_j = sum of i[n] over n in [64j, 64j + 64)                          int64 block sums
+ *     SR_j = sum of R_k, SI_j = sum of I_k over k in [j - Wb/2, j + Wb/2), R_k = I_k = 0 for k < 0   (|SR| < 2^46)
+ *     e_j = the discriminator's formula from ax = |re| onward with re = (float) SR_j, im = (float) SI_j
+ *           (int64 -> fp32, round to nearest even); same constants, same order, same rint and clamp; SR = SI = 0 gives 0
+ *     output row n: m = n - L;  m < 0: 0;  else out[n] = (int16) (a[m] - e_{m div 64}), two's-complement wrap
+ *   (phase arithmetic modulo 2 pi).  Every block that e_{m div 64} needs is complete at row n-1, so a call of len rows
+ *   gives len rows and the result does not depend on how the stream is cut into calls.
+ * Carried per channel: the last L audio samples, the ring of block sums, the open block; all zero after
+ * gnuais_batch_afc() and after gnuais_batch_reset(), which keeps the window.  Audio run calls and
+ * gnuais_batch_discriminate() neither read nor change any of it. */
+/* window = 0: off (default), else W; other values GNUAIS_E_ARG.  Synchronises the device and clears the AFC state. */
+int  gnuais_batch_afc(gnuais_batch *b, int window);
+/* e_j of the last output row of each channel (0 before there is one) into h_out[n_channels]; Hz = e * rate / 65536:
+ * what to read for an SDR's ppm.  Waits for the last I/Q-type call's AFC stage.  GNUAIS_E_STATE while the AFC is off. */
+int  gnuais_batch_afc_estimate(gnuais_batch *b, int16_t *h_out /* [n_channels] */);
+/* discriminator + AFC only (a parity tap, as gnuais_batch_discriminate): d_iq DEVICE int16 [len][n_channels][2], d_out
+ * DEVICE int16 [len][n_channels]; advances the I/Q carry and the AFC state, nothing else.  Asynchronous on `stream`.
+ * GNUAIS_E_STATE while the AFC is off. */
+int  gnuais_batch_afc_apply(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream);
+
 /* ---- input side, row f2: sample files -> interleaved int16 frames (src/ais.c:173-182,214-217) ---
  * raw_channels > 0: the file is a bare stream of little-endian int16 frames of that many channels,
  *   header and all, exactly as the reference reads a sound file; 0: parse RIFF/WAVE (16-bit PCM,
@@ -244,7 +278,7 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
 /* facts about a batch, by name: "sign_exact" (1 if the receive path runs the sign-exact slicer),
  * "sign_eps" (its certification threshold), "sign_central_taps", "first_effective_tap",
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
- * gnuais_batch_stream_nmea() call and the one that hands its text out) */
+ * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
 /* ---- results ------------------------------------------------------------------
@@ -492,6 +526,8 @@ int  gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const i
 /* one HOST buffer int16 [len][N/K][2] of wide streams; every shard copies the columns of its own streams,
  * [first/K, (first+n)/K), and runs channeliser, discriminator and chain; returns when the buffer may be reused */
 int  gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len);
+/* gnuais_batch_afc() on every shard */
+int  gnuais_node_afc(gnuais_node *nd, int window);
 int  gnuais_node_sync(gnuais_node *nd);
 /* merged results: records of every device, channel = global index, reference order (channel, then time) */
 int  gnuais_node_pending_frames(gnuais_node *nd, int *n_out);

@@ -6,6 +6,10 @@
   python scripts/decode_file.py sdr.wav --wideband 6 --offsets -25000,25000
                                                       # wide I/Q (2M channels = M streams) at R = 6 x 48 kHz, each
                                                       # stream channelised on the device to one receiver per offset
+  python scripts/decode_file.py iq.wav --iq --afc 2048
+                                                      # --iq / --wideband: remove each receiver's carrier error on the device
+                                                      # (an SDR's oscillator), estimated over a window of that many samples;
+                                                      # the measured errors go to stderr
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -25,6 +29,9 @@ def main():
                          "decimate by D on the device, one receiver per stream and offset (receiver s*K + k)")
     ap.add_argument("--offsets", default="-25000,25000", help="--wideband: offsets in Hz from the tuned frequency")
     ap.add_argument("--rate", type=int, default=0, help="--wideband with --raw: the input rate in Hz")
+    ap.add_argument("--afc", type=int, default=0, metavar="W",
+                    help="--iq / --wideband: carrier-error correction over a window of W samples (a multiple of 128; "
+                         "2048 suits 48 kHz), 0 = off")
     ap.add_argument("--call", type=int, default=48000, help="frames per device call (at the chain's rate)")
     a = ap.parse_args()
     import torch
@@ -34,6 +41,8 @@ def main():
     else:
         rate, x = io.read_wav(a.path)
     n_ch = x.shape[1]
+    if a.afc and not (a.iq or a.wideband):
+        sys.exit("--afc needs --iq or --wideband: audio input has no carrier")
     if a.wideband:
         return decode_wideband(a, rate, x)
     if a.iq:
@@ -42,6 +51,9 @@ def main():
         n_ch //= 2
         x = x.reshape(x.shape[0], n_ch, 2)
     b = ReceiverBatch(n_ch, max_len=a.call)
+    if a.afc:
+        b.afc(a.afc)
+        x = afc_flush(x, a.afc // 2)
     seq = np.zeros(n_ch, dtype=np.uint8)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
@@ -54,6 +66,18 @@ def main():
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
+    afc_report(a, b, 48000)
+
+
+def afc_flush(x, rows):
+    """The AFC delays the audio by half its window: that many zero pairs push the end of the file through the chain."""
+    return np.concatenate([x, np.zeros((rows,) + x.shape[1:], dtype=x.dtype)])
+
+
+def afc_report(a, b, rate):
+    if a.afc:
+        hz = b.afc_estimate().astype(np.float64) * rate / 65536.0
+        sys.stderr.write("carrier error at the end of the file, Hz per receiver: " + " ".join(f"{v:+.0f}" for v in hz) + "\n")
 
 
 def decode_wideband(a, rate, x):
@@ -70,6 +94,9 @@ def decode_wideband(a, rate, x):
     x = x[: x.shape[0] // D * D].reshape(-1, M, 2)
     b = ReceiverBatch(n_ch, max_len=a.call)
     b.channeliser(D, rate, offsets)
+    if a.afc:
+        b.afc(a.afc)
+        x = afc_flush(x, a.afc // 2 * D)
     seq = np.zeros(n_ch, dtype=np.uint8)
     for part in io.chunks(x, a.call * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda())
@@ -78,6 +105,7 @@ def decode_wideband(a, rate, x):
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
+    afc_report(a, b, rate // D)
 
 
 if __name__ == "__main__":
