@@ -417,38 +417,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-// 24-bit integer taps in three signed int8 digits, laid out as the A operands of the five blocks; false when the table
-// does not fit (a tap too large for the scale).  bound_q: sum |tq / S - tc| (what the quantisation adds to the
-// certification bound, per unit of |x|); scale: S.
-bool fir_sign_mfma_taps(const float *tc48, MfmaTaps *out, double *scale, double *bound_q)
+// The 24-bit integer taps (fir_plan.cpp: SignBounds::tq, their sum) in three signed int8 digits, laid out as the A operands
+// of the blocks.  Layout only: that every tap fits three digits is the quantiser's check.
+void fir_sign_mfma_pack(const int *tq48, long tq_sum, MfmaTaps *out)
 {
-    double sabs = 0;
-    for (int q = 0; q < MF_NC; ++q) sabs += fabs((double) tc48[q]);
-    if (!(sabs > 0) || !isfinite(sabs)) return false;
-    int e = 0;
-    (void) frexp(8388608.0 / sabs * 0.999, &e);        // the largest power of two at or below 2^23 / sum |tc| (a power of two:
-    const double S = ldexp(1.0, e - 1);                //  tq / S is then exact in double and fp32 alike)
-    long tq[MF_NC], sumtq = 0, sumabs = 0;
-    double bq = 0;
-    for (int q = 0; q < MF_NC; ++q) {
-        tq[q] = lround((double) tc48[q] * S);
-        sumtq += tq[q];
-        sumabs += labs(tq[q]);
-        bq += fabs((double) tq[q] / S - (double) tc48[q]);
-    }
-    if (sumabs >= 8388608 - 64) return false;
     for (int b = 0; b < MF_NB; ++b)
         for (int lane = 0; lane < 64; ++lane) {
             const int i = lane & 31;
             uint32_t v[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
             for (int j = 0; j < MF_BR; ++j) {
                 const int k = MF_BR * (lane >> 5) + j, q = 32 * b + k - i;
-                long t = (q >= 0 && q < MF_NC) ? tq[q] : 0;
+                long t = (q >= 0 && q < MF_NC) ? tq48[q] : 0;
                 // signed digits: t = 65536 t2 + 256 t1 + t0, each in [-128, 127]
                 const long t0 = ((t + 128) & 255) - 128; t = (t - t0) >> 8;
                 const long t1 = ((t + 128) & 255) - 128; t = (t - t1) >> 8;
                 const long t2 = t;
-                if (t2 < -128 || t2 > 127) return false;
                 v[0][j >> 2] |= (uint32_t) (uint8_t) (int8_t) t0 << (8 * (j & 3));
                 v[1][j >> 2] |= (uint32_t) (uint8_t) (int8_t) t1 << (8 * (j & 3));
                 v[2][j >> 2] |= (uint32_t) (uint8_t) (int8_t) t2 << (8 * (j & 3));
@@ -456,13 +439,11 @@ bool fir_sign_mfma_taps(const float *tc48, MfmaTaps *out, double *scale, double 
             for (int dgt = 0; dgt < 3; ++dgt)
                 for (int w = 0; w < 4; ++w) out->a[b][dgt][lane][w] = (int) v[dgt][w];
         }
-    out->k0 = (int) (128 * sumtq);
-    *scale = S;
-    *bound_q = bq;
-    return true;
+    out->k0 = (int) (128 * tq_sum);
 }
 
-int launch_fir_sign_mfma_quantum() { return 128; }
+// T and `first` are whole multiples of 128 (the launcher below); plan_fir (fir_plan.cpp) rounds T and the packed head to that
+static_assert(MF_NC == FIR_MFMA_NC && FIR_Q_MFMA == 128, "fir_plan.h and this file disagree");
 
 // outputs first .. L - 1 in segments of T (the packed kernel takes the call's first `first` outputs, whose windows reach
 // into the history): a.mfma = the device copy of the taps, a.eps_seen / a.eps_ahead = the threshold in units of y' per unit of

@@ -474,7 +474,9 @@ PK_KERNEL(fir_sign_pk48_kernel, 48, true, PK48_VGPR_BUDGET)
 } // namespace
 
 // whole unrolled turns and whole 16-byte sign stores per segment: lcm(unrolled phases, 128)
-int launch_fir_sign_pk_quantum(int NC) { return pk_unroll(NC) * 128 / pk_gcd(pk_unroll(NC), 128); }
+constexpr int pk_quantum(int NC) { return pk_unroll(NC) * 128 / pk_gcd(pk_unroll(NC), 128); }
+static_assert(pk_quantum(40) == FIR_Q_PK40 && pk_quantum(48) == FIR_Q_PK48, "plan_fir (fir_plan.cpp) rounds T to these");
+int launch_fir_sign_pk_quantum(int NC) { return pk_quantum(NC); }
 
 namespace {
 

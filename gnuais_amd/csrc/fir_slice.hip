@@ -907,6 +907,7 @@ int launch_fir_sign_quantum(int NC)
 {
     // the 12-tap kernel stores four sign words at once: segments start on a multiple of 128 outputs
     // (the 48-tap one too, and its unrolled body is three words: 384)
+    static_assert(FIR_Q_SIGN12 == 128 && FIR_Q_SIGN48 == 384, "plan_fir (fir_plan.cpp) rounds T to these");
     return NC <= 12 ? 128 : 384;
 }
 

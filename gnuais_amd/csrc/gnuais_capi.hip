@@ -115,10 +115,6 @@ struct gnuais_batch {
     gnuais_frame *frames = nullptr;
     float *d_taps = nullptr;
     MfmaTaps *d_mfma = nullptr;     // fir_sign_mfma.hip: the 48 central taps as integer Toeplitz operands (long tables)
-    bool mfma_ok = false;
-    MfmaTaps mfma_host;
-    float mfma_eps_seen_u = 0.0f, mfma_eps_abs_u = 0.0f;     // its threshold in units of y' = floor(sum tq x / 256): per unit of max |x|, absolute
-    int fir_mfma = 1;               // 1: long tables run their inner segments on the matrix pipe where the batch allows it
     // f1 on the device (gnuais_batch_drain_nmea): allocated on first use
     uint8_t *d_seq[2] = {nullptr, nullptr};
     char *d_text = nullptr;
@@ -173,25 +169,9 @@ struct gnuais_batch {
     hipEvent_t e_in_hook = nullptr;             // run_host_async -> run: record this right behind K1
     unsigned long long host_calls = 0;
     // options
-    int fir_T = 512;
-    int fir_map = 1;                            // K1s workgroup mapping (fir_slice.hip): XCD-contiguous channel groups
+    FirOptions fir;                             // the fir_* options the choice of the FIR kernel depends on (fir_plan.h)
+    SignBounds sign;                            // the sign-exact slicer's error bounds for the table (fir_plan.h)
     int stage_mask = 0x1f;                      // experiments only: bit s = launch stage s
-    int fir_variant = 3;            // 3 sign-exact slicer (default when the table allows);
-                                    // 0 the exact ordered sum for every sample
-    bool sign_ok = false;           // table is 32 symmetric effective taps: K1s applicable
-    float sign_eps = 0.0f;
-    float sign_eps_pk = 0.0f;       // the same for the packed transposed kernel's order of operations
-    float sign_eps_seen = 0.0f, sign_eps_ahead = 0.0f;   // sign_eps split: what scales with the samples seen / what cannot
-    bool pk40_ok = false;           // the table allows 40 central taps where sign_NC is 48 (fir_sign_pk.hip)
-    float pk40_eps_pk = 0.0f, pk40_eps_seen = 0.0f, pk40_eps_ahead = 0.0f;
-    // the packed kernel's bound per output position in its 16-row group: the group's later rows are under the running
-    // maximum too, so an output that completes k rows before the group's end has k rows fewer "ahead" ([0..3]: k >= 6, 4, 2, 0)
-    float pk_seen_k[2][4] = {}, pk_ahead_k[2][4] = {};      // [0]: 48 central taps, [1]: 40
-    int fir_pk_taps = 0;            // 0: 40 where the table allows it; 48: never 40
-    int fir_inloop = 1;             // 48-tap K1s: running window maximum in the loop (0: the per-segment pre-pass)
-    int sign_NC = 12;               // central taps K1s evaluates
-    int fir_flag2 = 1;              // the direct-form K1s gathers sign and threshold bit with one instruction per output (FL2)
-    float sign_fscale = 0.0f;       //   the power of two its central taps are scaled by (0: the table does not allow it)
     int k0 = 0;                     // first effective tap
     int pll_variant = 0;            // 0: by channel count; 7 / 8 (kernels.h: PllLaunch::variant)
     int hdlc_lpw = 0;               // channels per wave in K2b; 0 = the variant's own default (16 event-driven, 64 bit-serial)
@@ -449,133 +429,10 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     b->NE = k1 - k0 + 1;
     b->d = b->NT - k0;
     b->k0 = k0;
-    if (b->NE <= 128)
+    if (b->NE <= FIR_MAX_NE)
         for (int j = 0; j < b->NE; ++j) b->te[j] = b->taps[k0 + j];
 
-    {
-        // sign-exact slicer (fir_slice.hip K1s): error budget of the NC central taps against the
-        // reference's ordered NE-term fp32 sum, for |x| <= 32768.  The smallest NC the kernel is
-        // built for (12, 48) whose bound stays small enough is used: 12 for the reference table
-        // (32 effective taps, bound 0.23), 48 for the 192 kHz table (126 taps, bound 0.87).  40 is
-        // evaluated on the way as the packed kernel's alternative to 48 (fir_sign_pk.hip; the 192 kHz
-        // table: bound 1.4, a sixth fewer multiply-adds).
-        const int NE = b->NE;
-        bool sym = NE <= 128;
-        for (int j = 0; sym && j < NE; ++j) sym = memcmp(&b->te[j], &b->te[NE - 1 - j], 4) == 0;
-        for (int NC : {12, 40, 48}) {
-            if (!sym || b->sign_ok || NE < NC || (NE - NC) % 2) continue;
-            const double u = 5.9604644775390625e-8, X = 32768.0;
-            const int J0 = (NE - NC) / 2;
-            // An ordered fp32 sum s_1 = fl(p_1), s_j = fl(s_{j-1} + fl(p_j)) of n products carries
-            // product i with the factor (1+d_i) * prod_{j=max(i,2)..n} (1+e_j), |d|,|e| <= u: k_i = n
-            // rounding factors for i = 1, n-i+2 for i >= 2 (Higham, Accuracy and Stability, sec. 4.2).
-            // So |s_n - S| <= X * sum_i |t_i| * ((1+u)^k_i - 1): the late terms of the sum, and for a
-            // bell-shaped table the big central ones are late enough, pass through few additions.
-            // The reference adds in tap order (filter.h:40-49); K1s's accumulators take their NC
-            // products in sample order, which is tap order from one edge of the centre to the other
-            // (either edge: the table is symmetric).
-            auto ordered = [&](int first, int n) {
-                double e = 0;
-                for (int i = 1; i <= n; ++i)
-                    e += std::fabs((double) b->te[first + i - 1]) * (std::pow(1 + u, i == 1 ? n : n - i + 2) - 1);
-                return e;
-            };
-            double sum_out = 0;
-            for (int j = 0; j < NE; ++j)
-                if (j < J0 || j >= J0 + NC) sum_out += std::fabs((double) b->te[j]);
-            // + NE subnormal products, each off by at most 2^-150 (absolute)
-            // NC = 12 is evaluated in direct form: s_q = x_a + x_b (exact: both are int16-valued), then
-            // y = fl(t_0 s_0), y = fl(y + fl(t_q s_q)) for q = 1..NC/2-1, edge taps first; |s_q| <= 2X
-            auto paired = [&]() {
-                double e = 0;
-                const int n = NC / 2;
-                for (int i = 1; i <= n; ++i)
-                    e += 2.0 * std::fabs((double) b->te[J0 + i - 1]) * (std::pow(1 + u, i == 1 ? n : n - i + 2) - 1);
-                return e;
-            };
-            const double central = K1S_DIRECT(NC) ? paired() : ordered(J0, NC);
-            const double bound = X * (ordered(0, NE) + central + sum_out) + 1e-30;
-            if (NC == 40) {
-                // the packed kernel only (running window maximum: its window behind a group is 96 rows)
-                if (std::isfinite(bound) && bound < 2.0 && NC - 1 + J0 <= 96) {
-                    double ahead = 0;
-                    for (int i = J0 + NC + 1; i <= NE; ++i)
-                        ahead += std::fabs((double) b->te[i - 1]) * (1.0 + (std::pow(1 + u, NE - i + 2) - 1));
-                    b->pk40_ok = true;
-                    b->pk40_eps_pk = (float) (bound * 1.1);
-                    b->pk40_eps_ahead = (float) (X * ahead * 1.1 + 1e-30);
-                    b->pk40_eps_seen = (float) ((bound - X * ahead) * 1.1);
-                    for (int q = 0; q < 4; ++q) {
-                        double ah = 0;
-                        for (int i = J0 + NC + 1 + (6 - 2 * q); i <= NE; ++i)
-                            ah += std::fabs((double) b->te[i - 1]) * (1.0 + (std::pow(1 + u, NE - i + 2) - 1));
-                        b->pk_ahead_k[1][q] = (float) (X * ah * 1.1 + 1e-30);
-                        b->pk_seen_k[1][q] = (float) ((bound - X * ah) * 1.1);
-                    }
-                }
-                continue;
-            }
-            if (std::isfinite(bound) && bound < 2.0) {
-                b->sign_eps = (float) (bound * 1.1);
-                b->sign_eps_pk = (float) ((X * (ordered(0, NE) + ordered(J0, NC) + sum_out) + 1e-30) * 1.1);   // transposed sum (fir_sign_pk.hip)
-                b->sign_NC = NC;
-                b->sign_ok = true;
-                // The same bound in two parts, for the kernel that scales it with the largest |x| it has SEEN (the
-                // 48-tap instantiation, fir_slice.hip): the last J0 taps of a reference window multiply samples
-                // that lie up to J0 rows beyond the newest one the central sum has loaded; their share of the
-                // bound keeps X = 32768 (it is tiny: those taps are) and everything else scales with the maximum
-                // over the rows behind.  bound = part_seen + part_ahead.
-                double ahead = 0;
-                for (int i = J0 + NC + 1; i <= NE; ++i)      // 1-based tap index, as in ordered()
-                    ahead += std::fabs((double) b->te[i - 1]) * (1.0 + (std::pow(1 + u, NE - i + 2) - 1));
-                b->sign_eps_ahead = (float) (X * ahead * 1.1 + 1e-30);
-                b->sign_eps_seen = (float) ((bound - X * ahead) * 1.1);
-                for (int q = 0; q < 4; ++q) {
-                    double ah = 0;
-                    for (int i = J0 + NC + 1 + (6 - 2 * q); i <= NE; ++i)
-                        ah += std::fabs((double) b->te[i - 1]) * (1.0 + (std::pow(1 + u, NE - i + 2) - 1));
-                    b->pk_ahead_k[0][q] = (float) (X * ah * 1.1 + 1e-30);
-                    b->pk_seen_k[0][q] = (float) ((bound - X * ah) * 1.1);
-                }
-                if (NC == 48 && J0 <= 48) {
-                    // fir_sign_mfma.hip: the central sum in exact integer arithmetic on quantised taps -- the bound is the
-                    // reference's own rounding + the omitted taps + the quantisation, ALL of it per unit of the largest
-                    // |x| in reach of a window (its running maximum covers the rows behind and ahead), + 1 for the floor
-                    double S = 0, bq = 0;
-                    if (fir_sign_mfma_taps(&b->te[J0], &b->mfma_host, &S, &bq)) {
-                        const double rel = ordered(0, NE) + sum_out + bq;          // per unit of |x|, in units of y
-                        if (X * rel < 2.0) {
-                            b->mfma_ok = true;
-                            b->mfma_eps_seen_u = (float) (rel * (S / 256.0) * 1.1);
-                            b->mfma_eps_abs_u = 3.0f;
-                        }
-                    }
-                }
-                // FL2 (fir_sign_kernel): the direct form's central taps times k = 2 / P, P = the power of two at or above
-                // eps.  k is a power of two >= 1, so every product, pre-add and partial sum of the scaled evaluation is
-                // exactly k times the unscaled one (nothing overflows: |y'| <= 2 X sum|t| / eps < 1e9; an underflow the
-                // unscaled sum has, the scaled one has at most as badly) and |y_c| < P  <=>  |y'| < 2  <=>  exponent
-                // bit 7 of y' clear.  P >= eps: the band only widens.  Not taken when a central tap is subnormal or k
-                // would leave [1, 2^60].
-                auto flag_scale = [&](float eps, int nc) -> float {
-                    if (!(eps > 0.0f) || !(eps <= 2.0f) || !K1S_DIRECT(nc)) return 0.0f;
-                    int e = 0;
-                    const float m = std::frexp(eps, &e);            // eps = m 2^e, m in [0.5, 1)
-                    const float P = std::ldexp(1.0f, m == 0.5f ? e - 1 : e);
-                    const float k = 2.0f / P;
-                    if (!(k >= 1.0f) || !(k <= 1.152921504606846976e18f)) return 0.0f;
-                    for (int j = 0; j < nc; ++j) {
-                        const float t = b->te[(NE - nc) / 2 + j];
-                        if (t != 0.0f && (!std::isnormal(t) || !std::isnormal(t * k))) return 0.0f;
-                    }
-                    return k;
-                };
-                if (NC == 12) {
-                    b->sign_fscale = flag_scale(b->sign_eps, 12);
-                }
-            }
-        }
-    }
+    b->sign = sign_bounds(b->te, b->NE);         // the sign-exact slicer's error bounds for this table (fir_plan.cpp)
     b->sgn_words = (max_len + 31) / 32;
     // at most one slice per sample step of (pllinc + pllinc/16)/65536
     const uint64_t step = (uint64_t) b->pllinc + b->pllinc / 16;
@@ -628,9 +485,11 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     alloc((void **) &b->frames, sizeof(gnuais_frame) * (size_t) b->frame_cap);
     alloc((void **) &b->d_taps, sizeof(float) * b->NT);
     alloc((void **) &b->iq_prev, sizeof(int16_t) * 2 * N);
-    if (b->mfma_ok) {
+    if (b->sign.mfma_ok) {
+        MfmaTaps host;
+        fir_sign_mfma_pack(b->sign.tq, b->sign.tq_sum, &host);
         alloc((void **) &b->d_mfma, sizeof(MfmaTaps));
-        if (e == hipSuccess) e = hipMemcpy(b->d_mfma, &b->mfma_host, sizeof(MfmaTaps), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(b->d_mfma, &host, sizeof(MfmaTaps), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess)
         e = hipMemcpy(b->d_taps, b->taps.data(), sizeof(float) * b->NT, hipMemcpyHostToDevice);
@@ -693,10 +552,10 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     }
     if (const char *v = getenv("GNUAIS_FIR_VARIANT")) {
         const int fv = atoi(v);
-        if (fv == 0 || fv == 3) b->fir_variant = fv;
+        if (fv == 0 || fv == 3) b->fir.fir_variant = fv;
     }
-    if (const char *v = getenv("GNUAIS_FIR_FLAG2")) b->fir_flag2 = atoi(v) != 0;
-    if (const char *v = getenv("GNUAIS_FIR_T")) b->fir_T = std::max(64, atoi(v) / 32 * 32);
+    if (const char *v = getenv("GNUAIS_FIR_FLAG2")) b->fir.fir_flag2 = atoi(v) != 0;
+    if (const char *v = getenv("GNUAIS_FIR_T")) b->fir.fir_T = std::max(64, atoi(v) / 32 * 32);
     *out = b;
     int rc = gnuais_batch_reset(b);
     if (rc != GNUAIS_OK) {
@@ -780,7 +639,7 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
     }
     if (!strcmp(name, "fir_T")) {
         if (value < 64 || value % 32) return fail(GNUAIS_E_ARG, "fir_T must be a multiple of 32, >= 64");
-        b->fir_T = value;
+        b->fir.fir_T = value;
     } else if (!strcmp(name, "nbuf")) {             // hand-off sets in use: the calls that may be in flight
         if (value < 2 || value > gnuais_batch::NBUF) return fail(GNUAIS_E_ARG, "nbuf must be 2..8");
         if (int rc = gnuais_batch_sync(b)) return rc;
@@ -807,22 +666,21 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         }
     } else if (!strcmp(name, "fir_flag2")) {         // 0: |y| - eps and two alignbits per output (rounds 1-4)
         if (value != 0 && value != 1) return fail(GNUAIS_E_ARG, "fir_flag2: 0 or 1");
-        b->fir_flag2 = value;
+        b->fir.fir_flag2 = value;
     } else if (!strcmp(name, "fir_pk_taps")) {       // long tables: 0 = 40 central taps where the table allows them, 48 = never 40
         if (value != 0 && value != 48) return fail(GNUAIS_E_ARG, "fir_pk_taps: 0 or 48");
-        b->fir_pk_taps = value;
+        b->fir.fir_pk_taps = value;
     } else if (!strcmp(name, "fir_mfma")) {          // long tables: 1 = inner segments on the matrix pipe (fir_sign_mfma.hip), 0 = the packed kernel throughout
         if (value != 0 && value != 1) return fail(GNUAIS_E_ARG, "fir_mfma: 0 or 1");
-        b->fir_mfma = value;
+        b->fir.fir_mfma = value;
     } else if (!strcmp(name, "fir_variant")) {
         if (value != 0 && value != 3) return fail(GNUAIS_E_ARG, "fir_variant must be 0 (the exact sum for every sample) or 3 (the sign-exact slicer)");
-        b->fir_variant = value;
+        b->fir.fir_variant = value;
     } else if (!strcmp(name, "timing_stride")) {
         if (value < 1) return fail(GNUAIS_E_ARG, "timing_stride must be >= 1");
         b->timing_stride = value;
     } else if (!strcmp(name, "pipeline")) {
         b->pipeline = value != 0;
-
     } else if (!strcmp(name, "pll_variant")) {
         if (value != 0 && value != 7 && value != 8)
             return fail(GNUAIS_E_ARG, "pll_variant must be 0 (by channel count), 7 (time-parallel, pll_tp.hip) or 8 (pll_h3.hip)");
@@ -838,6 +696,7 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
     return GNUAIS_OK;
 }
 
+// everything of a FIR launch that is not a decision: buffers, taps, shape
 static void fill_fir(const gnuais_batch *b, FirLaunch &f, const int16_t *x, int len, float *dump,
                      int k)
 {
@@ -853,19 +712,11 @@ static void fill_fir(const gnuais_batch *b, FirLaunch &f, const int16_t *x, int 
     memcpy(f.te, b->te, sizeof f.te);
     f.N = b->N;
     f.L = len;
-    f.T = b->fir_T;
     f.NT = b->NT;
     f.NE = b->NE;
     f.d = b->d;
-    f.eps = b->sign_eps;
-    f.eps_pk = b->sign_eps_pk;
-    f.eps_seen = b->fir_inloop ? b->sign_eps_seen : 0.0f;
-    f.eps_ahead = b->sign_eps_ahead;
-    f.NC = b->sign_NC;
-    if (b->sign_ok)
-        for (int j = 0; j < b->sign_NC; ++j) f.ctaps[j] = b->te[(b->NE - b->sign_NC) / 2 + j];
     f.te_mem = b->d_taps + b->k0;
-    f.map = b->fir_map;
+    f.map = 1;                      // K1s workgroup mapping (fir_slice.hip): XCD-contiguous channel groups
 }
 
 static void fill_hdlc(const gnuais_batch *b, HdlcLaunch &h, int k)
@@ -900,75 +751,43 @@ static hipStream_t k3_stream(const gnuais_batch *b)
     return (b->k3_same && !b->streaming) ? b->s_k[2] : b->s_k[3];
 }
 
-// K1 + carry.  The specialised kernel updates the history and clears the next peak
-// buffer itself; the generic fallback needs the two helper launches.
+// K1 + carry: the kernel and its thresholds are plan_fir()'s choice (fir_plan.cpp).  The specialised kernels update
+// the history and clear the next peak buffer themselves; the generic fallback needs the two helper launches.
 static int run_fir(gnuais_batch *b, const int16_t *x, int len, float *dump, hipStream_t s, int k)
 {
+    const FirPlan p = plan_fir(b->sign, b->fir, FirShape{b->N, b->NT, b->NE, b->d}, len, dump != nullptr);
     FirLaunch f;
     fill_fir(b, f, x, len, dump, k);
-    if (b->fir_variant == 3 && b->sign_ok && !dump) {
-        const int q = launch_fir_sign_quantum(f.NC);        // whole loop turns of the kernel's unrolled body
-        f.T = std::min((f.T + q - 1) / q * q, 65280 / q * q);       // K1s notes open outputs as 16-bit offsets into the segment
-        // 48 central taps (the 192 kHz table): the transposed sum on register pairs (fir_sign_pk.hip)
-        if (f.NC == 48 && b->pk40_ok && b->fir_pk_taps != 48 && f.eps_seen > 0.0f) {
-            f.NC = 40;
-            f.eps_pk = b->pk40_eps_pk;
-            f.eps_seen = b->pk40_eps_seen;
-            f.eps_ahead = b->pk40_eps_ahead;
-            for (int j = 0; j < 40; ++j) f.ctaps[j] = b->te[(b->NE - 40) / 2 + j];
-        }
-        for (int q = 0; q < 4; ++q) {
-            f.eps_seen_k[q] = b->pk_seen_k[f.NC == 40][q];
-            f.eps_ahead_k[q] = b->pk_ahead_k[f.NC == 40][q];
-        }
-        if ((f.NC == 48 || f.NC == 40) && f.NC - 1 + (f.NE - f.NC) / 2 <= 96 && f.eps_seen > 0.0f) {
-            const int qp = launch_fir_sign_pk_quantum(f.NC);
-            // 48 taps: a segment's warm-up is 47 pair steps' worth of samples; longer segments (there are plenty of
-            // waves: 16384 x 192000 is 16000 segments of 3072) cut its share (round 4: 3072 against 1536, 4.29 against
-            // 4.39 ms per C5 call in steady state, profiles/r04_c5_ring_and_segments.txt)
-            // 40 taps: 1920 (FIR alone 3.34-3.40 ms against 3.43-3.49 at 3200 and 3.85 at 6400: the lists of open outputs a
-            // segment settles at its end grow with it; profiles/r05_c5_forty_central_taps.txt)
-            f.T = ((b->fir_T <= 768 ? (f.NC == 40 ? 1920 : 3072) : b->fir_T) + qp - 1) / qp * qp;
-            f.T = std::min(f.T, 65280 / qp * qp);           // the kernel notes open outputs as 16-bit offsets into the segment
-            // The matrix-pipe kernel takes everything but the call's head -- the outputs whose windows reach into the history
-            // rows --, which stays the packed kernel's: the fewest whole packed loop turns (and whole 16-byte sign stores) that
-            // cover d and dc + 64 rows (640 outputs for the 192 kHz table: one wave per 64 channels walks it alone, 0.1 ms for
-            // 256 waves on 1024 SIMDs; round 5's whole first segment of 1920 took 0.3).  (Beside the matrix-pipe launch on a side
-            // stream, between two events: 2.44 instead of 2.51 ms per C5 call, but one pipelined run in six came out with a frame
-            // more or less -- not kept; profiles/r06_c5_matrix_pipe_k32.txt.)
-            const int dc48 = f.d - (f.NE - 48) / 2;
-            const int qh = qp % launch_fir_sign_mfma_quantum() == 0 ? qp : qp * launch_fir_sign_mfma_quantum();
-            const int head = (std::max(dc48 + 64, f.d) + qh - 1) / qh * qh;
-            const bool mfma = b->fir_mfma && b->mfma_ok && b->N % 64 == 0 && f.T % launch_fir_sign_mfma_quantum() == 0 && len > head &&
-                              len >= b->NT && head <= 65280 &&
-                              (unsigned long long) (f.T + f.NE + 512) * (unsigned long long) b->N * 2ull < 0x7fffffffull;
-            if (mfma) {
-                FirLaunch h = f, m = f;
-                h.T = head;
-                h.max_segments = 1;
-                m.NC = 48;
-                m.mfma = b->d_mfma;
-                m.eps_seen = b->mfma_eps_seen_u;
-                m.eps_ahead = b->mfma_eps_abs_u;
-                HIP_TRY(launch_fir_sign_pk(h, s));
-                HIP_TRY(launch_fir_sign_mfma(m, head, s));
-            } else {
-                HIP_TRY(launch_fir_sign_pk(f, s));
-            }
-            b->hist_cur = (b->hist_cur + 1) % gnuais_batch::HB;
-            b->max_last = b->max_cur;
-            b->max_cur = (b->max_cur + 1) % gnuais_batch::HB;
-            return GNUAIS_OK;
-        }
-        if (f.NC == 12 && b->fir_flag2) f.fscale = b->sign_fscale;
-        HIP_TRY(launch_fir_sign(f, s));
-    } else if (b->NE != 32) {
-        HIP_TRY(hipMemsetAsync(b->maxval[(b->max_cur + 2) % gnuais_batch::HB], 0, sizeof(int) * (size_t) b->N, s));
+    static_cast<FirThresholds &>(f) = p.th;
+    if (b->sign.ok)
+        for (int j = 0; j < f.NC; ++j) f.ctaps[j] = b->te[(b->NE - f.NC) / 2 + j];
+    switch (p.kernel) {
+    case FirKernel::GENERIC:
+        HIP_TRY(hipMemsetAsync(f.maxval_next, 0, sizeof(int) * (size_t) b->N, s));
         HIP_TRY(launch_fir_generic(f, s));
-        HIP_TRY(launch_fir_history(x, b->hist[b->hist_cur], b->hist[(b->hist_cur + 1) % gnuais_batch::HB], b->N, len,
-                                   b->NT, s));
-    } else {
+        HIP_TRY(launch_fir_history(x, f.hist, f.hist_out, b->N, len, b->NT, s));
+        break;
+    case FirKernel::SCALAR32:
         HIP_TRY(scalar::launch_fir_slice(f, s));
+        break;
+    case FirKernel::SIGN:
+        HIP_TRY(launch_fir_sign(f, s));
+        break;
+    case FirKernel::SIGN_PACKED:
+        HIP_TRY(launch_fir_sign_pk(f, s));
+        break;
+    case FirKernel::SIGN_PACKED_MFMA: {
+        FirLaunch m = f;            // the matrix pipe behind the packed kernel's head, its thresholds in ITS units
+        f.T = p.head;
+        f.max_segments = 1;
+        m.NC = FIR_MFMA_NC;
+        m.mfma = b->d_mfma;
+        m.eps_seen = p.mfma_seen_u;
+        m.eps_ahead = p.mfma_abs_u;
+        HIP_TRY(launch_fir_sign_pk(f, s));
+        HIP_TRY(launch_fir_sign_mfma(m, p.head, s));
+        break;
+    }
     }
     b->hist_cur = (b->hist_cur + 1) % gnuais_batch::HB;
     b->max_last = b->max_cur;
@@ -1069,10 +888,6 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
     b->calls++;
     return GNUAIS_OK;
 }
-
-int gnuais_batch_sync(gnuais_batch *b);
-int gnuais_batch_reset(gnuais_batch *b);
-int gnuais_batch_discard_frames(gnuais_batch *b, void *stream);
 
 // Try the stage -> stream assignments greedily (PLL stage first, then K3, K2b, the spare; each on every
 // free candidate stream), timing a few pipelined calls of the caller's own input each, and keep
@@ -2359,18 +2174,15 @@ int gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride)
 int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
 {
     if (!b || !name || !value) return fail(GNUAIS_E_ARG, "info: argument");
-    if (!strcmp(name, "sign_exact")) *value = b->sign_ok && b->fir_variant == 3;
-    else if (!strcmp(name, "sign_eps")) {            // of the kernel the options select; FL2: the power of two it works with
-        const float fs = !b->fir_flag2 ? 0.0f : b->sign_NC == 12 ? b->sign_fscale : 0.0f;
-        *value = fs > 0.0f ? 2.0f / fs : b->sign_eps;
-    }
-    else if (!strcmp(name, "sign_flag_scale")) *value = !b->fir_flag2 ? 0.0f : b->sign_NC == 12 ? b->sign_fscale : 0.0f;
-    else if (!strcmp(name, "sign_eps_seen") || !strcmp(name, "sign_eps_ahead")) {
-        const bool pk40 = b->sign_NC == 48 && b->pk40_ok && b->fir_pk_taps != 48 && b->fir_inloop;
-        *value = name[9] == 's' ? (pk40 ? b->pk40_eps_seen : b->sign_eps_seen) : (pk40 ? b->pk40_eps_ahead : b->sign_eps_ahead);
-    }
-    else if (!strcmp(name, "sign_matrix_pipe")) *value = (b->fir_mfma && b->mfma_ok && b->N % 64 == 0 && b->sign_NC == 48 && b->fir_variant == 3) ? 1 : 0;
-    else if (!strcmp(name, "sign_central_taps")) *value = (b->sign_NC == 48 && b->pk40_ok && b->fir_pk_taps != 48 && b->fir_inloop) ? 40 : b->sign_NC;
+    // what the options select for the batch's table: the function plan_fir() starts from (fir_plan.cpp), nothing restated here
+    const SignChoice c = sign_choice(b->sign, b->fir, b->N);
+    if (!strcmp(name, "sign_exact")) *value = c.exact;
+    else if (!strcmp(name, "sign_eps")) *value = c.eps;          // of the kernel the options select; FL2: the power of two it works with
+    else if (!strcmp(name, "sign_flag_scale")) *value = c.th.fscale;
+    else if (!strcmp(name, "sign_eps_seen")) *value = c.th.eps_seen;
+    else if (!strcmp(name, "sign_eps_ahead")) *value = c.th.eps_ahead;
+    else if (!strcmp(name, "sign_matrix_pipe")) *value = c.matrix_pipe;     // eligible: a call takes the matrix pipe when its length allows
+    else if (!strcmp(name, "sign_central_taps")) *value = c.th.NC;
     else if (!strcmp(name, "first_effective_tap")) *value = b->k0;
     else if (!strcmp(name, "n_effective_taps")) *value = b->NE;
     else if (!strcmp(name, "compute_units")) *value = b->n_cu;

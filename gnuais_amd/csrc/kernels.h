@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fir_plan.h"   // what the host decides before a FIR launch: the slicer's bounds, the kernel, T's quanta (no HIP in there)
+
 namespace gnuais {
 
 // ---- K1: FIR + slicer (fir_slice.hip) -------------------------------------
-struct FirLaunch {
+struct FirLaunch : FirThresholds {   // NC, T, eps .. eps_ahead_k: the host's decision (fir_plan.h)
     const int16_t *x;      // [L][N] interleaved input
     const int16_t *hist;   // [NT][N] previous call's last NT samples, oldest first
     uint32_t *sgn;         // sign words, bit 31 = oldest sample; layout: sgn_index() below
@@ -17,18 +19,10 @@ struct FirLaunch {
     int *maxval_next;      // [N] the other peak buffer: cleared by the specialised kernel
     const float *d_taps;   // device copy of all NT taps (generic kernel)
     float te[64];          // trimmed taps (specialised kernel)
-    int N, L, T;           // T: outputs per wave, multiple of 32
+    int N, L;
     int NT, NE, d;         // out[n] = sum_j te[j] * x[n - d + j], j < NE
-    float eps;             // sign-exact slicer: |central sum| > eps certifies the sign
-    float fscale = 0;      // K1s direct form: > 0 = a power of two the central taps are scaled by so that the certified distance
-                           //   is |y'| >= 2.0 and one v_alignbit_b32 gathers sign and exponent bit (fir_sign_kernel FL2); eps is then unused
-    float eps_pk = 0;      // fir_sign_pk.hip, 12 taps: the bound for the transposed fused sum (the direct form's is eps)
-    float eps_seen = 0, eps_ahead = 0;     // 48-tap K1s with the running maximum (eps_seen > 0): eps = eps_seen * M / 32768 + eps_ahead
-    float eps_seen_k[4] = {}, eps_ahead_k[4] = {};   // fir_sign_pk.hip, 40 / 48 taps: the same for an output that completes >= 6, 4, 2, 0 rows
-                                                     //   before the end of its 16-row group (those rows are under the maximum M as well)
-    int NC;                //   central taps used (12 or 48)
-    float ctaps[48];       //   te[(NE-NC)/2 .. +NC)
-    const float *te_mem;   //   the NE effective taps in device memory (exact re-evaluation)
+    float ctaps[48];       // the NC central taps, te[(NE-NC)/2 .. +NC)
+    const float *te_mem;   // the NE effective taps in device memory (exact re-evaluation)
     int map;               // K1s workgroup -> (channel group, segment) mapping, see fir_sign_kernel
     int max_segments = 0;  // fir_sign_pk.hip: > 0 = only the call's first segments (the rest is fir_sign_mfma.hip's)
     const struct MfmaTaps *mfma = nullptr;   // fir_sign_mfma.hip: the device copy of its integer taps; eps_seen / eps_ahead are then in ITS units
@@ -39,8 +33,7 @@ hipError_t launch_fir_sign(const FirLaunch &a, hipStream_t stream);
 int launch_fir_sign_pk_quantum(int NC);
 // K1s, 48 central taps as an exact integer Toeplitz product on the matrix pipe (fir_sign_mfma.hip): outputs first .. of a call
 struct alignas(16) MfmaTaps { int a[3][3][64][4]; int k0; };   // [block of 32 window rows][tap digit 0..2][lane][16 bytes]: the A operands; 128 * sum of the integer taps
-bool fir_sign_mfma_taps(const float *tc48, MfmaTaps *out, double *scale, double *bound_q);
-int launch_fir_sign_mfma_quantum();
+void fir_sign_mfma_pack(const int *tq48, long tq_sum, MfmaTaps *out);     // SignBounds::tq, ::tq_sum -> the A operands
 hipError_t launch_fir_sign_mfma(const FirLaunch &a, int first, hipStream_t stream);
 hipError_t launch_fir_sign_pk(const FirLaunch &a, hipStream_t stream);
 hipError_t launch_fir_generic(const FirLaunch &a, hipStream_t stream);
@@ -167,10 +160,6 @@ struct ChanLaunch {
 };
 int channeliser_fast_na(int K, int T, int D);    // 0: no fast form for this shape
 hipError_t launch_channeliser(const ChanLaunch &a, uint32_t *hist_out, hipStream_t stream);
-
-// K1s evaluates the NC = 12 central taps in direct form with symmetric pre-adds (fir_slice.hip); the
-// host's error bound for y_c follows the same order of operations (gnuais_capi.hip)
-constexpr bool K1S_DIRECT(int nc) { return nc <= 12; }
 
 // ---- f1 on the device (nmea_device.hip) ---------------------------------------
 size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);

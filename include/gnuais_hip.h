@@ -276,7 +276,9 @@ int  gnuais_batch_last_bits(gnuais_batch *b, uint8_t *h_bits, int stride, int32_
  * h_out HOST uint8 [n_channels][stride], stride >= len of that call */
 int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
 /* facts about a batch, by name: "sign_exact" (1 if the receive path runs the sign-exact slicer),
- * "sign_eps" (its certification threshold), "sign_central_taps", "first_effective_tap",
+ * "sign_eps" (its certification threshold), "sign_central_taps", "sign_matrix_pipe" (1 if the batch is ELIGIBLE for
+ * the matrix-pipe FIR: table, options and channel count allow it; a call takes it when its length does too),
+ * "first_effective_tap",
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);

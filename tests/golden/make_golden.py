@@ -105,6 +105,47 @@ def make_vessels():
           {int(b): int((tab["set"] == b).sum()) for b in np.unique(tab["set"])})
 
 
+def make_fir_plan(harness):
+    """fir_plan.npz: what the host derives from a tap table (the sign-exact slicer's bounds) and decides per call (kernel,
+    segment length, thresholds), for tests/test_fir_plan_cpu.py.  FROZEN FROM THE COMMIT BEFORE gnuais_amd/csrc/fir_plan.cpp
+    EXISTED, never from fir_plan.cpp itself: `harness` is a program that speaks the protocol of tests/fir_plan_cases.py and
+    holds that commit's code verbatim -- gnuais_batch_create's bound block, fir_sign_mfma_taps, fill_fir, run_fir (launchers
+    stubbed to record their FirLaunch) and gnuais_batch_info's sign_* lines behind a stub struct, built with
+    g++ -O1 -std=c++17 -ffp-contract=off.  Re-running this needs such a harness again; the values do not change otherwise."""
+    import subprocess
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "scripts"))
+    import fir_plan_cases as fc
+    import fuzz_parity
+    tables = [("48k", params.taps_48k()), ("192k", params.taps_192k())]
+    for seed in fc.RANDOM_SEEDS:
+        t, _, name = fuzz_parity.table(np.random.default_rng(seed))
+        assert name.startswith("rand"), (seed, name)
+        tables.append((f"s{seed}", t))
+    with tempfile.NamedTemporaryFile("w", suffix=".txt") as f:
+        f.write(fc.driver_input(tables, fc.PLAN_TABLES))
+        f.flush()
+        text = subprocess.run([harness, f.name], capture_output=True, text=True, check=True).stdout
+    bounds, plans = fc.parse(text)
+    out = {"names": np.array([n for n, _ in tables]),
+           "taps": np.concatenate([np.asarray(t, dtype=np.float32).view(np.uint32) for _, t in tables]),
+           "taps_len": np.array([len(t) for _, t in tables])}
+    for k in bounds["48k"]:
+        out["b_" + k] = np.stack([bounds[n][k] for n, _ in tables])
+    out["plan_rows"] = np.array([len(plans[n]["kernel"]) for n in fc.PLAN_TABLES])
+    for k in plans["48k"]:
+        out["p_" + k] = np.concatenate([plans[n][k] for n in fc.PLAN_TABLES])
+    path = os.path.join(HERE, "fir_plan.npz")
+    np.savez_compressed(path, **out)
+    census = {}
+    for n, _ in tables[2:]:
+        b = bounds[n]
+        key = (f"NC {b['NC'][0]} forty {b['ok40'][0]} matrix pipe {b['mfma_ok'][0]} FL2 {int(b['fscale'][0] != 0)}"
+               if b["ok"][0] else f"not admitted (forty {b['ok40'][0]})")
+        census[key] = census.get(key, 0) + 1
+    print("fir_plan.npz", os.path.getsize(path), len(tables), "tables,", int(out["plan_rows"].sum()), "plans;", census)
+
+
 def cases_frame_dtype():
     from oracle_lib import FRAME_DTYPE
     return FRAME_DTYPE
@@ -115,6 +156,8 @@ def main():
         return make_vessels()
     if sys.argv[1:] == ["range"]:
         return make_range()
+    if sys.argv[1:2] == ["fir_plan"]:       # + the path of the harness (see make_fir_plan)
+        return make_fir_plan(sys.argv[2])
     if sys.argv[1:] == ["nmea"]:
         make_nmea()
         return
