@@ -1,0 +1,282 @@
+// batch.h -- what the three host units of the C ABI share (gnuais_capi.hip, capi_ingest.hip, capi_delivery.hip): the
+// owners of a batch's device resources, struct gnuais_batch, the error helpers and the few functions that more than
+// one unit calls.  Internal to csrc; not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/gnuais_hip.h"
+#include "kernels.h"
+
+using namespace gnuais;
+
+namespace gnuais {
+// Sets gnuais_last_error() to `what` (and HIP's text for e) and returns code
+int fail(int code, const char *what, hipError_t e = hipSuccess);
+}
+
+#define HIP_TRY(expr)                                                          \
+    do {                                                                       \
+        hipError_t e_ = (expr);                                                \
+        if (e_ != hipSuccess) return fail(GNUAIS_E_HIP, #expr, e_);            \
+    } while (0)
+
+namespace gnuais {
+// The owners of what a batch holds.  Each releases its resource exactly once -- when it is told to, when it is given
+// another, or when the batch is deleted (gnuais_batch_destroy has made the batch's device current by then) -- so a
+// half-built batch and a batch that used every feature end the same way, without a list.  Move-only.  Nothing more:
+// no sharing, no pooling; the aliases in gnuais_batch (s_k, s_post, s_copy, e_in_hook) stay plain handles.
+
+// Device memory (PINNED: page-locked host memory) and its size in bytes
+template <class T, bool PINNED = false>
+struct Buf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~Buf() { (void) release(); }
+    operator T *() const { return p; }
+    hipError_t release()
+    {
+        const hipError_t e = !p ? hipSuccess : PINNED ? hipHostFree(p) : hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        return e;
+    }
+    // n bytes anew (zeroed: device memory cleared); empty with size 0 on failure
+    hipError_t alloc(size_t n, bool zeroed = false)
+    {
+        hipError_t e = release();
+        if (e == hipSuccess) e = PINNED ? hipHostMalloc((void **) &p, n, hipHostMallocDefault) : hipMalloc((void **) &p, n);
+        if (e != hipSuccess) return p = nullptr, e;
+        bytes = n;
+        if (zeroed) e = PINNED ? (memset(p, 0, n), hipSuccess) : hipMemset(p, 0, n);
+        if (e != hipSuccess) (void) release();
+        return e;
+    }
+    // allocated on first use: nothing happens when it exists (also what an attempt that failed further on left behind)
+    hipError_t ensure(size_t n, bool zeroed = false) { return p ? hipSuccess : alloc(n, zeroed); }
+    // scratch that grows on demand: when `need` exceeds what it holds, it is freed and allocated anew with `need + slack`
+    hipError_t grow(size_t need, size_t slack = 0) { return bytes >= need ? hipSuccess : alloc(need + slack); }
+};
+template <class T> using Pinned = Buf<T, true>;
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void) hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    // created only if it does not exist yet
+    hipError_t ensure(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+};
+
+// a non-blocking stream
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) (void) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    // created only if it does not exist yet (priority 0: the default one)
+    hipError_t ensure(int priority = 0) { return s ? hipSuccess : hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority); }
+};
+
+} // namespace gnuais
+
+// The stages a call may pass through, in launch order: the channeliser, the discriminator, the carrier-error stage
+// (gnuais_batch_afc, when it is on), the chain (K1 .. K3)
+enum Stage { CHAN, DISC, AFC, CHAIN, N_STAGES };
+
+// The input forms (include/gnuais_hip.h): audio [len][N], I/Q [len][N][2], wideband [len][N/K][2]
+enum FormId { AUDIO, IQ, WIDE };
+
+struct gnuais_batch {
+    int device = 0;
+    int N = 0, NT = 0, NE = 0, d = 0;
+    uint32_t pllinc = 0;
+    int max_len = 0, frame_cap = 0;
+    int sgn_words = 0, bits_words = 0;
+    std::vector<float> taps;
+    float te[128] = {0};
+    // device state
+    // The FIR's carry (the last NT input rows) and the per-call peak buffers rotate over HB buffers: call i reads
+    // hist[i % HB], writes hist[(i + 1) % HB], gathers its peaks in maxval[i % HB] and clears maxval[(i + 2) % HB].
+    // (Two would do for FIR launches that run one after the other; four keep the writer of a buffer two calls away
+    // from its readers.)
+    static constexpr int HB = 4;
+    Buf<int16_t> hist[HB];
+    int hist_cur = 0;
+    // every hand-off buffer exists NBUF times; `nbuf` of them are in use (index = call % nbuf), so K1 can run up
+    // to nbuf-1 calls ahead of the sequential stages
+    static constexpr int NBUF = 8;
+    // Depth in use.  The host waits for K3 of call i-nbuf before it launches the FIR of call i, so the pipeline is a
+    // closed loop: period >= latency of a call / nbuf.  Round 4, C3, same box (profiles/r04_nbuf_3_vs_4.txt): depth 3
+    // and 4 give the same steady state (0.518 ms: at 3 the loop's bound and the PLL stage's duration meet), 5-8 no
+    // better (0.53-0.55), 2 starves (0.70); a short timed region ends sooner with fewer calls in flight to drain
+    // (20 steps: 0.574 against 0.583), so 3.
+    int nbuf = 3;
+    int sets_alloc = 0;                         // hand-off sets that exist (>= nbuf)
+    Buf<uint32_t> sgn[NBUF];                    // K1 -> K2
+    Buf<uint32_t> pll, lastbit, prev;           // receiver.h:38-44, carried by K2
+    int n_cu = 256;
+    Buf<uint32_t> segbits[NBUF];                // K2 -> K2b
+    Buf<uint32_t> segcnt[NBUF];
+    int n_seg = 0, seg_words = 0;
+    // stage pipeline: K1 on the caller's stream and one internal stream per later
+    // kernel, so that the short-on-parallelism stages of call i overlap the FIR of
+    // call i+1 (and each other).
+    hipStream_t s_k[4] = {nullptr, nullptr, nullptr, nullptr};   // K2, (spare), K2b, K3 (entries of pool[])
+    hipStream_t s_k_default[4] = {nullptr, nullptr, nullptr, nullptr};
+    static constexpr int POOL = 12;
+    Stream pool[POOL];                          // candidates for gnuais_batch_autotune(): [0..3] the default
+                                                // assignment, [0..7] high priority, [8..11] default priority
+    Event e_done[5][NBUF];                      // e_done[s][k]: stage s of the call using set k is done
+                                                // (0 K1, 1 K2, 3 K2b, 4 K3)
+    unsigned long long calls = 0, hdlc_calls = 0;   // run calls / K3 launches since the last drain
+    bool pipeline = true;
+    Buf<uint32_t> ctl, cand;
+    Buf<uint32_t> cand_first[NBUF], cand_count[NBUF];   // K2b -> K3
+    int cand_K = 64;
+    Buf<int32_t> counters;
+    Buf<int> maxval[HB];                   // rotate with the history buffers
+    int max_cur = 0, max_last = 0;
+    Buf<float> d_taps;
+    Buf<MfmaTaps> d_mfma;           // fir_sign_mfma.hip: the 48 central taps as integer Toeplitz operands (long tables)
+    // f1 on the device (gnuais_batch_drain_nmea): allocated on first use
+    Buf<uint8_t> d_seq[2];
+    Buf<char> d_text;
+    Buf<void> nmea_scratch;
+    Buf<char> d_msg;                // gnuais_batch_drain_messages: lines, lengths, offsets, packed text
+    Buf<uint32_t> d_word;           // a few device words for counts read back by the drain-type calls
+    // the vessel table carried on the device (gnuais_batch_vessel_table_*): one allocation, per-frame slot scratch
+    Buf<void> vt;
+    Buf<uint32_t> vt_fslot;
+    uint32_t vt_slots = 0;
+    int vt_capacity = 0;
+    // The frame ring K3 appends to and its four counters: ring[ring_cur] / ring_count[ring_cur].  Ring 0 exists from
+    // create on and is the only one a batch that does not stream ever uses; gnuais_batch_stream_nmea makes the
+    // other NRING - 1 on its first call.  A ring is filled by K3; its formatter and the copy of its
+    // text into pinned memory are queued behind that K3 at once, with every size taken on the device; the
+    // text is handed out NRING - 1 calls later, which is the only thing the host ever waits for.  A call
+    // is about 2.7 ms from its FIR to its text on the host (four chain stages, formatter, PCIe copy), so
+    // about six of them have to be in flight for one to finish every 0.55 ms.
+    static constexpr int NRING = 8;
+    Buf<gnuais_frame> ring[NRING];
+    Buf<uint32_t> ring_count[NRING];
+    Buf<uint2> ring_chunks[NRING];              // K3's chunk table per ring (kernels.h: HdlcLaunch::chunks)
+    int ring_runs[NRING] = {};                  // K3 launches into the ring since it became current
+    int n_chunks = 0;
+    // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
+    // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
+    // (rings_reset)
+    int ring_cur = 0;
+    bool streaming = false;
+    hipStream_t s_post = nullptr, s_copy = nullptr;     // s_copy: s_copy_own, or the pool stream autotune_delivery chose
+    Stream s_copy_own;                          // the one created for the copy
+    Event e_fill[NRING], e_fmt[NRING], e_txt[NRING];
+    Buf<char> sd_text[NRING];                   // device text per slot
+    Pinned<char> sh_text[NRING];                // pinned host text per slot
+    Pinned<uint32_t> sh_info;                   // pinned: [NRING][8]: format's 4 words, the ring's 4 counters
+    int s_stage[NRING] = {};                    // 1: the slot's formatter is queued, its text not handed out yet
+    size_t sh_text_want = 0;                    // pinned text buffers grow to this (learnt from the traffic)
+    Buf<uint32_t> sd_info;                      // device: [NRING][8], what sh_info receives with the text
+    bool copy_on_k3 = false;                    // experiment: the copy kernel on K3's stream as well
+    int copy_wgs = 24;                          // waves of the device -> pinned copy (measured: 16 0.65, 24 0.62, 32 0.64, 64 0.79 ms per C3 step)
+    Buf<uint8_t> sd_seq[2];                     // per-channel sequence digit, carried on the device
+    int sd_seq_cur = 0;
+    unsigned long long stream_calls = 0;
+    Buf<int16_t> stage_x;
+    Buf<float> stage_f;             // gnuais_batch_filter_host: the floats on their way out
+    // gnuais_batch_run_host_async: two pinned host buffers + two device buffers, one internal stream
+    Pinned<int16_t> pin[2];
+    Buf<int16_t> dev_in[2];
+    size_t pin_bytes = 0;                       // the size of all four once they exist
+    Stream s_io;
+    Event e_in[2];                              // the FIR of the call that used staging pair q is done
+    hipEvent_t e_in_hook = nullptr;             // run_host_async -> run: record this right behind K1
+    unsigned long long host_calls = 0;
+    // options
+    FirOptions fir;                             // the fir_* options the choice of the FIR kernel depends on (fir_plan.h)
+    SignBounds sign;                            // the sign-exact slicer's error bounds for the table (fir_plan.h)
+    int stage_mask = 0x1f;                      // experiments only: bit s = launch stage s
+    int k0 = 0;                     // first effective tap
+    int pll_variant = 0;            // 0: by channel count; 7 / 8 (kernels.h: PllLaunch::variant)
+    int hdlc_lpw = 0;               // channels per wave in K2b; 0 = the variant's own default (16 event-driven, 64 bit-serial)
+    int hdlc_variant = 1;           // 1: the event-driven deframer (hdlc_events.hip), 0: window by window (hdlc_crc.hip)
+    bool timing = false;
+    int timing_stride = 1;          // time every n-th call only: ten event records a call are not free
+    // timing: a ring of per-call event sets so that kernel durations can be read back
+    // for every call of a timed region, not just the last one
+    static constexpr int TIMING_RING = 64;
+    Event evr[TIMING_RING][10];            // 0,1 K1 | 2,6 K2 | 5,7 K2b | 9,4 K3
+    unsigned long long timed_calls = 0;
+    int last_k = 0;
+    bool timed_last = false;
+    // The drain rule: each stage keeps the stream of its last launch here (last[CHAIN].s is also the stream that
+    // gnuais_batch_sync drains).  Before a call launches anything on stream s, it drains the recorded stream of every
+    // stage it passes through, when that stream is not s (drain()).  This covers two hazards.  A stage's carry goes
+    // from launch to launch in stream order: the channeliser's history, the discriminator's previous pair, the chain's
+    // FIR history and peaks.  And a stage in front of the chain overwrites an intermediate buffer whose reader is the
+    // next stage of the previous call, on that call's stream: ch_iq is read by the discriminator, iq_audio by K1 or the
+    // AFC stage, afc_audio by K1.  The AFC stage's delay line, block sums and estimates are carries of the first kind.
+    struct { hipStream_t s = nullptr; bool used = false; } last[N_STAGES];
+    int last_len = 0;
+    // K3 on the deframer's stream: at ring lag 1 the two never overlap (deframer(i) -> K3(i) -> deframer(i+1)), so the two
+    // cross-stream event waits per call in the loop that sets the period become stream order: 20-step 0.550 -> 0.544,
+    // steady 0.527 -> 0.522 (three A/B pairs, profiles/r04_k3_on_the_deframers_stream.txt).  0 = a stream of its own.
+    int k3_same = 1;
+    // complex baseband in (gnuais_batch_run_iq / _discriminate, iq_disc.hip): the discriminator's carry -- the last (I, Q)
+    // pair an I/Q call saw, per channel -- and the audio it writes for the chain, [max_len][N] (allocated on first use).
+    Buf<int16_t> iq_prev;                       // [N][2]
+    Buf<int16_t> iq_audio;
+    // wideband in (gnuais_batch_channeliser / _run_wideband, channeliser.hip): the configuration, the device tables, the
+    // carry (the last T-1 wide samples of each stream, double-buffered: a launch reads one and writes the other), the
+    // wide-sample count n and the narrowband I/Q it writes for the discriminator, [max_len][N][2] (allocated on first use).
+    int ch_K = 0, ch_D = 0, ch_T = 0, ch_R = 0, ch_NA = 0;  // ch_K == 0: not configured
+    int ch_per[CHAN_MAX_K] = {}, ch_off[CHAN_MAX_K] = {};
+    Buf<uint32_t> ch_mix, ch_poly, ch_hist[2];
+    Buf<int16_t> ch_taps;
+    int ch_cur = 0;
+    unsigned long long ch_n = 0;
+    Buf<int16_t> ch_iq;
+    // the carrier-error stage (gnuais_batch_afc, afc.hip; 0 = off): the window W, the rows n it has taken, the ring of
+    // block sums [afc_nb][N][2], the delay line [W/2][N], the estimates of the last call [max_len/64 + 2][N] with the row
+    // that serves the last output row (-1: none yet), and the corrected audio it writes for the chain, [max_len][N]
+    // (allocated on first use)
+    int afc_W = 0, afc_nb = 0, afc_est_row = -1;
+    unsigned long long afc_n = 0;
+    Buf<int64_t> afc_blk;
+    Buf<int16_t> afc_delay, afc_est, afc_audio;
+};
+
+// Per chain row, `rows` input rows of `cols` columns of `bytes` bytes each; `stages`: bit s = the call passes stage s
+struct Form {
+    int bytes, cols, rows;
+    unsigned stages;
+    size_t bytes_of(int in_rows) const { return (size_t) bytes * (size_t) cols * (size_t) in_rows; }
+};
+
+namespace gnuais {
+int set_device(const gnuais_batch *b);
+// The drain rule (gnuais_batch::last): drains the recorded stream of each stage in `stages` that is not s
+int drain(gnuais_batch *b, unsigned stages, hipStream_t s);
+// the stream K3 runs on, and the stream behind the last K3 (when the chain runs on the caller's stream: that one)
+hipStream_t k3_stream(const gnuais_batch *b);
+hipStream_t behind_k3(const gnuais_batch *b);
+double now_ms();
+// capi_ingest.hip: the carries of the stages in front of the chain, for gnuais_batch_reset
+int chan_zero_state(gnuais_batch *b);
+int afc_zero_state(gnuais_batch *b);
+}

@@ -1,0 +1,501 @@
+// capi_delivery.hip -- the C ABI's output side (include/gnuais_hip.h): what becomes of the frames K3 has appended to the
+// batch's ring -- the drains, the messages and vessel folds, the vessel table carried on the device, the streamed
+// delivery (gnuais_batch_stream_nmea) and the placement of its copy stream.  Host code only.
+#include "batch.h"
+
+extern "C" {
+
+// device buffers of the post-stage (sorted records / text, rocPRIM scratch): allocated on first use
+static int ensure_post_buffers(gnuais_batch *b, uint32_t have)
+{
+    const size_t need_text = (size_t) have * 164, need_scratch = nmea_scratch_bytes((int) have);
+    HIP_TRY(b->d_text.grow(need_text));
+    HIP_TRY(b->nmea_scratch.grow(need_scratch));
+    return GNUAIS_OK;
+}
+
+// What is queued in the ring of a batch that does not stream, once the chain is idle: `have` frames; `overflow`: more
+// came than the ring holds; `watchdog`: a PLL-stage wave timed out waiting for its partner
+struct Pending {
+    uint32_t have;
+    bool overflow, watchdog;
+};
+
+static int read_pending(gnuais_batch *b, Pending &p)
+{
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(cnt, b->ring_count[0], sizeof cnt, hipMemcpyDeviceToHost));
+    p.have = std::min<uint32_t>(cnt[0], (uint32_t) b->frame_cap);
+    p.overflow = cnt[1] || cnt[0] > (uint32_t) b->frame_cap;
+    p.watchdog = cnt[3] != 0;
+    return GNUAIS_OK;
+}
+
+// the two errors a span of frames reports late, with what it delivered, in the name of the entry `who`
+static int late_error(const char *who, bool watchdog, bool overflow, const char *watchdog_tail = "")
+{
+    char msg[200];
+    if (watchdog) {
+        snprintf(msg, sizeof msg, "%s: the PLL stage's watchdog fired (device hung or badly oversubscribed)%s", who, watchdog_tail);
+        return fail(GNUAIS_E_HIP, msg);
+    }
+    if (!overflow) return GNUAIS_OK;
+    snprintf(msg, sizeof msg, "%s: frame ring overflowed, frames were dropped", who);
+    return fail(GNUAIS_E_OVERFLOW, msg);
+}
+
+// the end of a drain that consumes: the ring is empty again, then the late errors
+static int finish_drain(gnuais_batch *b, const Pending &p, const char *who, const char *watchdog_tail = "")
+{
+    HIP_TRY(hipMemset(b->ring_count[0], 0, sizeof(uint32_t) * 4));
+    b->hdlc_calls = 0;
+    return late_error(who, p.watchdog, p.overflow, watchdog_tail);
+}
+
+// the caller's sequence digits into d_seq[0] and, for the formatter to advance, d_seq[1] (allocated on first use)
+static int upload_seq(gnuais_batch *b, const uint8_t *seqnr)
+{
+    const size_t N = (size_t) b->N;
+    for (auto &p : b->d_seq) HIP_TRY(p.ensure(N));
+    HIP_TRY(hipMemcpy(b->d_seq[0], seqnr, N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_seq[1], b->d_seq[0], N, hipMemcpyDeviceToDevice));
+    return GNUAIS_OK;
+}
+
+// drain: records and / or sentences of everything queued, consumed once
+static int drain_impl(gnuais_batch *b, gnuais_frame *h_frames, int max_frames, int *n_frames,
+                      uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len, int *n_sentences)
+{
+    // a streaming batch spreads its frames over NRING rings that gnuais_batch_stream_nmea() consumes: ring 0 alone
+    // would be a partial view, and clearing its counters would lose frames and error flags
+    if (b->streaming) return fail(GNUAIS_E_STATE, "drain: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    Pending pend;
+    if (int rc = read_pending(b, pend)) return rc;
+    const uint32_t have = pend.have;
+    if (h_frames && (uint32_t) max_frames < have) return fail(GNUAIS_E_ARG, "drain: frame buffer too small");
+    if (have) {
+        const size_t N = (size_t) b->N;
+        if (int rc = ensure_post_buffers(b, have)) return rc;
+        if (seqnr) {
+            // sentences first (the formatter sorts for itself and leaves the ring untouched)
+            if (int rc = upload_seq(b, seqnr)) return rc;
+            uint32_t info[3] = {0, 0, 0};
+            HIP_TRY(nmea_format(b->ring[0], (int) have, b->N, b->d_seq[0], b->d_seq[1], b->d_text, b->d_text.bytes,
+                                b->nmea_scratch, b->nmea_scratch.bytes, info, nullptr));
+            if (info[2]) return fail(GNUAIS_E_HIP, "drain: a frame record names a channel outside the batch");
+            if ((size_t) info[0] > out_cap) {
+                *out_len = info[0];
+                return fail(GNUAIS_E_ARG, "drain: text buffer too small");
+            }
+            if (info[0]) HIP_TRY(hipMemcpy(out, b->d_text, info[0], hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(seqnr, b->d_seq[1], N, hipMemcpyDeviceToHost));
+            *out_len = info[0];
+            if (n_sentences) *n_sentences = (int) info[1];
+        }
+        if (h_frames) {
+            // K3 appends the frames in pieces, in whatever order its blocks finish; the reference's
+            // print order (channel, then time) is restored on the device -- radix sort of
+            // (channel, end_bit), gather -- and the records cross PCIe once, straight into h_frames
+            gnuais_frame *sorted = reinterpret_cast<gnuais_frame *>(b->d_text.p);
+            HIP_TRY(frames_sort(b->ring[0], (int) have, sorted, b->nmea_scratch, b->nmea_scratch.bytes, nullptr));
+            HIP_TRY(hipMemcpy(h_frames, sorted, sizeof(gnuais_frame) * have, hipMemcpyDeviceToHost));
+        }
+        if (n_frames) *n_frames = (int) have;
+    }
+    return finish_drain(b, pend, "drain", "; results are incomplete");
+}
+
+// Row f1 complete on the device: sentences AND stdout lines of everything queued, consumed once
+int gnuais_batch_drain_messages(gnuais_batch *b, uint8_t *seqnr, const char *chanid, char *nmea, size_t nmea_cap,
+                                size_t *nmea_len, int *n_sentences, char *text, size_t text_cap, size_t *text_len,
+                                int *n_lines, int *n_frames)
+{
+    if (!b || !seqnr || !nmea_len || !text_len || (nmea_cap && !nmea) || (text_cap && !text))
+        return fail(GNUAIS_E_ARG, "drain_messages: argument");
+    if (b->streaming) return fail(GNUAIS_E_ARG, "drain_messages: the batch is streaming (gnuais_batch_stream_nmea)");
+    *nmea_len = *text_len = 0;
+    if (n_sentences) *n_sentences = 0;
+    if (n_lines) *n_lines = 0;
+    if (n_frames) *n_frames = 0;
+    Pending pend;
+    if (int rc = read_pending(b, pend)) return rc;
+    const uint32_t have = pend.have;
+    if (have) {
+        const size_t N = (size_t) b->N, line = messages_line_bytes();
+        if (nmea_cap < (size_t) have * 164 || text_cap < (size_t) have * line)
+            return fail(GNUAIS_E_ARG, "drain_messages: buffers too small (164 / 512 bytes per pending frame always suffice)");
+        if (int rc = ensure_post_buffers(b, have)) return rc;
+        // lines at a fixed stride, their lengths and offsets, the packed text, two info words, the channel names
+        const size_t need = (size_t) have * line * 2 + (size_t) have * 8 + 256 + N + 256;
+        HIP_TRY(b->d_msg.grow(need, need / 4));
+        char *lines = b->d_msg, *packed = lines + (size_t) have * line;
+        uint32_t *len = reinterpret_cast<uint32_t *>(packed + (size_t) have * line), *off = len + have;
+        uint32_t *info2 = off + have;
+        char *d_chanid = reinterpret_cast<char *>(info2 + 64);
+        if (chanid) HIP_TRY(hipMemcpy(d_chanid, chanid, N, hipMemcpyHostToDevice));
+        if (int rc = upload_seq(b, seqnr)) return rc;
+        uint32_t raw[4] = {0, 0, 0, 0}, inf[2] = {0, 0};
+        HIP_TRY(nmea_format_enqueue(b->ring[0], (int) have, (int) have, b->N, b->d_seq[0], b->d_seq[1], b->d_text,
+                                    b->d_text.bytes, b->nmea_scratch, b->nmea_scratch.bytes, raw, nullptr, 0, 0,
+                                    nullptr, nullptr));
+        HIP_TRY(messages_format_enqueue(b->ring[0], (int) have, b->N, b->d_seq[0], chanid ? d_chanid : nullptr,
+                                        b->nmea_scratch, b->nmea_scratch.bytes, lines, len, off, packed,
+                                        (size_t) have * line, info2, nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(inf, info2, 8, hipMemcpyDeviceToHost));
+        if (raw[3]) return fail(GNUAIS_E_HIP, "drain_messages: a frame record names a channel outside the batch");
+        const size_t nl = (size_t) raw[0] + raw[1];
+        if (nl) HIP_TRY(hipMemcpy(nmea, b->d_text, nl, hipMemcpyDeviceToHost));
+        if (inf[0]) HIP_TRY(hipMemcpy(text, packed, inf[0], hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(seqnr, b->d_seq[1], N, hipMemcpyDeviceToHost));
+        *nmea_len = nl;
+        *text_len = inf[0];
+        if (n_sentences) *n_sentences = (int) raw[2];
+        if (n_lines) *n_lines = (int) inf[1];
+        if (n_frames) *n_frames = (int) have;
+    }
+    return finish_drain(b, pend, "drain_messages");
+}
+
+// Row f3 on the device: what the queued frames do to the reference's position cache, folded per vessel.
+// Does not consume the frames (call it before a drain).
+int gnuais_batch_fold_vessels(gnuais_batch *b, gnuais_vessel *vessels, int cap, int *n_vessels)
+{
+    if (!b || !n_vessels || cap < 0 || (cap > 0 && !vessels)) return fail(GNUAIS_E_ARG, "fold_vessels: argument");
+    if (b->streaming) return fail(GNUAIS_E_ARG, "fold_vessels: the batch is streaming (gnuais_batch_stream_nmea)");
+    *n_vessels = 0;
+    Pending pend;
+    if (int rc = read_pending(b, pend)) return rc;
+    const uint32_t have = pend.have;
+    if (!have) return GNUAIS_OK;
+    if (int rc = ensure_post_buffers(b, have)) return rc;
+    // at most one vessel per frame; the table shares the text buffer (164 bytes per frame >= 120)
+    gnuais_vessel *d_tab = reinterpret_cast<gnuais_vessel *>(b->d_text.p);
+    const int d_cap = (int) std::min<size_t>(b->d_text.bytes / sizeof(gnuais_vessel), (size_t) have);
+    HIP_TRY(b->d_word.ensure(16));
+    HIP_TRY(vessels_fold_enqueue(b->ring[0], (int) have, b->nmea_scratch, b->nmea_scratch.bytes, d_tab, d_cap,
+                                 b->d_word, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t nv = 0;
+    HIP_TRY(hipMemcpy(&nv, b->d_word, 4, hipMemcpyDeviceToHost));
+    *n_vessels = (int) nv;
+    if ((int) nv > cap) return fail(GNUAIS_E_OVERFLOW, "fold_vessels: table too small (*n_vessels entries needed)");
+    if (nv) HIP_TRY(hipMemcpy(vessels, d_tab, sizeof(gnuais_vessel) * nv, hipMemcpyDeviceToHost));
+    return GNUAIS_OK;
+}
+
+// ---- row f3, carried: the position cache kept on the device from batch to batch ------------------------------------
+int gnuais_batch_vessel_table_enable(gnuais_batch *b, int capacity)
+{
+    if (!b || capacity < 1 || capacity > (1 << 24)) return fail(GNUAIS_E_ARG, "vessel_table_enable: capacity 1 .. 2^24");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    if (b->s_post) HIP_TRY(hipStreamSynchronize(b->s_post));
+    uint32_t slots = 1024;
+    while (slots < 2u * (uint32_t) capacity) slots <<= 1;        // at most half full: short probe sequences
+    b->vt_slots = 0;
+    HIP_TRY(b->vt.alloc(vessel_table_bytes(slots), true));
+    HIP_TRY(b->vt_fslot.ensure(sizeof(uint32_t) * (size_t) b->frame_cap));
+    b->vt_slots = slots;
+    b->vt_capacity = capacity;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_vessel_table_clear(gnuais_batch *b)
+{
+    if (!b || !b->vt) return fail(GNUAIS_E_STATE, "vessel_table_clear: no table (gnuais_batch_vessel_table_enable)");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    if (b->s_post) HIP_TRY(hipStreamSynchronize(b->s_post));
+    HIP_TRY(hipMemset(b->vt, 0, vessel_table_bytes(b->vt_slots)));
+    return GNUAIS_OK;
+}
+
+// drain-type use: the queued frames into the table (they stay queued)
+int gnuais_batch_vessel_table_update(gnuais_batch *b)
+{
+    if (!b || !b->vt) return fail(GNUAIS_E_STATE, "vessel_table_update: no table (gnuais_batch_vessel_table_enable)");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "vessel_table_update: a streaming batch updates its table by itself");
+    if (int rc = gnuais_batch_sync(b)) return rc;             // a drain-type call: waits for the chain like the drains do
+    HIP_TRY(vessel_table_update_enqueue(b->ring[0], b->ring_count[0], b->frame_cap, b->vt, b->vt_slots, b->vt_fslot, behind_k3(b)));
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_vessel_table(gnuais_batch *b, gnuais_vessel *vessels, int cap, int *n_vessels)
+{
+    if (!b || !n_vessels || cap < 0 || (cap > 0 && !vessels)) return fail(GNUAIS_E_ARG, "vessel_table: argument");
+    *n_vessels = 0;
+    if (!b->vt) return fail(GNUAIS_E_STATE, "vessel_table: no table (gnuais_batch_vessel_table_enable)");
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s = b->streaming ? b->s_post : behind_k3(b);
+    uint32_t info[4] = {0, 0, 0, 0};
+    int n = 0;
+    HIP_TRY(vessel_table_fetch(b->vt, b->vt_slots, vessels, cap, &n, info, s));
+    *n_vessels = n;
+    if (info[1] || (int) info[0] > b->vt_capacity) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "vessel_table: more vessels than the table was enabled for (%u seen%s, capacity %d)",
+                 info[0], info[1] ? ", some dropped" : "", b->vt_capacity);
+        return fail(GNUAIS_E_OVERFLOW, msg);
+    }
+    if (n > cap) return fail(GNUAIS_E_OVERFLOW, "vessel_table: output too small (*n_vessels entries needed)");
+    std::sort(vessels, vessels + n, [](const gnuais_vessel &x, const gnuais_vessel &y) { return x.mmsi < y.mmsi; });
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_drain_frames(gnuais_batch *b, gnuais_frame *h_out, int max, int *n_out)
+{
+    if (!b || !n_out || (max > 0 && !h_out)) return fail(GNUAIS_E_ARG, "drain_frames: argument");
+    *n_out = 0;
+    static gnuais_frame none;
+    return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr);
+}
+
+int gnuais_batch_drain_nmea(gnuais_batch *b, uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len,
+                            int *n_sentences, int *n_frames)
+{
+    if (!b || !seqnr || !out_len || (out_cap > 0 && !out)) return fail(GNUAIS_E_ARG, "drain_nmea: argument");
+    *out_len = 0;
+    if (n_sentences) *n_sentences = 0;
+    if (n_frames) *n_frames = 0;
+    return drain_impl(b, nullptr, 0, n_frames, seqnr, out, out_cap, out_len, n_sentences);
+}
+
+int gnuais_batch_drain_frames_nmea(gnuais_batch *b, gnuais_frame *h_frames, int max, int *n_frames,
+                                   uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len, int *n_sentences)
+{
+    if (!b || !h_frames || !n_frames || !seqnr || !out_len || (out_cap > 0 && !out))
+        return fail(GNUAIS_E_ARG, "drain_frames_nmea: argument");
+    *n_frames = 0;
+    *out_len = 0;
+    if (n_sentences) *n_sentences = 0;
+    return drain_impl(b, h_frames, max, n_frames, seqnr, out, out_cap, out_len, n_sentences);
+}
+
+// First use of the streamed delivery (or back from set_option("streaming", 0)): the other rings, per slot the chunk
+// table, texts and events, the info words, the copy stream, the carried sequence digits.
+static int stream_setup(gnuais_batch *b)
+{
+    constexpr int NR = gnuais_batch::NRING;
+    const size_t N = (size_t) b->N;
+    const size_t text_cap = (size_t) b->frame_cap * 164;        // a full ring of two-sentence frames
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
+    // allocation) is repeated by the next call without leaking what the failed one had made
+    for (int q = 1; q < NR; ++q) {
+        HIP_TRY(b->ring[q].ensure(sizeof(gnuais_frame) * (size_t) b->frame_cap));
+        HIP_TRY(b->ring_count[q].ensure(sizeof(uint32_t) * 4, true));
+    }
+    b->n_chunks = k3_blocks(b->N) * k3_passes(b->cand_K);
+    b->sh_text_want = std::max(b->sh_text_want, ((size_t) b->frame_cap * 32 + 65536) & ~(size_t) 15);
+    for (int q = 0; q < NR; ++q) {
+        HIP_TRY(b->ring_chunks[q].ensure(sizeof(uint2) * (size_t) b->n_chunks));
+        b->ring_runs[q] = 2;                // whatever ring 0 holds by now came without a table
+        HIP_TRY(b->sd_text[q].ensure(text_cap));
+        for (Event *e : {&b->e_fill[q], &b->e_fmt[q], &b->e_txt[q]}) HIP_TRY(e->ensure(hipEventDisableTiming));
+        // pinned text: a fifth of the worst case to begin with (single-sentence frames of average
+        // length fill it to about a third); a slot whose text does not fit grows, see (3)
+        HIP_TRY(b->sh_text[q].ensure(b->sh_text_want));
+    }
+    HIP_TRY(b->sd_info.ensure(sizeof(uint32_t) * 8 * NR, true));
+    if (const char *v = getenv("GNUAIS_COPY_WGS")) b->copy_wgs = std::max(1, atoi(v));
+    if (const char *v = getenv("GNUAIS_COPY_ON_K3")) b->copy_on_k3 = atoi(v) != 0;
+    HIP_TRY(b->nmea_scratch.grow(nmea_scratch_bytes(b->frame_cap, b->n_chunks)));
+    if (!b->s_copy_own) {
+        // The formatter's kernels go onto K3's stream: they are small, K3's stream is idle most of a call,
+        // and every further stream is one more tenant for the few hardware queues (a formatter stream
+        // that shares its queue with a stage serialises with it: 0.8 or 1.5 ms per call, by luck).
+        // Only the copy, which lasts as long as PCIe needs, has a stream of its own.
+        int lo = 0, hi = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIP_TRY(b->s_copy_own.ensure(hi));
+        b->s_copy = b->s_copy_own;
+    }
+    HIP_TRY(b->sh_info.ensure(sizeof(uint32_t) * 8 * NR, true));
+    for (auto &p : b->sd_seq) HIP_TRY(p.ensure(N, true));
+    HIP_TRY(hipDeviceSynchronize());
+    b->streaming = true;
+    return GNUAIS_OK;
+}
+
+// Streaming delivery (row f1 end to end).  Call after every gnuais_batch_run(): the frames of the
+// runs since the previous call are taken off (K3 moves on to the next ring at once) and go through
+// three later calls -- two calls on: count read + device formatter queued; then: text copy into pinned
+// memory queued; then: text handed out -- so that no call waits for work queued in the same call.
+int gnuais_batch_stream_nmea(gnuais_batch *b, const char **text, size_t *len, int *n_sentences, int *n_frames)
+{
+    if (!b || !text || !len) return fail(GNUAIS_E_ARG, "stream_nmea: argument");
+    if (int rc = set_device(b)) return rc;
+    *text = nullptr;
+    *len = 0;
+    if (n_sentences) *n_sentences = 0;
+    if (n_frames) *n_frames = -1;               // nothing handed out yet
+    constexpr int NR = gnuais_batch::NRING;
+    const size_t N = (size_t) b->N;
+    if (!b->streaming)
+        if (int rc = stream_setup(b)) return rc;
+    hipStream_t sD = behind_k3(b);
+    const int c = b->ring_cur;
+    // (1) ring c: everything K3 has been asked to append so far
+    HIP_TRY(hipEventRecord(b->e_fill[c], sD));
+    const int runs = b->ring_runs[c];
+    // (2) K3 moves on to the next ring; that ring's formatter (queued NRING - 1 calls ago) must be done
+    const int nx = (c + 1) % NR;
+    if (b->s_stage[nx]) HIP_TRY(hipStreamWaitEvent(sD, b->e_fmt[nx], 0));
+    b->ring_cur = nx;
+    b->ring_runs[nx] = 0;
+    // (3) hand out the text of slot nx, queued NRING - 1 calls ago: the only wait of this call.  (Before (4): a slow-path copy below must not queue behind it.)
+    int rc_late = GNUAIS_OK;
+    if (b->s_stage[nx]) {
+        HIP_TRY(hipEventSynchronize(b->e_txt[nx]));
+        const uint32_t *info = b->sh_info + 8 * nx;
+        const uint32_t have = std::min<uint32_t>(info[4], (uint32_t) b->frame_cap);
+        const size_t n_text = (size_t) info[0] + info[1];
+        if (n_text > b->sh_text[nx].bytes) {
+            // the pinned buffer was too small for this slot (the first calls, or traffic grew): make it larger
+            // and fetch the text from the device copy, which stays intact until the slot is formatted again
+            const size_t want = std::max(b->sh_text_want, (n_text + n_text / 2 + 65536) & ~(size_t) 15);
+            b->sh_text_want = want;
+            HIP_TRY(b->sh_text[nx].grow(b->sh_text_want));
+            HIP_TRY(hipMemcpyAsync(b->sh_text[nx], b->sd_text[nx], n_text, hipMemcpyDeviceToHost, b->s_copy));
+            HIP_TRY(hipStreamSynchronize(b->s_copy));
+        }
+        *text = b->sh_text[nx];
+        *len = n_text;
+        if (n_sentences) *n_sentences = (int) info[2];
+        if (n_frames) *n_frames = (int) have;
+        b->s_stage[nx] = 0;
+        if (info[3]) rc_late = fail(GNUAIS_E_HIP, "stream_nmea: a frame record names a channel outside the batch");
+        else rc_late = late_error("stream_nmea", info[7] != 0, info[5] || info[4] > (uint32_t) b->frame_cap);
+    }
+    // (4) ring c: order, sequence digits, text, copy into pinned memory -- queued now, behind its K3, with
+    // every size taken on the device
+    b->s_post = sD;                             // behind the K3 launches that filled the ring, in stream order
+    uint32_t *totals = nullptr;
+    HIP_TRY(b->sh_text[c].grow(b->sh_text_want));               // catch up with a buffer that had to grow (slot c is idle)
+    if (runs >= 1) {
+        int n_host = -1;                        // one run: K3's chunk table is the order, the count stays on the device
+        if (runs > 1) {                         // several runs share the ring: count on the host, radix sort
+            uint32_t cnt[4];
+            HIP_TRY(hipStreamSynchronize(b->s_post));
+            HIP_TRY(hipMemcpy(cnt, b->ring_count[c], 16, hipMemcpyDeviceToHost));
+            n_host = (int) std::min<uint32_t>(cnt[0], (uint32_t) b->frame_cap);
+        }
+        if (n_host != 0) {
+            uint8_t *sin = b->sd_seq[b->sd_seq_cur], *sout = b->sd_seq[b->sd_seq_cur ^ 1];
+            HIP_TRY(hipMemcpyAsync(sout, sin, N, hipMemcpyDeviceToDevice, b->s_post));
+            HIP_TRY(nmea_format_enqueue(b->ring[c], n_host, b->frame_cap, b->N, sin, sout, b->sd_text[c],
+                                        b->sd_text[c].bytes, b->nmea_scratch, b->nmea_scratch.bytes, nullptr,
+                                        b->ring_chunks[c], b->n_chunks, k3_passes(b->cand_K), &totals, b->s_post));
+            b->sd_seq_cur ^= 1;
+        }
+    }
+    // the span's frames into the carried vessel table, behind the formatter and before the ring is handed back
+    if (b->vt && runs >= 1)
+        HIP_TRY(vessel_table_update_enqueue(b->ring[c], b->ring_count[c], b->frame_cap, b->vt, b->vt_slots, b->vt_fslot,
+                                            b->s_post));
+    HIP_TRY(nmea_slot_info_enqueue(totals, b->ring_count[c], b->sd_info + 8 * c, b->s_post));
+    HIP_TRY(hipMemsetAsync(b->ring_count[c], 0, 16, b->s_post));
+    HIP_TRY(hipEventRecord(b->e_fmt[c], b->s_post));          // the ring is free for K3 again
+    // (5) the copy has a stream of its own: it runs at PCIe speed beside the next slot's formatter
+    hipStream_t sc = b->copy_on_k3 ? b->s_post : b->s_copy;
+    if (!b->copy_on_k3) HIP_TRY(hipStreamWaitEvent(sc, b->e_fmt[c], 0));
+    HIP_TRY(nmea_text_copy_enqueue(b->sd_text[c], b->sd_info + 8 * c, b->sh_text[c], b->sh_text[c].bytes,
+                                   b->sh_info + 8 * c, b->copy_wgs, sc));
+    HIP_TRY(hipEventRecord(b->e_txt[c], sc));
+    b->s_stage[c] = 1;
+    b->hdlc_calls = 0;
+    b->stream_calls++;
+    return rc_late;
+}
+
+int gnuais_batch_pending_frames(gnuais_batch *b, int *n_out)
+{
+    if (!b || !n_out) return fail(GNUAIS_E_ARG, "pending_frames: argument");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "pending_frames: the batch is streaming (gnuais_batch_stream_nmea)");
+    Pending pend;
+    if (int rc = read_pending(b, pend)) return rc;
+    *n_out = (int) pend.have;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_discard_frames(gnuais_batch *b, void *stream)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "discard_frames: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "discard_frames: the batch is streaming (gnuais_batch_stream_nmea)");
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s = b->pipeline ? k3_stream(b) : (hipStream_t) stream;   // behind the last K3
+    HIP_TRY(hipMemsetAsync(b->ring_count[0], 0, sizeof(uint32_t) * 3, s));
+    b->hdlc_calls = 0;
+    return GNUAIS_OK;
+}
+
+// The delivery loop (run + stream_nmea) has one more stream to place: the copy kernel's.  Which hardware
+// queue a stream shares is not queryable (see gnuais_batch_autotune); a copy stream that shares its queue with
+// a stage serialises with it (0.62 against 1.5 ms per C3 call).  Times the loop with the copy kernel on each
+// free pool stream and on the stream created for it, keeps the fastest, resets the batch (it stays in
+// streaming mode).
+int gnuais_batch_autotune_delivery(gnuais_batch *b, const int16_t *d_samples, int len, void *stream, float *ms_per_call)
+{
+    if (!b || !d_samples) return fail(GNUAIS_E_ARG, "autotune_delivery: NULL argument");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    const char *text = nullptr;
+    size_t tl = 0;
+    if (int rc = gnuais_batch_stream_nmea(b, &text, &tl, nullptr, nullptr)) return rc;      // rings, buffers, s_copy
+    if (!b->pipeline) {
+        if (ms_per_call) *ms_per_call = 0.0f;
+        return gnuais_batch_reset(b);
+    }
+    const bool timing = b->timing;
+    b->timing = false;
+    auto quiesce = [&]() -> int {
+        if (int rc = gnuais_batch_sync(b)) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        return GNUAIS_OK;
+    };
+    auto measure = [&](double &ms, int meas) -> int {
+        const int warm = gnuais_batch::NRING + 2;
+        for (int i = 0; i < warm + meas; ++i) {
+            if (i == warm) {
+                if (int rc = quiesce()) return rc;
+                ms = -now_ms();
+            }
+            if (int rc = gnuais_batch_run(b, d_samples, len, stream)) return rc;
+            const int rc = gnuais_batch_stream_nmea(b, &text, &tl, nullptr, nullptr);
+            if (rc != GNUAIS_OK && rc != GNUAIS_E_OVERFLOW) return rc;
+        }
+        if (int rc = quiesce()) return rc;
+        ms = (ms + now_ms()) / meas;
+        return GNUAIS_OK;
+    };
+    hipStream_t own = b->s_copy_own;
+    // twelve calls per candidate, then the two fastest again over thirty (a dozen calls are noisy)
+    hipStream_t top[2] = {own, own};
+    double top_ms[2] = {1e30, 1e30};
+    for (int cand = -1; cand < gnuais_batch::POOL; ++cand) {
+        hipStream_t st = cand < 0 ? own : b->pool[cand];
+        bool used = false;
+        for (int q = 0; q < 4; ++q) used |= b->s_k[q] == st;
+        if (used || !st) continue;
+        b->s_copy = st;
+        double ms = 0;
+        if (int rc = measure(ms, 12)) return rc;
+        if (ms < top_ms[0]) { top_ms[1] = top_ms[0]; top[1] = top[0]; top_ms[0] = ms; top[0] = st; }
+        else if (ms < top_ms[1]) { top_ms[1] = ms; top[1] = st; }
+    }
+    hipStream_t best_s = top[0];
+    double best = 1e30;
+    for (int k = 0; k < 2; ++k) {
+        if (k == 1 && top[1] == top[0]) break;
+        b->s_copy = top[k];
+        double ms = 0;
+        if (int rc = measure(ms, 30)) return rc;
+        if (ms < best) { best = ms; best_s = top[k]; }
+    }
+    b->s_copy = best_s;
+    b->timing = timing;
+    if (ms_per_call) *ms_per_call = (float) best;
+    return gnuais_batch_reset(b);
+}
+
+} // extern "C"

@@ -1,0 +1,483 @@
+// capi_ingest.hip -- the C ABI's input side (include/gnuais_hip.h): the stages in front of the chain -- discriminator,
+// carrier-error stage, channeliser with its host tables -- and the entries that take a form's input from device or
+// host memory and hand the audio to gnuais_batch_run (gnuais_capi.hip).  Host code only.
+#include "batch.h"
+
+static Form form(const gnuais_batch *b, FormId f)
+{
+    switch (f) {
+    case AUDIO: return {2, b->N, 1, 1u << CHAIN};
+    case IQ: return {4, b->N, 1, 1u << DISC | (b->afc_W ? 1u << AFC : 0u) | 1u << CHAIN};
+    default: return {4, b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages};
+    }
+}
+
+// An intermediate buffer of `bytes`, allocated on first use once the device has room for it: `what` of N x max_len
+template <class T>
+static int alloc_checked(gnuais_batch *b, Buf<T> &p, size_t bytes, const char *who, const char *what)
+{
+    if (p) return GNUAIS_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: %s for %d channels x %d samples needs %.2f GB of device memory, device %d has %.2f "
+                 "GB free of %.2f", who, what, b->N, b->max_len, bytes / 1e9, b->device, free_b / 1e9, total_b / 1e9);
+        return fail(GNUAIS_E_HIP, msg);
+    }
+    HIP_TRY(p.alloc(bytes));
+    return GNUAIS_OK;
+}
+
+// the channeliser's carry and sample count (configuration kept)
+int gnuais::chan_zero_state(gnuais_batch *b)
+{
+    if (b->ch_K)
+        for (auto &p : b->ch_hist)
+            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) (b->ch_T - 1) * (size_t) (b->N / b->ch_K)));
+    b->ch_cur = 0;
+    b->ch_n = 0;
+    b->last[CHAN].used = false;
+    return GNUAIS_OK;
+}
+
+// the AFC stage's carry: row count, delay line, block sums (window kept)
+int gnuais::afc_zero_state(gnuais_batch *b)
+{
+    if (b->afc_W) {
+        const size_t N = (size_t) b->N;
+        HIP_TRY(hipMemset(b->afc_delay, 0, sizeof(int16_t) * N * (size_t) (b->afc_W / 2)));
+        HIP_TRY(hipMemset(b->afc_blk, 0, sizeof(int64_t) * 2 * N * (size_t) b->afc_nb));
+    }
+    b->afc_n = 0;
+    b->afc_est_row = -1;
+    b->last[AFC].used = false;
+    return GNUAIS_OK;
+}
+
+extern "C" {
+
+// ---- complex baseband in (include/gnuais_hip.h): the discriminator (iq_disc.hip) in front of the unchanged chain ----
+
+// afc: the launch also takes the block sums of the rows from afc_n on (afc_launch follows on the same stream)
+static int disc_launch(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, hipStream_t s, bool afc = false)
+{
+    if (afc)
+        HIP_TRY(launch_iq_discriminator_afc(d_iq, d_out, b->iq_prev, b->N, len, b->afc_blk, b->afc_nb, b->afc_n, s));
+    else
+        HIP_TRY(launch_iq_discriminator(d_iq, d_out, b->iq_prev, b->N, len, s));
+    b->last[DISC] = {s, true};
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_discriminate(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream)
+{
+    if (!b || !d_iq || !d_out) return fail(GNUAIS_E_ARG, "discriminate: NULL argument");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "discriminate: len out of range (max_len)");
+    if (int rc = set_device(b)) return rc;
+    if (int rc = drain(b, 1u << DISC, (hipStream_t) stream)) return rc;
+    return disc_launch(b, d_iq, len, d_out, (hipStream_t) stream);
+}
+
+// ---- the carrier-error stage (include/gnuais_hip.h, afc.hip) between the discriminator and the chain ----
+
+int gnuais_batch_afc(gnuais_batch *b, int window)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "afc: NULL batch");
+    if (window && (window < AFC_MIN_WINDOW || window > AFC_MAX_WINDOW || window % (2 * AFC_BLOCK)))
+        return fail(GNUAIS_E_ARG, "afc: the window must be 0 (off) or a multiple of 128 from 128 to 16384");
+    if (int rc = set_device(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(b->afc_blk.release());
+    HIP_TRY(b->afc_delay.release());
+    HIP_TRY(b->afc_est.release());
+    b->afc_W = 0;
+    if (window) {
+        const size_t N = (size_t) b->N;
+        const int call_blocks = (b->max_len + AFC_BLOCK - 1) / AFC_BLOCK + 1;      // a call that starts inside a block
+        // the blocks of the oldest window a call reads up to the last one it writes
+        b->afc_nb = window / AFC_BLOCK + call_blocks + 1;
+        if (int rc = alloc_checked(b, b->afc_blk, sizeof(int64_t) * 2 * N * (size_t) b->afc_nb, "afc", "the block sums")) return rc;
+        if (int rc = alloc_checked(b, b->afc_delay, sizeof(int16_t) * N * (size_t) (window / 2), "afc", "the delay line")) return rc;
+        if (int rc = alloc_checked(b, b->afc_est, sizeof(int16_t) * N * (size_t) call_blocks, "afc", "the estimates")) return rc;
+        b->afc_W = window;
+    }
+    if (int rc = afc_zero_state(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return GNUAIS_OK;
+}
+
+// behind disc_launch(.., afc = true) on s: the estimates of the blocks this call's output rows need, then the corrected
+// audio of its len rows
+static int afc_launch(gnuais_batch *b, const int16_t *d_audio, int len, int16_t *d_out, hipStream_t s)
+{
+    const unsigned long long n0 = b->afc_n, n1 = n0 + (unsigned long long) len, L = (unsigned long long) (b->afc_W / 2);
+    long long j_lo = 0;
+    if (n1 > L) {                                // row n1 - 1 has m >= 0: blocks (max(n0 - L, 0)) / 64 .. (n1 - 1 - L) / 64
+        j_lo = (long long) ((n0 > L ? n0 - L : 0) / AFC_BLOCK);
+        const int n_est = (int) ((long long) ((n1 - 1 - L) / AFC_BLOCK) - j_lo) + 1;
+        HIP_TRY(launch_afc_estimate(b->afc_blk, b->afc_nb, b->N, b->afc_est, j_lo, n_est, b->afc_W, s));
+        b->afc_est_row = n_est - 1;
+    }
+    HIP_TRY(launch_afc_apply(d_audio, b->afc_delay, b->afc_est, j_lo, d_out, b->N, len, b->afc_W, n0, s));
+    b->afc_n = n1;
+    b->last[AFC] = {s, true};
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_afc_apply(gnuais_batch *b, const int16_t *d_iq, int len, int16_t *d_out, void *stream)
+{
+    if (!b || !d_iq || !d_out) return fail(GNUAIS_E_ARG, "afc_apply: NULL argument");
+    if (!b->afc_W) return fail(GNUAIS_E_STATE, "afc_apply: the AFC is off (gnuais_batch_afc)");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "afc_apply: len out of range (max_len)");
+    if (int rc = set_device(b)) return rc;
+    hipStream_t s = (hipStream_t) stream;
+    if (int rc = drain(b, 1u << DISC | 1u << AFC, s)) return rc;
+    if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), "afc_apply", "the discriminator's audio"))
+        return rc;
+    if (int rc = disc_launch(b, d_iq, len, b->iq_audio, s, true)) return rc;
+    return afc_launch(b, b->iq_audio, len, d_out, s);
+}
+
+int gnuais_batch_afc_estimate(gnuais_batch *b, int16_t *h_out)
+{
+    if (!b || !h_out) return fail(GNUAIS_E_ARG, "afc_estimate: NULL argument");
+    if (!b->afc_W) return fail(GNUAIS_E_STATE, "afc_estimate: the AFC is off (gnuais_batch_afc)");
+    if (int rc = set_device(b)) return rc;
+    if (b->afc_est_row < 0) {
+        memset(h_out, 0, sizeof(int16_t) * (size_t) b->N);
+        return GNUAIS_OK;
+    }
+    if (b->last[AFC].used) HIP_TRY(hipStreamSynchronize(b->last[AFC].s));
+    HIP_TRY(hipMemcpy(h_out, b->afc_est + (size_t) b->afc_est_row * (size_t) b->N, sizeof(int16_t) * (size_t) b->N,
+                      hipMemcpyDeviceToHost));
+    return GNUAIS_OK;
+}
+
+// ---- wideband in (include/gnuais_hip.h): the channeliser (channeliser.hip) in front of the discriminator ----
+
+static long long rnd_away(double x) { return lround(x); }
+
+static int chan_default_taps(int D, std::vector<int16_t> &h)
+{
+    const int T = 16 * D + 1;
+    std::vector<double> g((size_t) T);
+    double G = 0.0;
+    for (int j = 0; j < T; ++j) {
+        const double w = 0.42 - 0.5 * cos(2.0 * M_PI * j / (T - 1)) + 0.08 * cos(4.0 * M_PI * j / (T - 1));
+        const double x = 0.75 * (j - 8 * D) / D;
+        const double s = (x == 0.0) ? 1.0 : sin(M_PI * x) / (M_PI * x);
+        g[(size_t) j] = w * s;
+        G += g[(size_t) j];
+    }
+    h.resize((size_t) T);
+    for (int j = 0; j < T; ++j) h[(size_t) j] = (int16_t) rnd_away(g[(size_t) j] * 32768.0 / G);
+    return T;
+}
+
+static long long gcd_ll(long long a, long long b)
+{
+    while (b) { const long long t = a % b; a = b; b = t; }
+    return a;
+}
+
+// the period of offset f at rate R, or 0 if it exceeds 2^20
+static int chan_period(int R, int f)
+{
+    const long long g = gcd_ll(std::llabs((long long) f), (long long) R);
+    const long long P = (long long) R / g;
+    return P > (1LL << 20) ? 0 : (int) P;
+}
+
+static void chan_mixer(int R, int f, int P, int16_t *cs)
+{
+    for (int p = 0; p < P; ++p) {
+        long long q = ((long long) f * p) % R;
+        if (q < 0) q += R;
+        const double th = 2.0 * M_PI * (double) q / (double) R;
+        cs[2 * p] = (int16_t) rnd_away(32767.0 * cos(th));
+        cs[2 * p + 1] = (int16_t) rnd_away(32767.0 * sin(th));
+    }
+}
+
+int gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps)
+{
+    if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser_default_taps: decim must be 1..64");
+    std::vector<int16_t> h;
+    const int T = chan_default_taps(decim, h);
+    if (n_taps) *n_taps = T;
+    if (!out) return GNUAIS_OK;
+    if (cap < T) return fail(GNUAIS_E_ARG, "channeliser_default_taps: cap < 16*decim + 1");
+    memcpy(out, h.data(), sizeof(int16_t) * (size_t) T);
+    return GNUAIS_OK;
+}
+
+int gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period)
+{
+    if (in_rate_hz <= 0) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: in_rate_hz must be > 0");
+    const int P = chan_period(in_rate_hz, offset_hz);
+    if (!P) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: the offset's mixer period R / gcd(|f|, R) exceeds 2^20");
+    if (period) *period = P;
+    if (!out) return GNUAIS_OK;
+    if (cap < P) return fail(GNUAIS_E_ARG, "channeliser_mixer_table: cap < period");
+    chan_mixer(in_rate_hz, offset_hz, P, out);
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                             const int16_t *taps, int n_taps)
+{
+    if (!b || !offsets_hz) return fail(GNUAIS_E_ARG, "channeliser: NULL argument");
+    if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser: decim must be 1..64");
+    if (in_rate_hz <= 0) return fail(GNUAIS_E_ARG, "channeliser: in_rate_hz must be > 0");
+    if (n_offsets < 1 || n_offsets > CHAN_MAX_K) return fail(GNUAIS_E_ARG, "channeliser: n_offsets must be 1..32");
+    if (b->N % n_offsets) return fail(GNUAIS_E_ARG, "channeliser: the batch's channel count is not a multiple of n_offsets");
+    std::vector<int16_t> h;
+    if (!taps || n_taps == 0) {
+        chan_default_taps(decim, h);
+    } else {
+        if (n_taps < 1 || n_taps > 1025) return fail(GNUAIS_E_ARG, "channeliser: n_taps must be 1..1025");
+        h.assign(taps, taps + n_taps);
+    }
+    const int T = (int) h.size();
+    long long sum = 0;
+    for (int16_t v : h) {
+        if (v == -32768) return fail(GNUAIS_E_ARG, "channeliser: a tap is -32768 (|h| <= 32767)");
+        sum += std::abs((int) v);
+    }
+    if (sum > 65535) return fail(GNUAIS_E_ARG, "channeliser: sum |h| exceeds 65535");
+    const int K = n_offsets;
+    int per[CHAN_MAX_K], off[CHAN_MAX_K];
+    int total = 0;
+    for (int k = 0; k < K; ++k) {
+        per[k] = chan_period(in_rate_hz, offsets_hz[k]);
+        if (!per[k]) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "channeliser: offset %d Hz at %d Hz has a mixer period above 2^20", (int) offsets_hz[k],
+                     in_rate_hz);
+            return fail(GNUAIS_E_ARG, msg);
+        }
+        off[k] = total;
+        total += per[k];
+    }
+    // host tables: mixer words (C lo, S hi); the fast form's tap pairs POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q])
+    std::vector<int16_t> mix(2 * (size_t) total);
+    for (int k = 0; k < K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], per[k], mix.data() + 2 * (size_t) off[k]);
+    const int D = decim;
+    const int NA = channeliser_fast_na(K, T, D);
+    std::vector<uint32_t> poly;
+    if (NA) {
+        const int NP = (D + 1) / 2;
+        poly.assign((size_t) NP * NA, 0u);
+        auto tap = [&](int a, int r) -> int {
+            if (r >= D) return 0;
+            const int j = a * D + D - 1 - r;
+            return j < T ? h[(size_t) j] : 0;
+        };
+        for (int q = 0; q < NP; ++q)
+            for (int a = 0; a < NA; ++a)
+                poly[(size_t) q * NA + a] = (uint32_t) (uint16_t) tap(a, 2 * q) | ((uint32_t) (uint16_t) tap(a, 2 * q + 1) << 16);
+    }
+    if (int rc = set_device(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (Buf<uint32_t> *p : {&b->ch_mix, &b->ch_poly, &b->ch_hist[0], &b->ch_hist[1]}) HIP_TRY(p->release());
+    HIP_TRY(b->ch_taps.release());
+    b->ch_K = 0;
+    const size_t M = (size_t) (b->N / K);
+    HIP_TRY(b->ch_mix.alloc(sizeof(uint32_t) * (size_t) total));
+    HIP_TRY(hipMemcpy(b->ch_mix, mix.data(), sizeof(uint32_t) * (size_t) total, hipMemcpyHostToDevice));
+    HIP_TRY(b->ch_taps.alloc(sizeof(int16_t) * (size_t) T));
+    HIP_TRY(hipMemcpy(b->ch_taps, h.data(), sizeof(int16_t) * (size_t) T, hipMemcpyHostToDevice));
+    if (NA) {
+        HIP_TRY(b->ch_poly.alloc(sizeof(uint32_t) * poly.size()));
+        HIP_TRY(hipMemcpy(b->ch_poly, poly.data(), sizeof(uint32_t) * poly.size(), hipMemcpyHostToDevice));
+    }
+    if (T > 1)
+        for (auto &p : b->ch_hist) HIP_TRY(p.alloc(sizeof(uint32_t) * (size_t) (T - 1) * M));
+    b->ch_K = K;
+    b->ch_D = D;
+    b->ch_T = T;
+    b->ch_R = in_rate_hz;
+    b->ch_NA = NA;
+    for (int k = 0; k < K; ++k) { b->ch_per[k] = per[k]; b->ch_off[k] = off[k]; }
+    if (int rc = chan_zero_state(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return GNUAIS_OK;
+}
+
+// The checks of the entries that take a form's input, in the name of the entry `who` (the device entries of the
+// narrowband forms add "(max_len)" to the len message, as gnuais_batch_run does)
+static int check_input(const gnuais_batch *b, FormId id, const int16_t *x, int len, const char *who, bool host)
+{
+    char msg[200];
+    if (!b || !x) {
+        snprintf(msg, sizeof msg, "%s: NULL argument", who);
+    } else if (id != WIDE) {
+        if (len > 0 && len <= b->max_len) return GNUAIS_OK;
+        snprintf(msg, sizeof msg, "%s: len out of range%s", who, host ? "" : " (max_len)");
+    } else if (!b->ch_K) {
+        snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
+    } else if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
+        snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
+                 len, b->ch_D, b->ch_D);
+    } else if (reinterpret_cast<uintptr_t>(x) % 4) {
+        snprintf(msg, sizeof msg, "%s: the wide samples must be 4-byte aligned", who);
+    } else {
+        return GNUAIS_OK;
+    }
+    return fail(GNUAIS_E_ARG, msg);
+}
+
+static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, hipStream_t s)
+{
+    ChanLaunch a{};
+    a.in = reinterpret_cast<const uint32_t *>(d_wide);
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.hist = b->ch_hist[b->ch_cur];
+    a.mix = b->ch_mix;
+    a.poly = b->ch_poly;
+    a.taps = b->ch_taps;
+    a.M = b->N / b->ch_K;
+    a.K = b->ch_K;
+    a.D = b->ch_D;
+    a.T = b->ch_T;
+    a.len = len;
+    // the fast form stores K words per lane as one vector: the output must be aligned to it (else the direct form)
+    const unsigned vec = a.K == 2 ? 8u : a.K == 4 ? 16u : 4u;
+    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : b->ch_NA;
+    if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(GNUAIS_E_ARG, "channelise: the output must be 4-byte aligned");
+    for (int k = 0; k < a.K; ++k) {
+        a.per[k] = b->ch_per[k];
+        a.off[k] = b->ch_off[k];
+        a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
+    }
+    HIP_TRY(launch_channeliser(a, b->ch_hist[b->ch_cur ^ 1], s));
+    if (b->ch_T > 1) b->ch_cur ^= 1;
+    b->ch_n += (unsigned long long) len;
+    b->last[CHAN] = {s, true};
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream)
+{
+    if (int rc = check_input(b, WIDE, d_wide, len, "channelise", false)) return rc;
+    if (!d_out) return fail(GNUAIS_E_ARG, "channelise: NULL argument");
+    if (int rc = set_device(b)) return rc;
+    if (int rc = drain(b, 1u << CHAN, (hipStream_t) stream)) return rc;
+    return chan_launch(b, d_wide, len, d_out, (hipStream_t) stream);
+}
+
+// ---- one run path and one host path for every input form ----
+
+// gnuais_batch_run_iq / _run_wideband: on the caller's stream, the stages in front of the chain, each into the
+// intermediate buffer that the next one reads, then gnuais_batch_run on the audio
+static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void *stream, const char *who)
+{
+    if (int rc = check_input(b, id, x, len, who, false)) return rc;
+    if (int rc = set_device(b)) return rc;
+    const Form f = form(b, id);
+    const bool chan = f.stages >> CHAN & 1u, disc = f.stages >> DISC & 1u, afc = f.stages >> AFC & 1u;
+    hipStream_t s = (hipStream_t) stream;
+    if (int rc = drain(b, f.stages, s)) return rc;
+    // the channeliser writes max_len rows of the I/Q form, the discriminator and the AFC max_len rows of the audio form
+    if (chan)
+        if (int rc = alloc_checked(b, b->ch_iq, form(b, IQ).bytes_of(b->max_len), who, "the channeliser's I/Q")) return rc;
+    if (disc)
+        if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the discriminator's audio"))
+            return rc;
+    if (afc)
+        if (int rc = alloc_checked(b, b->afc_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the AFC's audio")) return rc;
+    if (chan) {
+        if (int rc = chan_launch(b, x, len, b->ch_iq, s)) return rc;
+        x = b->ch_iq;
+    }
+    len /= f.rows;
+    if (disc) {
+        if (int rc = disc_launch(b, x, len, b->iq_audio, s, afc)) return rc;
+        x = b->iq_audio;
+    }
+    if (afc) {
+        if (int rc = afc_launch(b, x, len, b->afc_audio, s)) return rc;
+        x = b->afc_audio;
+    }
+    return gnuais_batch_run(b, x, len, stream);
+}
+
+// gnuais_batch_run_host / _run_iq_host / _run_wideband_host: the host input staged in stage_x, then `run`, the
+// device entry of the same form, on the NULL stream, then a sync
+static int run_staged(gnuais_batch *b, FormId id, const int16_t *h, int len, const char *who,
+                      int (*run)(gnuais_batch *, const int16_t *, int, void *))
+{
+    if (int rc = check_input(b, id, h, len, who, true)) return rc;
+    if (int rc = set_device(b)) return rc;
+    const size_t bytes = form(b, id).bytes_of(len);
+    HIP_TRY(b->stage_x.grow(bytes));
+    HIP_TRY(hipMemcpy(b->stage_x, h, bytes, hipMemcpyHostToDevice));
+    if (int rc = run(b, b->stage_x, len, nullptr)) return rc;
+    return gnuais_batch_sync(b);
+}
+
+int gnuais_batch_run_iq(gnuais_batch *b, const int16_t *d_iq, int len, void *stream)
+{
+    return run_form(b, IQ, d_iq, len, stream, "run_iq");
+}
+
+int gnuais_batch_run_wideband(gnuais_batch *b, const int16_t *d_wide, int len, void *stream)
+{
+    return run_form(b, WIDE, d_wide, len, stream, "run_wideband");
+}
+
+int gnuais_batch_run_host(gnuais_batch *b, const int16_t *h_samples, int len)
+{
+    return run_staged(b, AUDIO, h_samples, len, "run_host", gnuais_batch_run);
+}
+
+int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
+{
+    return run_staged(b, IQ, h_iq, len, "run_iq_host", gnuais_batch_run_iq);
+}
+
+int gnuais_batch_run_wideband_host(gnuais_batch *b, const int16_t *h_wide, int len)
+{
+    return run_staged(b, WIDE, h_wide, len, "run_wideband_host", gnuais_batch_run_wideband);
+}
+
+int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int len)
+{
+    if (!b || !h_samples) return fail(GNUAIS_E_ARG, "run_host_async: NULL argument");
+    if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run_host_async: len out of range");
+    if (int rc = set_device(b)) return rc;
+    const size_t bytes = sizeof(int16_t) * (size_t) len * (size_t) b->N;
+    HIP_TRY(b->s_io.ensure());
+    for (auto &e : b->e_in) HIP_TRY(e.ensure(hipEventDisableTiming));
+    if (b->pin_bytes < bytes) {                 // (re)size for the largest call seen
+        HIP_TRY(hipStreamSynchronize(b->s_io));
+        const size_t cap = sizeof(int16_t) * (size_t) b->max_len * (size_t) b->N;
+        const size_t want = std::min(cap, std::max(bytes, (size_t) 1 << 20));
+        for (int q = 0; q < 2; ++q) {              // all four go before any comes back
+            HIP_TRY(b->pin[q].release());
+            HIP_TRY(b->dev_in[q].release());
+        }
+        b->pin_bytes = 0;
+        for (int q = 0; q < 2; ++q) {
+            HIP_TRY(b->pin[q].alloc(want));
+            HIP_TRY(b->dev_in[q].alloc(want));
+        }
+        b->pin_bytes = want;
+        b->host_calls = 0;
+    }
+    const int q = (int) (b->host_calls & 1);
+    // the pair was last used two calls ago: its transfer and the FIR that read it must be done
+    if (b->host_calls >= 2) HIP_TRY(hipEventSynchronize(b->e_in[q]));
+    memcpy(b->pin[q], h_samples, bytes);
+    HIP_TRY(hipMemcpyAsync(b->dev_in[q], b->pin[q], bytes, hipMemcpyHostToDevice, b->s_io));
+    b->e_in_hook = b->e_in[q];                  // recorded right behind K1 (run_chain): K1 is the input's only reader
+    const int rc = gnuais_batch_run(b, b->dev_in[q], len, b->s_io);
+    if (b->e_in_hook) {                         // the run failed before its K1: whatever s_io holds (the copy) guards the pair
+        b->e_in_hook = nullptr;
+        (void) hipEventRecord(b->e_in[q], b->s_io);
+    }
+    b->host_calls++;                            // also after a failed run: the copy from pin[q] may still be in flight
+    return rc;
+}
+
+} // extern "C"

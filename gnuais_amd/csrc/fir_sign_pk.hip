@@ -22,7 +22,7 @@
 // swapped by op_sel; the sample broadcast is op_sel too.  After the first instruction group slot P+1 is complete (its
 // last term was tc[NC-1] * x_P): it is read and cleared; after the second, slot P+2.  Every accumulator receives its
 // NC products in sample order, one fused rounding each -- the arithmetic of the scalar transposed form, so the host's
-// bound for it (ordered sum of NC fused terms, gnuais_capi.hip) carries over unchanged.
+// bound for it (ordered sum of NC fused terms, fir_plan.cpp) carries over unchanged.
 //
 // Everything around the sum (typed loads, flags through v_alignbit_b32, the silence test, the exact ordered NE-tap
 // re-evaluation of uncertified samples, the running window maximum that scales eps for long tables, peak, carry) is
@@ -70,7 +70,7 @@ constexpr int PK_PEND = 8;          // noted outputs per lane (1 KB of LDS per w
 template <int NES> struct PkExact { float te[NES > 0 ? NES : 1]; };
 // INLOOP: eps = seen * M / 32768 + ahead with M the running maximum of |x| over the rows behind AND the rest of the
 // output's own 16-row group; [0..3]: the output completes >= 6, 4, 2, 0 rows before the group's end (pair steps 0-4, 5,
-// 6, 7) -- the taps that reach beyond those rows are priced with |x| = 32768 in `ahead` (gnuais_capi.hip)
+// 6, 7) -- the taps that reach beyond those rows are priced with |x| = 32768 in `ahead` (fir_plan.cpp)
 struct PkEps { float seen[4], ahead[4]; };
 
 constexpr int PK_WARM_BATCH = 8;    // warm-up rows loaded at a time

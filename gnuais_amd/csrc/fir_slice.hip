@@ -256,7 +256,7 @@ __global__ __launch_bounds__(64) void fir_slice_kernel(
 //   |S - S_c|     <= X * sum|te outside the centre|
 // with u = 2^-24, X = 32768 (int16 input), S / S_c the exact real sums; subnormal
 // products add at most 32 * 2^-150.  The host adds the three terms in double
-// precision from the actual table (gnuais_capi.hip; 0.124 for the reference table) and
+// precision from the actual table (fir_plan.cpp; 0.124 for the reference table) and
 // passes eps = that * 1.1.  If |y_c| > eps then y_ref has the sign of y_c and is not
 // zero; otherwise (about 1e-4 of the samples of a noisy channel, all of them in
 // a silent one) the sample is re-evaluated with the exact ordered 32-tap sum from

@@ -1,5 +1,5 @@
 // kernels.h -- internal launch interface between the C-ABI host code
-// (gnuais_capi.hip) and the gfx950 kernels.  Not installed.
+// (gnuais_capi.hip, capi_ingest.hip, capi_delivery.hip over batch.h) and the gfx950 kernels.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
