@@ -2,13 +2,15 @@
 // carrier-error stage, channeliser with its host tables -- and the entries that take a form's input from device or
 // host memory and hand the audio to gnuais_batch_run (gnuais_capi.hip).  Host code only.
 #include "batch.h"
+#include "wide_format.h"
 
-static Form form(const gnuais_batch *b, FormId f)
+// fmt: the sample format of a wide column (GNUAIS_FMT_*); the narrowband forms are int16
+static Form form(const gnuais_batch *b, FormId f, int fmt = GNUAIS_FMT_CS16)
 {
     switch (f) {
     case AUDIO: return {2, b->N, 1, 1u << CHAIN};
     case IQ: return {4, b->N, 1, 1u << DISC | (b->afc_W ? 1u << AFC : 0u) | 1u << CHAIN};
-    default: return {4, b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages};
+    default: return {wide_format_bytes(fmt), b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages};
     }
 }
 
@@ -305,8 +307,9 @@ int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const i
 }
 
 // The checks of the entries that take a form's input, in the name of the entry `who` (the device entries of the
-// narrowband forms add "(max_len)" to the len message, as gnuais_batch_run does)
-static int check_input(const gnuais_batch *b, FormId id, const int16_t *x, int len, const char *who, bool host)
+// narrowband forms add "(max_len)" to the len message, as gnuais_batch_run does); fmt: the wide form's sample format
+static int check_input(const gnuais_batch *b, FormId id, const void *x, int len, const char *who, bool host,
+                       int fmt = GNUAIS_FMT_CS16)
 {
     char msg[200];
     if (!b || !x) {
@@ -314,23 +317,26 @@ static int check_input(const gnuais_batch *b, FormId id, const int16_t *x, int l
     } else if (id != WIDE) {
         if (len > 0 && len <= b->max_len) return GNUAIS_OK;
         snprintf(msg, sizeof msg, "%s: len out of range%s", who, host ? "" : " (max_len)");
+    } else if (!wide_format_bytes(fmt)) {
+        snprintf(msg, sizeof msg, "%s: unknown sample format %d (GNUAIS_FMT_*)", who, fmt);
     } else if (!b->ch_K) {
         snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
     } else if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
         snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
                  len, b->ch_D, b->ch_D);
-    } else if (reinterpret_cast<uintptr_t>(x) % 4) {
-        snprintf(msg, sizeof msg, "%s: the wide samples must be 4-byte aligned", who);
+    } else if (reinterpret_cast<uintptr_t>(x) % (uintptr_t) wide_format_align(fmt)) {
+        snprintf(msg, sizeof msg, "%s: %s wide samples must be %d-byte aligned", who, wide_format_name(fmt),
+                 wide_format_align(fmt));
     } else {
         return GNUAIS_OK;
     }
     return fail(GNUAIS_E_ARG, msg);
 }
 
-static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, hipStream_t s)
+static int chan_launch(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, hipStream_t s)
 {
     ChanLaunch a{};
-    a.in = reinterpret_cast<const uint32_t *>(d_wide);
+    a.in = d_wide;
     a.out = reinterpret_cast<uint32_t *>(d_out);
     a.hist = b->ch_hist[b->ch_cur];
     a.mix = b->ch_mix;
@@ -350,29 +356,41 @@ static int chan_launch(gnuais_batch *b, const int16_t *d_wide, int len, int16_t 
         a.off[k] = b->ch_off[k];
         a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
     }
-    HIP_TRY(launch_channeliser(a, b->ch_hist[b->ch_cur ^ 1], s));
+    HIP_TRY(launch_channeliser(a, fmt, b->ch_hist[b->ch_cur ^ 1], s));
     if (b->ch_T > 1) b->ch_cur ^= 1;
     b->ch_n += (unsigned long long) len;
     b->last[CHAN] = {s, true};
     return GNUAIS_OK;
 }
 
-int gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream)
+static int channelise(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, void *stream, const char *who)
 {
-    if (int rc = check_input(b, WIDE, d_wide, len, "channelise", false)) return rc;
-    if (!d_out) return fail(GNUAIS_E_ARG, "channelise: NULL argument");
+    if (int rc = check_input(b, WIDE, d_wide, len, who, false, fmt)) return rc;
+    if (!d_out) return fail(GNUAIS_E_ARG, (std::string(who) + ": NULL argument").c_str());
     if (int rc = set_device(b)) return rc;
     if (int rc = drain(b, 1u << CHAN, (hipStream_t) stream)) return rc;
-    return chan_launch(b, d_wide, len, d_out, (hipStream_t) stream);
+    return chan_launch(b, fmt, d_wide, len, d_out, (hipStream_t) stream);
+}
+
+int gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, int16_t *d_out, void *stream)
+{
+    return channelise(b, GNUAIS_FMT_CS16, d_wide, len, d_out, stream, "channelise");
+}
+
+int gnuais_batch_channelise_fmt(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, void *stream)
+{
+    return channelise(b, fmt, d_wide, len, d_out, stream, "channelise_fmt");
 }
 
 // ---- one run path and one host path for every input form ----
 
 // gnuais_batch_run_iq / _run_wideband: on the caller's stream, the stages in front of the chain, each into the
-// intermediate buffer that the next one reads, then gnuais_batch_run on the audio
-static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void *stream, const char *who)
+// intermediate buffer that the next one reads, then gnuais_batch_run on the audio.  in: the form's input, wide samples in
+// format fmt
+static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *stream, const char *who,
+                    int fmt = GNUAIS_FMT_CS16)
 {
-    if (int rc = check_input(b, id, x, len, who, false)) return rc;
+    if (int rc = check_input(b, id, in, len, who, false, fmt)) return rc;
     if (int rc = set_device(b)) return rc;
     const Form f = form(b, id);
     const bool chan = f.stages >> CHAN & 1u, disc = f.stages >> DISC & 1u, afc = f.stages >> AFC & 1u;
@@ -386,8 +404,9 @@ static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void 
             return rc;
     if (afc)
         if (int rc = alloc_checked(b, b->afc_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the AFC's audio")) return rc;
+    const int16_t *x = static_cast<const int16_t *>(in);
     if (chan) {
-        if (int rc = chan_launch(b, x, len, b->ch_iq, s)) return rc;
+        if (int rc = chan_launch(b, fmt, in, len, b->ch_iq, s)) return rc;
         x = b->ch_iq;
     }
     len /= f.rows;
@@ -403,16 +422,18 @@ static int run_form(gnuais_batch *b, FormId id, const int16_t *x, int len, void 
 }
 
 // gnuais_batch_run_host / _run_iq_host / _run_wideband_host: the host input staged in stage_x, then `run`, the
-// device entry of the same form, on the NULL stream, then a sync
-static int run_staged(gnuais_batch *b, FormId id, const int16_t *h, int len, const char *who,
-                      int (*run)(gnuais_batch *, const int16_t *, int, void *))
+// device entry of the same form, on the NULL stream, then a sync.  run == NULL: the wide form in format fmt, through
+// gnuais_batch_run_wideband_fmt; its bytes are those of the format: nothing is widened on the host
+static int run_staged(gnuais_batch *b, FormId id, const void *h, int len, const char *who,
+                      int (*run)(gnuais_batch *, const int16_t *, int, void *), int fmt = GNUAIS_FMT_CS16)
 {
-    if (int rc = check_input(b, id, h, len, who, true)) return rc;
+    if (int rc = check_input(b, id, h, len, who, true, fmt)) return rc;
     if (int rc = set_device(b)) return rc;
-    const size_t bytes = form(b, id).bytes_of(len);
+    const size_t bytes = form(b, id, fmt).bytes_of(len);
     HIP_TRY(b->stage_x.grow(bytes));
     HIP_TRY(hipMemcpy(b->stage_x, h, bytes, hipMemcpyHostToDevice));
-    if (int rc = run(b, b->stage_x, len, nullptr)) return rc;
+    if (int rc = run ? run(b, b->stage_x, len, nullptr) : gnuais_batch_run_wideband_fmt(b, fmt, b->stage_x, len, nullptr))
+        return rc;
     return gnuais_batch_sync(b);
 }
 
@@ -439,6 +460,16 @@ int gnuais_batch_run_iq_host(gnuais_batch *b, const int16_t *h_iq, int len)
 int gnuais_batch_run_wideband_host(gnuais_batch *b, const int16_t *h_wide, int len)
 {
     return run_staged(b, WIDE, h_wide, len, "run_wideband_host", gnuais_batch_run_wideband);
+}
+
+int gnuais_batch_run_wideband_fmt(gnuais_batch *b, int fmt, const void *d_wide, int len, void *stream)
+{
+    return run_form(b, WIDE, d_wide, len, stream, "run_wideband_fmt", fmt);
+}
+
+int gnuais_batch_run_wideband_fmt_host(gnuais_batch *b, int fmt, const void *h_wide, int len)
+{
+    return run_staged(b, WIDE, h_wide, len, "run_wideband_fmt_host", nullptr, fmt);
 }
 
 int gnuais_batch_run_host_async(gnuais_batch *b, const int16_t *h_samples, int len)

@@ -142,11 +142,12 @@ hipError_t launch_afc_apply(const int16_t *audio, int16_t *delay, const int16_t 
                             int len, int W, unsigned long long n0, hipStream_t stream);
 
 // ---- wideband in: the channeliser (channeliser.hip) -------------------------------------
-// in [len][M][2] int16 -> out [len/D][M*K][2] int16, the definition in include/gnuais_hip.h.  hist [T-1][M] words is the
-// carry (the last T-1 wide samples), read here; the launch writes the next one into hist_out (another buffer).
+// in [len][M] pairs of sample format fmt (GNUAIS_FMT_*, wide_format.h) -> out [len/D][M*K][2] int16, the definition in
+// include/gnuais_hip.h.  hist [T-1][M] words is the carry (the last T-1 wide samples, converted to int16 pairs), read
+// here; the launch writes the next one into hist_out (another buffer).
 constexpr int CHAN_MAX_K = 32;       // offsets per stream
 struct ChanLaunch {
-    const uint32_t *in;    // [len][M] (I lo, Q hi)
+    const void *in;        // [len][M] pairs in the launch's format; as int16: (I lo, Q hi)
     uint32_t *out;         // [len/D][M*K]
     const uint32_t *hist;  // [T-1][M]
     const uint32_t *mix;   // mixer tables, (C lo, S hi), offset k's at mix + off[k], per[k] entries
@@ -159,7 +160,9 @@ struct ChanLaunch {
     int ph0[CHAN_MAX_K];   // (n mod per[k]) of the call's first wide sample
 };
 int channeliser_fast_na(int K, int T, int D);    // 0: no fast form for this shape
-hipError_t launch_channeliser(const ChanLaunch &a, uint32_t *hist_out, hipStream_t stream);
+hipError_t launch_channeliser(const ChanLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
+// the formats other than GNUAIS_FMT_CS16 (channeliser_fmt.hip); hipErrorInvalidValue for an unknown one
+hipError_t launch_channeliser_fmt(const ChanLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
 
 // ---- f1 on the device (nmea_device.hip) ---------------------------------------
 size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);

@@ -123,7 +123,8 @@ struct Booking {
 };
 
 // The input forms (include/gnuais_hip.h) as one shard sees them: a row of the caller's host array holds `cols` columns
-// of `bytes` bytes each, of which the shard owns [c0, c0 + nc); a chain row takes `rows` input rows
+// of `bytes` bytes each (a wide column: its sample format's pair), of which the shard owns [c0, c0 + nc); a chain row
+// takes `rows` input rows
 struct Form { int bytes, cols, c0, nc, rows; };
 enum FormId { AUDIO, IQ, WIDE };
 
@@ -188,10 +189,11 @@ extern "C" {
 
 const char *gnuais_node_last_error(void) { return g_node_err.c_str(); }
 
-static Form form(const gnuais_node *nd, const Shard &s, FormId f)
+static Form form(const gnuais_node *nd, const Shard &s, FormId f, int fmt = GNUAIS_FMT_CS16)
 {
     const int K = f == WIDE ? nd->ch_K : 1;
-    return {f == AUDIO ? 2 : 4, nd->N / K, s.first / K, s.n / K, f == WIDE ? nd->ch_D : 1};
+    return {f == AUDIO ? 2 : f == IQ ? 4 : gnuais_sample_format_bytes(fmt), nd->N / K, s.first / K, s.n / K,
+            f == WIDE ? nd->ch_D : 1};
 }
 
 // f(shard, its index) on every shard's own thread at once; the first failure is reported with the shard it came from
@@ -327,13 +329,14 @@ static int run_slabs(gnuais_node *nd, const int16_t *const *slabs, int len, void
 // shard's slab by one strided 2-D copy, then `run`, the batch entry of the form, reads them there.  Everything that
 // reads the slab runs on s_in (K1, the discriminator, the channeliser), and every call syncs s_in before it returns,
 // so the slab is free again between calls: one slab serves every form, sized for max_len chain rows of the widest one.
-static int run_staged(gnuais_node *nd, FormId id, const int16_t *h, int len, const char *who,
-                      int (*run)(gnuais_batch *, const int16_t *, int, void *))
+// run == NULL: the wide form in sample format fmt, through gnuais_batch_run_wideband_fmt
+static int run_staged(gnuais_node *nd, FormId id, const void *h, int len, const char *who,
+                      int (*run)(gnuais_batch *, const int16_t *, int, void *), int fmt = GNUAIS_FMT_CS16)
 {
     return run_all(nd, [=](Shard &s, size_t) -> int {
         Booking book(s);
         auto hip_fail = [&](const char *what) { return node_fail(GNUAIS_E_HIP, std::string(who) + ": " + what); };
-        const Form f = form(nd, s, id);
+        const Form f = form(nd, s, id, fmt);
         if (hipSetDevice(s.device) != hipSuccess) return hip_fail("hipSetDevice");
         if (!s.s_in && hipStreamCreateWithFlags(&s.s_in, hipStreamNonBlocking) != hipSuccess) return hip_fail("stream");
         const size_t row = (size_t) f.bytes * (size_t) f.nc, need = row * (size_t) f.rows * (size_t) nd->max_len;
@@ -348,7 +351,8 @@ static int run_staged(gnuais_node *nd, FormId id, const int16_t *h, int len, con
         if (hipMemcpy2DAsync(s.d_in, row, src, (size_t) f.bytes * (size_t) f.cols, row, (size_t) len, hipMemcpyHostToDevice,
                              s.s_in) != hipSuccess)
             return hip_fail("host -> device copy");
-        const int rc = run(s.b, (const int16_t *) s.d_in, len, s.s_in);
+        const int rc = run ? run(s.b, (const int16_t *) s.d_in, len, s.s_in)
+                           : gnuais_batch_run_wideband_fmt(s.b, fmt, s.d_in, len, s.s_in);
         // the caller's buffer is borrowed for the call only (src/ais.c:216 reuses it): the copy out of it must be done
         if (hipStreamSynchronize(s.s_in) != hipSuccess && rc == GNUAIS_OK) return hip_fail("copy");
         return rc;
@@ -418,6 +422,18 @@ int gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int le
         return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: len must be a positive multiple of the decimation, at most "
                                        "decim * max_len");
     return run_staged(nd, WIDE, h_wide, len, "node_run_wideband_host", gnuais_batch_run_wideband);
+}
+
+int gnuais_node_run_wideband_fmt_host(gnuais_node *nd, int fmt, const void *h_wide, int len)
+{
+    if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: NULL argument");
+    if (gnuais_sample_format_bytes(fmt) < 0)
+        return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: unknown sample format (GNUAIS_FMT_*)");
+    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: no channeliser configured (gnuais_node_channeliser)");
+    if (len <= 0 || len % nd->ch_D || len / nd->ch_D > nd->max_len)
+        return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: len must be a positive multiple of the decimation, at "
+                                       "most decim * max_len");
+    return run_staged(nd, WIDE, h_wide, len, "node_run_wideband_fmt_host", nullptr, fmt);
 }
 
 int gnuais_node_sync(gnuais_node *nd)

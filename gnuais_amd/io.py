@@ -7,11 +7,15 @@ read_raw()  what the reference itself does with a sound file (src/ais.c:173-182,
 read_wav()  a proper RIFF/WAVE reader: 16-bit PCM (plain or WAVE_FORMAT_EXTENSIBLE), any number of
             channels, unknown chunks skipped, odd chunk sizes padded, truncated data tolerated.
 planar()    [channels][frames] (one file or array per channel) -> interleaved.
+read_iq_raw()  a bare SDR capture of (I, Q) pairs in one of the wideband sample formats (cu8, cs8, cs16, cf32:
+            GNUAIS_FMT_* in include/gnuais_hip.h), in its native dtype; format_of_path() names the format an
+            extension stands for.
 chunks()    the reference's read loop: 1020 frames per receiver_run() call.
 SampleFile  the same two readers on the C boundary (gnuais_wav_*, gnuais_amd/csrc/wavio.c), streaming.
 """
 from __future__ import annotations
 
+import os
 import struct
 from typing import Iterator, Sequence, Tuple
 
@@ -65,6 +69,30 @@ def write_wav(path: str, rate: int, x: np.ndarray) -> None:
         f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, ch, rate, rate * 2 * ch, 2 * ch, 16))
         f.write(b"data" + struct.pack("<I", n))
         f.write(x.tobytes())
+
+
+# the customary extensions of bare I/Q captures (rtl_sdr: .cu8, hackrf_transfer: .cs8, GNU Radio file sinks: .cfile)
+IQ_EXTENSIONS = {".cu8": "cu8", ".u8": "cu8", ".cs8": "cs8", ".s8": "cs8", ".cs16": "cs16", ".s16": "cs16",
+                 ".cf32": "cf32", ".f32": "cf32", ".cfile": "cf32"}
+IQ_DTYPES = {"cu8": np.dtype("u1"), "cs8": np.dtype("i1"), "cs16": np.dtype("<i2"), "cf32": np.dtype("<f4")}
+
+
+def format_of_path(path: str) -> str:
+    """the sample format a capture file's extension names ("cu8", "cs8", "cs16", "cf32"); ValueError for any other"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext not in IQ_EXTENSIONS:
+        raise ValueError(f"{path}: the extension names no sample format (known: {' '.join(sorted(IQ_EXTENSIONS))})")
+    return IQ_EXTENSIONS[ext]
+
+
+def read_iq_raw(path: str, fmt: str, n_streams: int = 1) -> np.ndarray:
+    """A bare capture of interleaved (I, Q) pairs of n_streams wide streams -> [len][n_streams][2] in the format's own
+    dtype (uint8, int8, int16, float32): nothing is converted.  A partial trailing row is dropped."""
+    if fmt not in IQ_DTYPES:
+        raise ValueError(f"fmt must be one of {sorted(IQ_DTYPES)}, not {fmt!r}")
+    data = np.fromfile(path, dtype=IQ_DTYPES[fmt])
+    rows = data.size // (2 * n_streams)
+    return np.ascontiguousarray(data[: rows * 2 * n_streams].reshape(rows, n_streams, 2))
 
 
 def planar(channels: Sequence[np.ndarray]) -> np.ndarray:

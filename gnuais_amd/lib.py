@@ -24,6 +24,11 @@ FSM_DTYPE = np.dtype([("state", "<i4"), ("nstartsign", "<i4"), ("antallpreamble"
                       ("bufferpos", "<i4")])
 assert FRAME_DTYPE.itemsize == 64
 
+# sample formats of wideband input (GNUAIS_FMT_* in include/gnuais_hip.h): value, and the dtype of an [len][M][2] array
+FMT_CS16, FMT_CU8, FMT_CS8, FMT_CF32 = 0, 1, 2, 3
+FORMATS = {"cs16": (FMT_CS16, np.dtype("<i2")), "cu8": (FMT_CU8, np.dtype("u1")), "cs8": (FMT_CS8, np.dtype("i1")),
+           "cf32": (FMT_CF32, np.dtype("<f4"))}
+
 # every symbol include/gnuais_hip.h declares: (restype, argtypes)
 _P, _I, _U = C.c_void_p, C.c_int, C.c_uint
 SYMBOLS = {
@@ -43,6 +48,11 @@ SYMBOLS = {
     "gnuais_batch_run_wideband": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_wideband_host": (_I, [_P, _P, _I]),
     "gnuais_batch_channelise": (_I, [_P, _P, _I, _P, _P]),
+    "gnuais_batch_run_wideband_fmt": (_I, [_P, _I, _P, _I, _P]),
+    "gnuais_batch_run_wideband_fmt_host": (_I, [_P, _I, _P, _I]),
+    "gnuais_batch_channelise_fmt": (_I, [_P, _I, _P, _I, _P, _P]),
+    "gnuais_sample_format_bytes": (_I, [_I]),
+    "gnuais_convert_samples": (_I, [_I, _P, C.c_size_t, _P]),
     "gnuais_channeliser_default_taps": (_I, [_I, _P, _I, C.POINTER(_I)]),
     "gnuais_channeliser_mixer_table": (_I, [_I, _I, _P, _I, C.POINTER(_I)]),
     "gnuais_wav_open": (_I, [C.POINTER(_P), C.c_char_p, _I]),
@@ -110,6 +120,7 @@ SYMBOLS = {
     "gnuais_node_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_node_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gnuais_node_run_wideband_host": (_I, [_P, _P, _I]),
+    "gnuais_node_run_wideband_fmt_host": (_I, [_P, _I, _P, _I]),
     "gnuais_node_afc": (_I, [_P, _I]),
     "gnuais_node_sync": (_I, [_P]),
     "gnuais_node_pending_frames": (_I, [_P, C.POINTER(_I)]),

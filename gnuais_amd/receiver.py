@@ -148,20 +148,73 @@ class ReceiverBatch:
         d, k = self._chan
         return x.ndim == 3 and x.shape[1] * k == self.n_channels and x.shape[2] == 2 and n_rows % d == 0
 
-    def run_wideband(self, samples, stream: Optional[int] = None, sync: bool = True):
+    def _wide_native(self, samples, fmt):
+        """The wide samples of sample format `fmt` ("cs16", "cu8", "cs8", "cf32": GNUAIS_FMT_* in include/gnuais_hip.h) as
+        they go to the library, [len][M][2] in the format's own dtype -> (format value, array or tensor).  The dtype
+        must already be the format's (int16, uint8, int8, float32; for cf32 also complex64 [len][M]): TypeError
+        otherwise, nothing is cast."""
+        if fmt not in _lib.FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(_lib.FORMATS)}, not {fmt!r}")
+        value, dtype = _lib.FORMATS[fmt]
+        if _is_torch(samples):
+            import torch
+            want = {"cs16": torch.int16, "cu8": torch.uint8, "cs8": torch.int8, "cf32": torch.float32}[fmt]
+            if fmt == "cf32" and samples.dtype == torch.complex64:
+                samples = torch.view_as_real(samples)
+            if samples.dtype != want:
+                raise TypeError(f"fmt={fmt!r} takes {want} samples, not {samples.dtype}")
+            assert samples.is_cuda and samples.is_contiguous()
+        else:
+            if not isinstance(samples, np.ndarray):
+                raise TypeError(f"fmt={fmt!r} takes a numpy array or a torch tensor of the format's dtype")
+            if fmt == "cf32" and samples.dtype == np.complex64:
+                samples = np.ascontiguousarray(samples).view(np.float32).reshape(samples.shape + (2,))
+            if samples.dtype != dtype:
+                raise TypeError(f"fmt={fmt!r} takes {dtype} samples, not {samples.dtype}")
+            samples = np.ascontiguousarray(samples)
+        assert self._wide_shape_ok(samples, int(samples.shape[0]))
+        return value, samples
+
+    def run_wideband(self, samples, stream: Optional[int] = None, sync: bool = True, fmt: Optional[str] = None):
         """Wideband in (gnuais_batch_run_wideband): samples int16 [len][n_channels / K][2] = (I, Q) of the wide streams,
         len a multiple of the decimation; channeliser, discriminator and chain on the device.  A CUDA/HIP torch tensor is
         used in place, asynchronously on `stream` or torch's current stream; a numpy array goes through
-        gnuais_batch_run_wideband_host (copy, run, sync)."""
-        self._run(samples, stream, sync, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
-                  self._lib.gnuais_batch_run_wideband, self._lib.gnuais_batch_run_wideband_host)
+        gnuais_batch_run_wideband_host (copy, run, sync).
+        fmt: the samples' format as an SDR wrote it, "cs16", "cu8", "cs8" or "cf32" (gnuais_batch_run_wideband_fmt; the
+        dtypes are in _wide_native): converted on the device where the channeliser loads them, a numpy array crosses
+        the bus in its native bytes.  Calls of different formats may follow each other."""
+        if fmt is None:
+            return self._run(samples, stream, sync, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
+                             self._lib.gnuais_batch_run_wideband, self._lib.gnuais_batch_run_wideband_host)
+        value, x = self._wide_native(samples, fmt)
+        if _is_torch(x):
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(x.device).cuda_stream
+            check(self._lib.gnuais_batch_run_wideband_fmt(self._h, value, x.data_ptr(), int(x.shape[0]), C.c_void_p(stream)))
+            if sync:
+                self.sync()
+        else:
+            check(self._lib.gnuais_batch_run_wideband_fmt_host(self._h, value, x.ctypes.data, int(x.shape[0])))
 
-    def channelise(self, samples):
+    def channelise(self, samples, fmt: Optional[str] = None):
         """The channeliser alone (gnuais_batch_channelise): int16 [len][n_channels / K][2] -> torch int16
-        [len / D][n_channels][2] on the device; advances the channeliser's state and nothing else."""
+        [len / D][n_channels][2] on the device; advances the channeliser's state and nothing else.  fmt: as
+        run_wideband (gnuais_batch_channelise_fmt)."""
         d = getattr(self, "_chan", (1, 1))[0]
-        return self._stage(samples, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
-                           lambda n: (n // d, self.n_channels, 2), self._lib.gnuais_batch_channelise)
+        if fmt is None:
+            return self._stage(samples, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
+                               lambda n: (n // d, self.n_channels, 2), self._lib.gnuais_batch_channelise)
+        import torch
+        value, x = self._wide_native(samples, fmt)
+        if not _is_torch(x):
+            x = torch.from_numpy(x).to(f"cuda:{self.device}")
+        out = torch.empty((int(x.shape[0]) // d, self.n_channels, 2), dtype=torch.int16, device=x.device)
+        stream = torch.cuda.current_stream(x.device)
+        check(self._lib.gnuais_batch_channelise_fmt(self._h, value, x.data_ptr(), int(x.shape[0]), out.data_ptr(),
+                                                    C.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        return out
 
     def run_host_async(self, samples: np.ndarray):
         """Host input without waiting for the device: pinned double-buffered staging inside the

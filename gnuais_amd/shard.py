@@ -93,6 +93,18 @@ class ReceiverNode:
         self._run_host(samples, lambda x: x.ndim == 3 and x.shape[1] * k == self.n_channels and x.shape[2] == 2,
                        self._lib.gnuais_node_run_wideband_host)
 
+    def run_wideband_fmt_host(self, samples, fmt: str):
+        """Wideband in from an SDR's own sample format (gnuais_node_run_wideband_fmt_host): one host array
+        [len][n_channels / K][2] in the dtype of fmt ("cs16", "cu8", "cs8", "cf32"), split and copied in its native bytes."""
+        from . import lib as _lib
+        value, dtype = _lib.FORMATS[fmt]
+        if not isinstance(samples, self._np.ndarray) or samples.dtype != dtype:
+            raise TypeError(f"fmt={fmt!r} takes a numpy array of {dtype}")
+        x = self._np.ascontiguousarray(samples)
+        k = getattr(self, "_chan_k", 1)
+        assert x.ndim == 3 and x.shape[1] * k == self.n_channels and x.shape[2] == 2
+        self._raise(self._lib.gnuais_node_run_wideband_fmt_host(self._h, value, x.ctypes.data, int(x.shape[0])))
+
     def _run_host(self, samples, shape_ok, fn):
         """run_host / run_iq_host / run_wideband_host: `fn` on one host array"""
         x = self._np.ascontiguousarray(samples, dtype=self._np.int16)

@@ -207,6 +207,37 @@ int  gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, in
 int  gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps);
 int  gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period);
 
+/* ---- sample formats of wideband input: 8-bit and float SDR captures, converted where the channeliser loads them ----
+ * Not in the reference.  A sample format says how one wide (I, Q) pair lies in memory and how each of its components
+ * becomes the int16 v of the channeliser's definition above:
+ *   GNUAIS_FMT_CS16  two little-endian int16 x     v = x: the input of the entries above
+ *   GNUAIS_FMT_CU8   two uint8 u (RTL-SDR)         v = 256*u - 32640 = (2u - 255) * 128: zero at 127.5, range +-32640;
+ *                                                  on the 16-bit word, (u << 8) ^ 0x8080
+ *   GNUAIS_FMT_CS8   two int8 s (HackRF)           v = 256*s, range -32768 .. 32512
+ *   GNUAIS_FMT_CF32  two little-endian IEEE fp32 x, full scale +-1.0 (GNU Radio, gqrx, SoapySDR):
+ *                                                  y = x * 32768.0f (one fp32 product); r = rint(y), ties to even;
+ *                                                  NaN -> 0; v = clamp(r, -32768, 32767), which covers +-inf
+ * Everything after the conversion is the channeliser's definition, unchanged, on the converted pairs.  (The 8-bit formats
+ * are scaled to full range because the mixer rounds with >> 15: unscaled 8-bit values would vanish in its rounding.)
+ * The carry holds converted int16 pairs, so the format is an argument of each call and not a state of the batch: calls of
+ * different formats may follow each other on one batch, mixed with cs16, audio and I/Q calls, and the output depends
+ * only on the sequence of converted samples -- not on where the stream was cut or on which format carried which part.
+ * The input pointer must be aligned to 4 bytes for cs16 and cf32 and to 2 bytes for cu8 and cs8 (else GNUAIS_E_ARG,
+ * with a message that names the format); an unknown format is GNUAIS_E_ARG.  len: as above, a positive multiple of D, at
+ * most D*max_len.  The entries below are the entries above with the format as an argument (GNUAIS_FMT_CS16 launches
+ * exactly what they launch); the _host forms copy the native bytes, len * M * gnuais_sample_format_bytes(fmt). */
+#define GNUAIS_FMT_CS16 0
+#define GNUAIS_FMT_CU8  1
+#define GNUAIS_FMT_CS8  2
+#define GNUAIS_FMT_CF32 3
+int  gnuais_batch_run_wideband_fmt(gnuais_batch *b, int fmt, const void *d_wide, int len, void *stream);
+int  gnuais_batch_run_wideband_fmt_host(gnuais_batch *b, int fmt, const void *h_wide, int len);
+int  gnuais_batch_channelise_fmt(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, void *stream);
+/* bytes per (I, Q) pair: 4, 2, 2, 8; GNUAIS_E_ARG for an unknown format */
+int  gnuais_sample_format_bytes(int fmt);
+/* host only, no batch: the table above, in[n_pairs] pairs of `fmt` (any alignment) -> out[n_pairs][2] */
+int  gnuais_convert_samples(int fmt, const void *in, size_t n_pairs, int16_t *out);
+
 /* ---- carrier frequency error of I/Q input: an AFC stage on the device between the discriminator and the chain ----
  * Not in the reference (a sound card is AC coupled).  A carrier error of f Hz adds the constant f * 65536 / rate to
  * every discriminator output; an SDR's oscillator is off by several kHz at 162 MHz, more than the AIS deviation, and
@@ -528,6 +559,8 @@ int  gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const i
 /* one HOST buffer int16 [len][N/K][2] of wide streams; every shard copies the columns of its own streams,
  * [first/K, (first+n)/K), and runs channeliser, discriminator and chain; returns when the buffer may be reused */
 int  gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len);
+/* the same on wide samples of format fmt (GNUAIS_FMT_*), split and copied in their native bytes */
+int  gnuais_node_run_wideband_fmt_host(gnuais_node *nd, int fmt, const void *h_wide, int len);
 /* gnuais_batch_afc() on every shard */
 int  gnuais_node_afc(gnuais_node *nd, int window);
 int  gnuais_node_sync(gnuais_node *nd);

@@ -6,6 +6,11 @@
   python scripts/decode_file.py sdr.wav --wideband 6 --offsets -25000,25000
                                                       # wide I/Q (2M channels = M streams) at R = 6 x 48 kHz, each
                                                       # stream channelised on the device to one receiver per offset
+  python scripts/decode_file.py rtl.cu8 --wideband 6 --rate 288000 [--format cu8|cs8|cs16|cf32] [--streams M]
+                                                      # a bare SDR capture (rtl_sdr: .cu8, hackrf_transfer: .cs8, GNU Radio:
+                                                      # .cf32 / .cfile, int16: .cs16): the format defaults to the one the
+                                                      # extension names; the file goes to the device in its native format and
+                                                      # is converted where the channeliser loads it
   python scripts/decode_file.py iq.wav --iq --afc 2048
                                                       # --iq / --wideband: remove each receiver's carrier error on the device
                                                       # (an SDR's oscillator), estimated over a window of that many samples;
@@ -29,6 +34,10 @@ def main():
                          "decimate by D on the device, one receiver per stream and offset (receiver s*K + k)")
     ap.add_argument("--offsets", default="-25000,25000", help="--wideband: offsets in Hz from the tuned frequency")
     ap.add_argument("--rate", type=int, default=0, help="--wideband with --raw: the input rate in Hz")
+    ap.add_argument("--format", choices=["cu8", "cs8", "cs16", "cf32"], default=None,
+                    help="--wideband: the file is a bare capture of (I, Q) pairs in this sample format (default: the one its "
+                         "extension names: .cu8 .cs8 .cs16 .cf32, .u8 .s8 .s16 .f32 .cfile); needs --rate")
+    ap.add_argument("--streams", type=int, default=1, metavar="M", help="--format: wide streams interleaved in the file")
     ap.add_argument("--afc", type=int, default=0, metavar="W",
                     help="--iq / --wideband: carrier-error correction over a window of W samples (a multiple of 128; "
                          "2048 suits 48 kHz), 0 = off")
@@ -36,6 +45,13 @@ def main():
     a = ap.parse_args()
     import torch
     from gnuais_amd import ReceiverBatch, io, messages_from_frames
+    fmt = a.format
+    if a.wideband and not a.raw and fmt is None and os.path.splitext(a.path)[1].lower() in io.IQ_EXTENSIONS:
+        fmt = io.format_of_path(a.path)
+    if fmt and not a.wideband:
+        sys.exit("--format needs --wideband: the sample formats are those of wide I/Q captures")
+    if fmt:
+        return decode_wideband(a, a.rate, io.read_iq_raw(a.path, fmt, a.streams), fmt)
     if a.raw:
         rate, x = a.rate, io.read_raw(a.path, a.raw)
     else:
@@ -69,9 +85,11 @@ def main():
     afc_report(a, b, 48000)
 
 
-def afc_flush(x, rows):
-    """The AFC delays the audio by half its window: that many zero pairs push the end of the file through the chain."""
-    return np.concatenate([x, np.zeros((rows,) + x.shape[1:], dtype=x.dtype)])
+def afc_flush(x, rows, fmt=None):
+    """The AFC delays the audio by half its window: that many zero pairs push the end of the file through the chain.
+    A format's zero is 0 for cs16, cs8 and cf32; no cu8 byte converts to 0 (zero lies at 127.5), so cu8 is flushed with
+    128, which converts to +128: a constant, like zero, and 0.4 % of full scale."""
+    return np.concatenate([x, np.full((rows,) + x.shape[1:], 128 if fmt == "cu8" else 0, dtype=x.dtype)])
 
 
 def afc_report(a, b, rate):
@@ -80,26 +98,27 @@ def afc_report(a, b, rate):
         sys.stderr.write("carrier error at the end of the file, Hz per receiver: " + " ".join(f"{v:+.0f}" for v in hz) + "\n")
 
 
-def decode_wideband(a, rate, x):
+def decode_wideband(a, rate, x, fmt=None):
+    """x: int16 [len][2M] from a WAV or int16 file, or (fmt given) [len][M][2] in the format's own dtype"""
     import torch
     from gnuais_amd import ReceiverBatch, io, messages_from_frames
     D = a.wideband
     offsets = [int(v) for v in a.offsets.split(",") if v.strip()]
-    if x.shape[1] % 2:
+    if fmt is None and x.shape[1] % 2:
         sys.exit(f"{a.path}: --wideband needs an even channel count (I, Q per stream), the file has {x.shape[1]}")
     if rate <= 0 or rate % D or rate // D != 48000:
         sys.exit(f"{a.path}: input rate {rate} Hz / {D} is not the chain's 48000 Hz (--rate for raw files)")
-    M = x.shape[1] // 2
+    M = x.shape[1] if fmt else x.shape[1] // 2
     n_ch = M * len(offsets)
     x = x[: x.shape[0] // D * D].reshape(-1, M, 2)
     b = ReceiverBatch(n_ch, max_len=a.call)
     b.channeliser(D, rate, offsets)
     if a.afc:
         b.afc(a.afc)
-        x = afc_flush(x, a.afc // 2 * D)
+        x = afc_flush(x, a.afc // 2 * D, fmt)
     seq = np.zeros(n_ch, dtype=np.uint8)
     for part in io.chunks(x, a.call * D):
-        b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda())
+        b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
         nmea, text = messages_from_frames(b.drain_frames(), seq)
         sys.stdout.write((text if a.text else nmea).decode("ascii", "replace"))
     c = b.counters()

@@ -10,6 +10,11 @@
   python scripts/time_wideband.py --summarise STATS.csv --shape W3
                                                   the kernel's mean time from a rocprofv3 stats file -> TB/s and the
                                                   share of the byte and issue bounds
+  ... --format cu8|cs8|cf32                       the same legs, --kernel-only and --summarise on wide samples of that format
+                                                  (the int16 streams quantised to it), converted where the kernel loads them
+  python scripts/time_wideband.py --shape W2 --host-path [--streams M]
+                                                  run_wideband_fmt_host on cu8 against run_wideband_host on the same samples
+                                                  widened to int16, alternating legs: ms per call and GB/s over the bus
 """
 import argparse
 import csv
@@ -23,16 +28,21 @@ import numpy as np
 
 SHAPES = {"W3": (8192, 2, 6, 288000), "W2": (128, 2, 6, 288000)}
 OFFSETS = [-25000, 25000]
+PAIR_BYTES = {"cs16": 4, "cu8": 2, "cs8": 2, "cf32": 8}
 PEAK_TBS = 8.0
 LANE_OPS_PER_S = 256 * 4 * 16 * 2.4e9    # as scripts/time_iq.py
 
 
-def valu_per_row(K, D, NA=17):
+CONVERT_VALU = {"cs16": 0, "cs8": 1, "cu8": 2, "cf32": 14}     # lane instructions per wide sample to convert it (ISA)
+
+
+def valu_per_row(K, D, NA=17, fmt="cs16"):
     """lane instructions per output row per stream in the fast form's loop (counted from its structure): per pair of wide
     samples, 2 loads' address math aside, K * (2 mixes of ~9 + 2 packs) and 2 * K * NA v_dot2c; per row, K * 2 * NA
-    accumulator moves and the K rounded stores"""
+    accumulator moves and the K rounded stores; and the format's conversion of each of the row's D wide samples (cs8
+    one v_perm_b32, cu8 that and a v_xor_b32, cf32 six per component and two to pack)"""
     pairs = (D + 1) // 2
-    return pairs * (K * (2 * 9 + 2) + 2 * K * NA) + 2 * K * NA + 6 * K
+    return pairs * (K * (2 * 9 + 2) + 2 * K * NA) + 2 * K * NA + 6 * K + D * CONVERT_VALU[fmt]
 
 
 def device_wide(M, n, D, k=64):
@@ -50,20 +60,45 @@ def device_wide(M, n, D, k=64):
     return out
 
 
-def summarise(path, shape):
+def quantise(xd, fmt):
+    """the int16 wide samples in format fmt, round to nearest: cu8 (v + 32640) / 256, cs8 v / 256, cf32 v / 32768"""
+    import torch
+    if fmt == "cs16":
+        return xd
+    if fmt == "cf32":
+        return xd.to(torch.float32) / 32768.0
+    out = torch.empty(xd.shape, dtype=torch.uint8 if fmt == "cu8" else torch.int8, device=xd.device)
+    for lo in range(0, xd.shape[0], 8192):
+        v = xd[lo:lo + 8192].to(torch.int32)
+        if fmt == "cu8":
+            out[lo:lo + 8192] = ((v + 32640 + 128) >> 8).clamp(0, 255).to(torch.uint8)
+        else:
+            out[lo:lo + 8192] = ((v + 128) >> 8).clamp(-128, 127).to(torch.int8)
+    return out
+
+
+def fmt_name(kernel_name, fmt):
+    """whether a rocprofv3 kernel name is the fast form's kernel of format fmt"""
+    if fmt == "cs16":
+        return "channeliser_kernel" in kernel_name
+    f = {"cu8": 1, "cs8": 2, "cf32": 3}[fmt]
+    return "channeliser_fmt_kernel" in kernel_name and kernel_name.replace(" ", "").split(">")[0].endswith(f",{f}")
+
+
+def summarise(path, shape, fmt="cs16"):
     M, K, D, n = SHAPES[shape]
     rows = list(csv.DictReader(open(path)))
-    row = next(r for r in rows if "channeliser_kernel" in r.get("Name", r.get("KernelName", "")))
+    row = next(r for r in rows if fmt_name(r.get("Name", r.get("KernelName", "")), fmt))
     ms = float(row.get("AverageNs", row.get("Average", 0))) / 1e6
-    nbytes = M * n * 4 + (n // D) * M * K * 4
+    nbytes = M * n * PAIR_BYTES[fmt] + (n // D) * M * K * 4
     t_bytes = nbytes / (PEAK_TBS * 1e12) * 1e3
-    t_valu = M * (n // D) * valu_per_row(K, D) / LANE_OPS_PER_S * 1e3
-    return dict(shape=shape, kernel=row.get("Name", row.get("KernelName")), calls=int(row.get("Calls", 0)),
+    t_valu = M * (n // D) * valu_per_row(K, D, fmt=fmt) / LANE_OPS_PER_S * 1e3
+    return dict(shape=shape, format=fmt, kernel=row.get("Name", row.get("KernelName")), calls=int(row.get("Calls", 0)),
                 kernel_ms=round(ms, 4), min_ms=round(float(row.get("MinNs", 0)) / 1e6, 4),
                 max_ms=round(float(row.get("MaxNs", 0)) / 1e6, 4), bytes_per_call=nbytes,
                 tb_per_s=round(nbytes / (ms / 1e3) / 1e12, 3), bound_bytes_ms=round(t_bytes, 3),
                 bound_valu_issue_ms=round(t_valu, 3), share_of_byte_bound=round(t_bytes / ms, 3),
-                share_of_issue_bound=round(t_valu / ms, 3), valu_per_row_per_stream=valu_per_row(K, D))
+                share_of_issue_bound=round(t_valu / ms, 3), valu_per_row_per_stream=valu_per_row(K, D, fmt=fmt))
 
 
 def main():
@@ -73,54 +108,112 @@ def main():
     ap.add_argument("--legs", type=int, default=3, help="alternating run_wideband / run_iq / run leg triples")
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--summarise", metavar="STATS_CSV")
+    ap.add_argument("--format", choices=sorted(PAIR_BYTES) + ["all"], default="cs16",
+                    help="the wide samples' format; all (--kernel-only): the four formats in turn, call by call, so that "
+                         "one profiler run holds them side by side on one box and clock")
+    ap.add_argument("--host-path", action="store_true", help="cu8 in native bytes against the same widened to int16")
+    ap.add_argument("--streams", type=int, default=0, help="--host-path: streams instead of the shape's")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.summarise:
-        res = summarise(a.summarise, a.shape)
+        res = summarise(a.summarise, a.shape, a.format)
     else:
         import torch
         from gnuais_amd import ReceiverBatch
         assert torch.cuda.is_available(), "time_wideband.py measures on the GPU"
         M, K, D, n = SHAPES[a.shape]
         N, rows = M * K, n // D
-        xd = device_wide(M, n, D)
+        if a.host_path:
+            return host_path(a)
+        fmt = None if a.format == "cs16" else a.format      # None: the entries without a format
+        if a.format == "all":
+            assert a.kernel_only, "--format all is for --kernel-only"
+            x16 = device_wide(M, n, D)
+            xs = [(None, x16)] + [(f, quantise(x16, f)) for f in ("cu8", "cs8", "cf32")]
+            w = ReceiverBatch(N, max_len=rows)
+            w.channeliser(D, 48000 * D, OFFSETS)
+            for _ in range(a.calls):
+                for f, x in xs:
+                    w.channelise(x, fmt=f)
+            torch.cuda.synchronize()
+            print(f"{a.calls} channeliser calls of each format in turn at {a.shape}")
+            return
+        xd = quantise(device_wide(M, n, D), a.format)
         w = ReceiverBatch(N, max_len=rows)
         w.channeliser(D, 48000 * D, OFFSETS)
         if a.kernel_only:
             for _ in range(a.calls):
-                w.channelise(xd)
+                w.channelise(xd, fmt=fmt)
             torch.cuda.synchronize()
-            print(f"{a.calls} channeliser calls at {a.shape}")
+            print(f"{a.calls} channeliser calls at {a.shape}, {a.format}")
             return
-        iq = w.channelise(xd)
+        iq = w.channelise(xd, fmt=fmt)
         w.reset()
         q = ReceiverBatch(N, max_len=rows)
         audio = q.discriminate(iq)
         q.reset()
         r = ReceiverBatch(N, max_len=rows)
 
-        def leg(batch, fn, x):
+        def leg(batch, fn, x, **kw):
             for _ in range(2):                       # warm-up
-                fn(x, sync=False)
+                fn(x, sync=False, **kw)
                 batch.discard_frames()
             batch.sync()
             t0 = time.perf_counter()
             for _ in range(a.calls):
-                fn(x, sync=False)
+                fn(x, sync=False, **kw)
                 batch.discard_frames()
             batch.sync()
             return (time.perf_counter() - t0) * 1e3 / a.calls
 
         wb, iqm, au = [], [], []
         for _ in range(a.legs):
-            wb.append(leg(w, w.run_wideband, xd))
+            wb.append(leg(w, w.run_wideband, xd, **({"fmt": fmt} if fmt else {})))
             iqm.append(leg(q, q.run_iq, iq))
             au.append(leg(r, r.run, audio))
         med = lambda v: round(float(np.median(v)), 4)
-        res = dict(shape=a.shape, streams=M, offsets=K, decim=D, wide_samples=n, receivers=N, rows=rows,
+        res = dict(shape=a.shape, format=a.format, streams=M, offsets=K, decim=D, wide_samples=n, receivers=N, rows=rows,
                    calls_per_leg=a.calls, run_wideband_ms=[round(v, 4) for v in wb], run_iq_ms=[round(v, 4) for v in iqm],
                    run_ms=[round(v, 4) for v in au], run_wideband_median_ms=med(wb), run_iq_median_ms=med(iqm),
                    run_median_ms=med(au), added_over_run_iq_ms=round(med(wb) - med(iqm), 4))
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+def host_path(a):
+    """run_wideband_fmt_host on cu8 against run_wideband_host on the same samples widened to int16 on the host"""
+    import torch
+    from gnuais_amd import ReceiverBatch
+    M, K, D, n = SHAPES[a.shape]
+    M = a.streams or M
+    u8 = quantise(device_wide(M, n, D), "cu8").cpu().numpy()
+    wide = ((u8.astype(np.int32) << 8) - 32640).astype(np.int16)
+    b = ReceiverBatch(M * K, max_len=n // D)
+    b.channeliser(D, 48000 * D, OFFSETS)
+
+    def leg(x, fmt):
+        b.run_wideband(x, fmt=fmt)                   # warm-up: staging allocation
+        b.discard_frames()
+        t0 = time.perf_counter()
+        for _ in range(a.calls):
+            b.run_wideband(x, fmt=fmt)
+            b.discard_frames()
+        return (time.perf_counter() - t0) * 1e3 / a.calls
+
+    t8, t16 = [], []
+    for _ in range(a.legs):
+        t8.append(leg(u8, "cu8"))
+        t16.append(leg(wide, None))
+    med = lambda v: float(np.median(v))
+    res = dict(shape=f"{a.shape}/{M}" if a.streams else a.shape, streams=M, wide_samples=n, calls_per_leg=a.calls, cu8_ms=[round(v, 3) for v in t8],
+               cs16_widened_ms=[round(v, 3) for v in t16], cu8_median_ms=round(med(t8), 3),
+               cs16_widened_median_ms=round(med(t16), 3), cu8_bytes=int(u8.nbytes), cs16_bytes=int(wide.nbytes),
+               cu8_gb_per_s_whole_call=round(u8.nbytes / med(t8) / 1e6, 2),
+               cs16_gb_per_s_whole_call=round(wide.nbytes / med(t16) / 1e6, 2))
     line = json.dumps(res)
     print(line)
     if a.out:
