@@ -178,6 +178,14 @@ struct gnuais_batch {
     Buf<uint2> ring_chunks[NRING];              // K3's chunk table per ring (kernels.h: HdlcLaunch::chunks)
     int ring_runs[NRING] = {};                  // K3 launches into the ring since it became current
     int n_chunks = 0;
+    // The receive time of every frame (gnuais_batch_frame_times, frame_time.hip; off by default).  `rows` counts the rows
+    // the chain has taken since create / reset, over every kind of run call, whether the feature is on or not; while it
+    // is on, one more launch behind each K3 writes times[slot] for the records that K3 appended to ring 0 (a batch with
+    // the feature on does not stream).  The kernel finds its records by their end_bit, so there is no state here that
+    // the drains, discard_frames or the resets would have to clear.
+    bool frame_times = false;
+    unsigned long long rows = 0;
+    Buf<int64_t> times;                         // [frame_cap], allocated when the feature is first switched on
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)

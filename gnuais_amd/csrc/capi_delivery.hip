@@ -64,8 +64,10 @@ static int upload_seq(gnuais_batch *b, const uint8_t *seqnr)
 }
 
 // drain: records and / or sentences of everything queued, consumed once
+// h_times (with h_frames): the records' receive times, through the sort's own permutation
 static int drain_impl(gnuais_batch *b, gnuais_frame *h_frames, int max_frames, int *n_frames,
-                      uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len, int *n_sentences)
+                      uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len, int *n_sentences,
+                      int64_t *h_times = nullptr)
 {
     // a streaming batch spreads its frames over NRING rings that gnuais_batch_stream_nmea() consumes: ring 0 alone
     // would be a partial view, and clearing its counters would lose frames and error flags
@@ -98,9 +100,13 @@ static int drain_impl(gnuais_batch *b, gnuais_frame *h_frames, int max_frames, i
             // K3 appends the frames in pieces, in whatever order its blocks finish; the reference's
             // print order (channel, then time) is restored on the device -- radix sort of
             // (channel, end_bit), gather -- and the records cross PCIe once, straight into h_frames
+            // (the text buffer holds 164 bytes per frame: the 64 of a record and the 8 of its time fit side by side)
             gnuais_frame *sorted = reinterpret_cast<gnuais_frame *>(b->d_text.p);
-            HIP_TRY(frames_sort(b->ring[0], (int) have, sorted, b->nmea_scratch, b->nmea_scratch.bytes, nullptr));
+            int64_t *sorted_t = reinterpret_cast<int64_t *>(sorted + have);
+            HIP_TRY(frames_sort_timed(b->ring[0], h_times ? b->times.p : nullptr, (int) have, sorted, sorted_t,
+                                      b->nmea_scratch, b->nmea_scratch.bytes, nullptr));
             HIP_TRY(hipMemcpy(h_frames, sorted, sizeof(gnuais_frame) * have, hipMemcpyDeviceToHost));
+            if (h_times) HIP_TRY(hipMemcpy(h_times, sorted_t, sizeof(int64_t) * have, hipMemcpyDeviceToHost));
         }
         if (n_frames) *n_frames = (int) have;
     }
@@ -251,6 +257,17 @@ int gnuais_batch_drain_frames(gnuais_batch *b, gnuais_frame *h_out, int max, int
     return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr);
 }
 
+// the records and, entry for entry, their receive times (gnuais_batch_frame_times)
+int gnuais_batch_drain_frames_timed(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out)
+{
+    if (!b || !n_out || (max > 0 && (!h_out || !h_times))) return fail(GNUAIS_E_ARG, "drain_frames_timed: argument");
+    *n_out = 0;
+    if (!b->frame_times) return fail(GNUAIS_E_STATE, "drain_frames_timed: the batch does not time its frames (gnuais_batch_frame_times)");
+    static gnuais_frame none;
+    static int64_t none_t;
+    return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr, h_times ? h_times : &none_t);
+}
+
 int gnuais_batch_drain_nmea(gnuais_batch *b, uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len,
                             int *n_sentences, int *n_frames)
 {
@@ -279,6 +296,8 @@ static int stream_setup(gnuais_batch *b)
     constexpr int NR = gnuais_batch::NRING;
     const size_t N = (size_t) b->N;
     const size_t text_cap = (size_t) b->frame_cap * 164;        // a full ring of two-sentence frames
+    if (b->frame_times) return fail(GNUAIS_E_STATE, "stream_nmea: the batch times its frames (gnuais_batch_frame_times); "
+                                                    "the streamed delivery carries no times");
     if (int rc = gnuais_batch_sync(b)) return rc;
     // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
     // allocation) is repeated by the next call without leaking what the failed one had made

@@ -333,6 +333,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     for (int k = 0; k < b->sets_alloc; ++k)
         HIP_TRY(hipMemset(b->segcnt[k], 0, sizeof(uint32_t) * N * (size_t) b->n_seg));
     b->calls = 0;
+    b->rows = 0;
     b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
@@ -372,6 +373,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         // 0: leave the streamed delivery (gnuais_batch_stream_nmea / autotune_delivery switch it on): everything in
         // flight is flushed and DROPPED, K3 goes back to ring 0, the drain-type calls work again.  The rings, texts
         // and streams stay allocated for the next streaming call.
+        if (value != 0 && b->frame_times)
+            return fail(GNUAIS_E_STATE, "streaming: the batch times its frames (gnuais_batch_frame_times); the streamed delivery carries no times");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
         if (b->streaming) {
             if (int rc = gnuais_batch_sync(b)) return rc;
@@ -459,6 +462,17 @@ static void fill_hdlc(const gnuais_batch *b, HdlcLaunch &h, int k)
     h.chunks = (b->streaming && b->ring_runs[b->ring_cur] == 0) ? b->ring_chunks[b->ring_cur] : nullptr;
 }
 
+// the launch behind the K3 described by h: len rows from row b->rows on (len <= 0: bits without samples)
+static FrameTimeLaunch fill_frame_times(const gnuais_batch *b, const HdlcLaunch &h, int len)
+{
+    FrameTimeLaunch t;
+    t.frames = h.frames; t.frame_count = h.frame_count; t.frame_cap = h.frame_cap;
+    t.ctl = h.ctl; t.segcnt = h.segcnt; t.times = b->times;
+    t.N = h.N; t.n_seg = h.n_seg; t.seg_words = h.seg_words;
+    t.len = len; t.n0 = (int64_t) b->rows;
+    return t;
+}
+
 // K1 + carry: the kernel and its thresholds are plan_fir()'s choice (fir_plan.cpp).  The specialised kernels update
 // the history and clear the next peak buffer themselves; the generic fallback needs the two helper launches.
 static int run_fir(gnuais_batch *b, const int16_t *x, int len, float *dump, hipStream_t s, int k)
@@ -536,6 +550,9 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     if (pl && sD != sC) HIP_TRY(hipStreamWaitEvent(sD, b->e_done[3][k], 0));
     if (tm) HIP_TRY(hipEventRecord(ev[9], sD));
     if (b->stage_mask & 16) HIP_TRY(launch_hdlc_crc(h, sD));
+    // the frames' receive times: behind K3 and in front of e_done[4][k], which is what the reuse of set k (segcnt) and,
+    // where K3 has a stream of its own, the next deframer launch (ctl) wait for
+    if (b->frame_times && (b->stage_mask & 16)) HIP_TRY(launch_frame_times(fill_frame_times(b, h, len), sD));
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -594,6 +611,7 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
     b->last_len = len;
     b->last_k = k;
     b->calls++;
+    b->rows += (unsigned long long) len;
     return GNUAIS_OK;
 }
 
@@ -766,6 +784,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         fill_hdlc(b, h, 0);
         HIP_TRY(b->hdlc_variant ? launch_hdlc_events(h, nullptr) : launch_hdlc_deframe(h, nullptr));
         HIP_TRY(launch_hdlc_crc(h, nullptr));
+        if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
@@ -962,6 +981,8 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "device")) *value = b->device;
     else if (!strcmp(name, "afc_window")) *value = b->afc_W;
     else if (!strcmp(name, "segments")) *value = b->n_seg;
+    else if (!strcmp(name, "frame_times")) *value = b->frame_times;
+    else if (!strcmp(name, "rows")) *value = (double) b->rows;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now
         *value = -1;
@@ -971,6 +992,49 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "stream_depth")) *value = gnuais_batch::NRING - 1;
     else return fail(GNUAIS_E_ARG, "info: unknown name");
     return GNUAIS_OK;
+}
+
+// The frames' receive times on / off (definition in include/gnuais_hip.h).  Synchronises: no call is in flight when the
+// switch turns, so every K3 either has its timing launch behind it or has not.  What the ring holds when the feature
+// comes on was appended without one: the whole array starts at -1.
+int gnuais_batch_frame_times(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "frame_times: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "frame_times: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    if (on && !b->frame_times) {
+        HIP_TRY(b->times.ensure(sizeof(int64_t) * (size_t) b->frame_cap));
+        HIP_TRY(hipMemset(b->times, 0xff, sizeof(int64_t) * (size_t) b->frame_cap));
+    }
+    b->frame_times = on != 0;
+    return GNUAIS_OK;
+}
+
+// input sample index = t * mul + off, for the batch's configuration as it is now: the nominal decision instant
+int gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long long *off)
+{
+    if (!b || !mul || !off) return fail(GNUAIS_E_ARG, "time_map: argument");
+    const long long d_f = (b->NT + 1) / 2, half_w = b->afc_W / 2;
+    switch (kind) {
+    case GNUAIS_INPUT_AUDIO:
+        *mul = 1;
+        *off = -d_f;
+        return GNUAIS_OK;
+    case GNUAIS_INPUT_IQ:
+        *mul = 1;
+        *off = -d_f - half_w;
+        return GNUAIS_OK;
+    case GNUAIS_INPUT_WIDEBAND: {
+        if (!b->ch_K) return fail(GNUAIS_E_STATE, "time_map: no channeliser configured (gnuais_batch_channeliser)");
+        const long long D = b->ch_D, T = b->ch_T;
+        *mul = D;
+        *off = (-d_f - half_w) * D + D - 1 - (T - 1) / 2;
+        return GNUAIS_OK;
+    }
+    default:
+        return fail(GNUAIS_E_ARG, "time_map: kind must be GNUAIS_INPUT_AUDIO, _IQ or _WIDEBAND");
+    }
 }
 
 int gnuais_batch_n_channels(const gnuais_batch *b) { return b ? b->N : 0; }

@@ -110,6 +110,26 @@ hipError_t launch_hdlc_crc(const HdlcLaunch &a, hipStream_t stream);     // K3
 hipError_t launch_hdlc_reset(uint32_t *ctl, int N, hipStream_t stream);
 hipError_t launch_hdlc_fsm_reset(uint32_t *ctl, int N, hipStream_t stream);   // protodec_reset() only: counters and time stay
 
+// ---- the receive time of the frames K3 appended in one call (frame_time.hip; definition in include/gnuais_hip.h) ----
+// One launch behind that call's K3, on its stream, before the call's hand-off set (segcnt) can be reused and before
+// the next deframer launch moves ctl on.  Writes times[i] for every record i of the ring whose end_bit lies among the
+// bits this call fed; other records are left alone.  len <= 0: the call fed bits without samples
+// (gnuais_batch_decode_bits), its frames get -1.
+struct FrameTimeLaunch {
+    const void *frames;            // gnuais_frame[frame_cap]: the ring K3 appended to
+    const uint32_t *frame_count;   // its counters ([0] = frames appended)
+    uint32_t frame_cap;
+    const uint32_t *ctl;           // the deframer's control state AFTER the call ([2], [5]: bits fed since reset)
+    const uint32_t *segcnt;        // [N][n_seg] of the call's hand-off set
+    int64_t *times;                // [frame_cap], by ring slot
+    int N, n_seg, seg_words;
+    int len;                       // rows of the call
+    int64_t n0;                    // rows the chain had taken before it
+};
+hipError_t launch_frame_times(const FrameTimeLaunch &a, hipStream_t stream);
+// times[order[j]] -> out[j], j < n: the times in the order of a sorted drain (frames_sort_timed)
+hipError_t launch_frame_times_gather(const int64_t *times, const uint32_t *order, int n, int64_t *out, hipStream_t stream);
+
 // ---- utilities (util.hip) ---------------------------------------------------
 hipError_t launch_tile_channels(const int16_t *base, int n_base, int len, int16_t *out,
                                 int n_channels, hipStream_t stream);
@@ -172,6 +192,9 @@ size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);
 // frames[n] (device) -> out[n] (device) in print order: channel, then end_bit
 hipError_t frames_sort(const struct gnuais_frame *frames, int n, struct gnuais_frame *out, void *scratch,
                        size_t scratch_bytes, hipStream_t s);
+// the same, and times[n] (by ring slot, frame_time.hip) -> times_out[n] through the same permutation
+hipError_t frames_sort_timed(const struct gnuais_frame *frames, const int64_t *times, int n, struct gnuais_frame *out,
+                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s);
 // the device part only, queued without waiting; h_info4 (host, pinned): [0] + [1] bytes written,
 // [2] sentences, [3] != 0 if a frame named a channel >= n_channels -- valid once `s` has got there
 // n > 0: count known to the host, order by radix sort.  n < 0: the ring holds exactly one call; order and

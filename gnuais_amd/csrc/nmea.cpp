@@ -685,3 +685,50 @@ extern "C" int gnuais_nmea_from_frames(const gnuais_frame *frames, int n_frames,
     return gnuais_messages_from_frames(frames, n_frames, seqnr, nullptr, n_channels, out, out_cap, out_len,
                                        n_sentences, nullptr, 0, nullptr, nullptr);
 }
+
+// The same sentences, each preceded by an NMEA 4.10 TAG block that carries the frame's receive time:
+// "\c:<unix>*hh\" with <unix> = epoch_s + floor((t * mul + off) / rate_hz) and hh the XOR of the characters between the
+// backslashes up to the '*'.  A frame with t = -1 (no receive time on record) gets no tag.  The sentences themselves are
+// format_range()'s, so with the tags removed the bytes are those of gnuais_nmea_from_frames().
+extern "C" int gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *times, int n_frames, uint8_t *seqnr,
+                                              int n_channels, long long mul, long long off, long long rate_hz,
+                                              long long epoch_s, char *out, size_t out_cap, size_t *out_len,
+                                              int *n_sentences)
+{
+    if (n_frames < 0 || (n_frames > 0 && (!frames || !times)) || !seqnr || n_channels <= 0 || rate_hz <= 0 || !out_len)
+        return GNUAIS_E_ARG;
+    Sink sink{out, out_cap, 0, true};
+    int sentences = 0, lines = 0;
+    std::string nm, tx;
+    for (int k = 0; k < n_frames; ++k) {
+        nm.clear();
+        if (int rc = format_range(frames, k, k + 1, seqnr, nullptr, n_channels, true, false, nm, tx, sentences, lines))
+            return rc;
+        char tag[48];
+        size_t n_tag = 0;
+        if (times[k] >= 0) {
+            // __int128: t * mul is the caller's product, and an int64 overflow would be undefined
+            const __int128 x = (__int128) times[k] * mul + off;
+            __int128 q = x / rate_hz;
+            if (x % rate_hz < 0) --q;                   // floor, not C's truncation: a sample before the epoch second
+            const int n = snprintf(tag + 1, sizeof tag - 8, "c:%lld", (long long) (epoch_s + (long long) q));
+            unsigned char sum = 0;
+            for (int i = 1; i <= n; ++i) sum ^= (unsigned char) tag[i];
+            tag[0] = '\\';
+            tag[n + 1] = '*';
+            tag[n + 2] = HEX[sum >> 4];
+            tag[n + 3] = HEX[sum & 15];
+            tag[n + 4] = '\\';
+            n_tag = (size_t) n + 5;
+        }
+        for (size_t at = 0; at < nm.size();) {          // every sentence of the frame ends in "\r\n"
+            const size_t end = nm.find("\r\n", at) + 2;
+            sink.put(tag, n_tag);
+            sink.put(nm.data() + at, end - at);
+            at = end;
+        }
+    }
+    *out_len = sink.len;
+    if (n_sentences) *n_sentences = sentences;
+    return sink.fits ? GNUAIS_OK : GNUAIS_E_OVERFLOW;
+}

@@ -985,6 +985,14 @@ size_t nmea_scratch_bytes(int n, int n_chunks)
 hipError_t frames_sort(const gnuais_frame *frames, int n, gnuais_frame *out, void *scratch, size_t scratch_bytes,
                        hipStream_t s)
 {
+    return frames_sort_timed(frames, nullptr, n, out, nullptr, scratch, scratch_bytes, s);
+}
+
+// The timed form: the frames' receive times (by ring slot) leave through the same permutation, so that times_out[i]
+// belongs to out[i].  times == nullptr: the records only.
+hipError_t frames_sort_timed(const gnuais_frame *frames, const int64_t *times, int n, gnuais_frame *out,
+                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s)
+{
     if (n <= 0) return hipSuccess;
     if (scratch_bytes < nmea_scratch_bytes(n)) return hipErrorInvalidValue;
     const size_t m = (size_t) n;
@@ -998,7 +1006,8 @@ hipError_t frames_sort(const gnuais_frame *frames, int n, gnuais_frame *out, voi
     hipError_t e = rocprim::radix_sort_pairs(tmp, t, keys, keys2, idx, idx2, m, 0, 61, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(frames_gather_kernel, dim3((4 * n + 255) / 256), dim3(256), 0, s, frames, idx2, n, out);
-    return hipGetLastError();
+    if ((e = hipGetLastError()) != hipSuccess || !times) return e;
+    return launch_frame_times_gather(times, idx2, n, times_out, s);
 }
 
 // The slot's eight info words, kept on the device: the formatter's four (offset and length of the last

@@ -486,9 +486,30 @@ int gnuais_node_pending_frames(gnuais_node *nd, int *n_out)
     return rc;
 }
 
+int gnuais_node_frame_times(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_frame_times: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_times(s.b, on); });
+}
+
+static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
+
 int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int *n_out)
 {
     if (!nd || !h_out || !n_out || max < 0) return node_fail(GNUAIS_E_ARG, "node_drain_frames: argument");
+    return node_drain(nd, h_out, nullptr, max, n_out);
+}
+
+// the same with every record's receive time (gnuais_batch_drain_frames_timed on every shard): every shard counts the
+// rows of its own calls, and a node's run calls give every shard the same rows
+int gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out)
+{
+    if (!nd || !h_out || !h_times || !n_out || max < 0) return node_fail(GNUAIS_E_ARG, "node_drain_frames_timed: argument");
+    return node_drain(nd, h_out, h_times, max, n_out);
+}
+
+static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out)
+{
     *n_out = 0;
     int total = 0;
     if (int rc = gnuais_node_pending_frames(nd, &total)) return rc;
@@ -509,7 +530,8 @@ int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int 
     }
     const int rc = run_all(nd, [&](Shard &s, size_t i) {
         int got = 0;
-        const int r = gnuais_batch_drain_frames(s.b, h_out + off[i], cnt[i], &got);
+        const int r = h_times ? gnuais_batch_drain_frames_timed(s.b, h_out + off[i], h_times + off[i], cnt[i], &got)
+                              : gnuais_batch_drain_frames(s.b, h_out + off[i], cnt[i], &got);
         for (int k = 0; k < got; ++k) h_out[off[i] + k].channel += (uint32_t) s.first;
         cnt[i] = got;
         return r;
@@ -518,6 +540,7 @@ int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int 
     int w = 0;
     for (size_t i = 0; i < sh.size(); ++i) {
         if (off[i] != w && cnt[i] > 0) memmove(h_out + w, h_out + off[i], sizeof(gnuais_frame) * (size_t) cnt[i]);
+        if (off[i] != w && cnt[i] > 0 && h_times) memmove(h_times + w, h_times + off[i], sizeof(int64_t) * (size_t) cnt[i]);
         w += cnt[i];
     }
     *n_out = w;

@@ -24,6 +24,9 @@ FSM_DTYPE = np.dtype([("state", "<i4"), ("nstartsign", "<i4"), ("antallpreamble"
                       ("bufferpos", "<i4")])
 assert FRAME_DTYPE.itemsize == 64
 
+# kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
+INPUT_KINDS = {"audio": 0, "iq": 1, "wideband": 2}
+
 # sample formats of wideband input (GNUAIS_FMT_* in include/gnuais_hip.h): value, and the dtype of an [len][M][2] array
 FMT_CS16, FMT_CU8, FMT_CS8, FMT_CF32 = 0, 1, 2, 3
 FORMATS = {"cs16": (FMT_CS16, np.dtype("<i2")), "cu8": (FMT_CU8, np.dtype("u1")), "cs8": (FMT_CS8, np.dtype("i1")),
@@ -69,6 +72,11 @@ SYMBOLS = {
     "gnuais_batch_info": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
     "gnuais_batch_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_pending_frames": (_I, [_P, C.POINTER(_I)]),
+    "gnuais_batch_frame_times": (_I, [_P, _I]),
+    "gnuais_batch_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_time_map": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "gnuais_nmea_tagged_from_frames": (_I, [_P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
+                                            _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I)]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
     "gnuais_batch_counters": (_I, [_P, _P]),
     "gnuais_batch_total_received": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -125,6 +133,8 @@ SYMBOLS = {
     "gnuais_node_sync": (_I, [_P]),
     "gnuais_node_pending_frames": (_I, [_P, C.POINTER(_I)]),
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_frame_times": (_I, [_P, _I]),
+    "gnuais_node_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_stream_nmea": (_I, [_P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_node_discard_frames": (_I, [_P]),
     "gnuais_node_counters": (_I, [_P, _P]),

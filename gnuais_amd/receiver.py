@@ -313,6 +313,29 @@ class ReceiverBatch:
                                                   C.byref(got)))
         return out[: got.value].copy()
 
+    def frame_times(self, on: bool = True):
+        """gnuais_batch_frame_times(): from now on every frame gets its receive time in chain rows (the definition is in
+        include/gnuais_hip.h); one more small launch per call.  Synchronises.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_frame_times(self._h, int(bool(on))))
+
+    def drain_frames_timed(self):
+        """gnuais_batch_drain_frames_timed(): (frames, int64 times), times[i] the receive time of frames[i] in chain rows
+        since create / reset, -1 where there is none (decode_bits, or appended while the feature was off)."""
+        n = self.pending_frames()
+        out = np.zeros(max(n, 1), dtype=FRAME_DTYPE)
+        times = np.zeros(max(n, 1), dtype=np.int64)
+        got = C.c_int()
+        check(self._lib.gnuais_batch_drain_frames_timed(self._h, out.ctypes.data, times.ctypes.data, int(out.size),
+                                                        C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy()
+
+    def time_map(self, kind: str = "audio"):
+        """gnuais_batch_time_map(): (mul, off) with input sample index = t * mul + off for the batch's configuration as
+        it is now; kind: "audio", "iq" or "wideband"."""
+        mul, off = C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.gnuais_batch_time_map(self._h, _lib.INPUT_KINDS[kind], C.byref(mul), C.byref(off)))
+        return mul.value, off.value
+
     def drain_nmea(self, seqnr: np.ndarray):
         """The queued frames as !AIVDM sentences, formatted on the device (row f1); consumes them.
         seqnr: uint8[n_channels], updated in place.  Returns (text bytes, sentences, frames)."""
@@ -496,6 +519,26 @@ def nmea_from_frames(frames: np.ndarray, seqnr: np.ndarray) -> bytes:
     n_sent = C.c_int(0)
     check(lib.gnuais_nmea_from_frames(frames.ctypes.data, len(frames), seqnr.ctypes.data, len(seqnr),
                                       out.ctypes.data, cap, C.byref(need), C.byref(n_sent)))
+    return out[: need.value].tobytes()
+
+
+def nmea_tagged_from_frames(frames: np.ndarray, times: np.ndarray, seqnr: np.ndarray, mul: int = 1, off: int = 0,
+                            rate_hz: int = 48000, epoch_s: int = 0) -> bytes:
+    """nmea_from_frames() with a TAG block "\\c:<unix>*hh\\" in front of every sentence of a frame whose time is not -1:
+    <unix> = epoch_s + floor((times[i] * mul + off) / rate_hz).  mul / off: ReceiverBatch.time_map(); rate_hz: the rate
+    of the input samples; epoch_s: the UNIX second of input sample 0."""
+    lib = _lib.load()
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    times = np.ascontiguousarray(times, dtype=np.int64)
+    assert len(times) == len(frames)
+    assert seqnr.dtype == np.uint8 and seqnr.flags.c_contiguous
+    cap = (164 + 2 * 32) * max(1, len(frames))
+    out = np.zeros(cap, dtype=np.uint8)
+    need = C.c_size_t(0)
+    n_sent = C.c_int(0)
+    check(lib.gnuais_nmea_tagged_from_frames(frames.ctypes.data, times.ctypes.data, len(frames), seqnr.ctypes.data,
+                                             len(seqnr), int(mul), int(off), int(rate_hz), int(epoch_s), out.ctypes.data,
+                                             cap, C.byref(need), C.byref(n_sent)))
     return out[: need.value].tobytes()
 
 

@@ -204,6 +204,30 @@ class ReceiverNode:
         self._raise(self._lib.gnuais_node_drain_frames(self._h, out.ctypes.data, len(out), self._C.byref(got)))
         return out[: got.value].copy()
 
+    def frame_times(self, on: bool = True):
+        """gnuais_batch_frame_times() on every shard"""
+        self._raise(self._lib.gnuais_node_frame_times(self._h, int(bool(on))))
+
+    def drain_frames_timed(self):
+        """gnuais_node_drain_frames_timed(): (frames, int64 times), as drain_frames with every record's receive time"""
+        from .lib import FRAME_DTYPE
+        n = max(self.pending_frames(), 1)
+        out, times = self._np.zeros(n, dtype=FRAME_DTYPE), self._np.zeros(n, dtype=self._np.int64)
+        got = self._C.c_int()
+        self._raise(self._lib.gnuais_node_drain_frames_timed(self._h, out.ctypes.data, times.ctypes.data, n,
+                                                             self._C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy()
+
+    def time_map(self, kind: str = "audio"):
+        """gnuais_batch_time_map() of the first shard: every shard has the node's configuration"""
+        from .lib import INPUT_KINDS, check
+        C = self._C
+        dev, first, n, bh = C.c_int(), C.c_int(), C.c_int(), C.c_void_p()
+        self._raise(self._lib.gnuais_node_shard(self._h, 0, C.byref(dev), C.byref(first), C.byref(n), C.byref(bh)))
+        mul, off = C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.gnuais_batch_time_map(bh, INPUT_KINDS[kind], C.byref(mul), C.byref(off)))
+        return mul.value, off.value
+
     def counters(self):
         from .lib import COUNTERS_DTYPE
         out = self._np.zeros(self.n_channels, dtype=COUNTERS_DTYPE)

@@ -311,7 +311,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * the matrix-pipe FIR: table, options and channel count allow it; a call takes it when its length does too),
  * "first_effective_tap",
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
- * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off) */
+ * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
+ * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
 /* ---- results ------------------------------------------------------------------
@@ -339,6 +340,64 @@ int  gnuais_batch_frame_bits(gnuais_batch *b, int channel, uint8_t *h_bits, int 
 /* the last n_taps input samples per channel, oldest first (live part of
  * struct filter.buffer, src/filter.h:60): h_out int16 [n_channels][n_taps] */
 int  gnuais_batch_history(gnuais_batch *b, int16_t *h_out);
+
+/* ---- when a frame was received: its time in input samples ---------------------------------------------------------
+ * The reference takes time(&received_t) for every message (src/protodec.c:904-905) and hands it to its cache, its JSON
+ * output and its MySQL sink.  A batch delivers a whole call's frames in one drain, and for a recorded capture decoded
+ * faster than real time the wall clock says nothing, so the receive time is counted in the input itself.  end_bit
+ * counts bits, and the PLL free-runs on noise between bursts: end_bit / 9600 drifts from the capture's clock without
+ * bound.  Off by default: while off, a call launches exactly what it launches without this section.
+ *   n counts the rows (samples per channel at the chain's rate) the chain has taken since gnuais_batch_create() /
+ *   gnuais_batch_reset(), over every kind of run call (audio, I/Q, wideband, their host forms), whether the feature is
+ *   on or not.  gnuais_batch_protodec_reset() keeps n as it keeps the bit count.  Row i "slices" when pll > 0xffff
+ *   after the add at src/receiver.c:122-124.
+ *   A call that takes rows [n0, n0 + len) is cut into segments s = 0, 1, ...: segment s covers the rows
+ *   [n0 + 2048 s, n0 + min(2048 (s + 1), len)); l_s is its length, c_s the number of its rows that slice.
+ *   The bit with the 37-bit index e = end_bit together with flags[5:1] -- the bit that closed the frame -- is the j-th
+ *   slice (counting from 0) of some segment s of the call that fed it.  Its time is
+ *     t(e) = n0 + 2048 s + floor((2 j + 1) * l_s / (2 * c_s))                                     int64, exact
+ *   independent of which form of the PLL stage ran.  It DOES depend on where the input was cut into calls: a segment
+ *   is 2048 rows of a call, not of the stream.
+ *   A frame closed by gnuais_batch_decode_bits() (bits without samples), and a frame that was appended while the
+ *   feature was off, has t = -1.
+ * t is an interpolation inside a segment of 2048 rows, not the slicing row itself: the PLL stage hands on a count per
+ * segment and not its phase.  Measured against the true slicing row over every bit of the test inputs
+ * the error is within -3 .. +3 rows at 48 kHz (a bit is 5 rows) and -10 .. +10 at 192 kHz (a bit is 20): at most half a
+ * bit.  tests/test_frame_times_cpu.py asserts |t - slicing row| <= ceil(65536 / pllinc), one bit period, over those
+ * inputs.  That bound is a property of those inputs, not a theorem: the phase nudges of +-pllinc/16 average out on
+ * signal and on noise, but an input whose nudges all went one way inside a segment could move the slices of that
+ * segment further from an even spread.
+ * gnuais_batch_frame_times(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE on a streaming batch, and
+ *   while it is on the batch cannot start streaming (gnuais_batch_stream_nmea, gnuais_batch_autotune_delivery and
+ *   set_option("streaming", 1) return GNUAIS_E_STATE): streamed sentences carry no times.  One more small launch
+ *   follows every call's K3 while it is on.
+ * gnuais_batch_drain_frames_timed(): gnuais_batch_drain_frames() with h_times[i] = t of h_out[i].  GNUAIS_E_STATE
+ *   while the feature is off.  Every other drain keeps working while it is on (and drops the times with the frames).
+ * gnuais_batch_time_map(kind): the input sample index of chain row t is t * mul + off for the batch's configuration at
+ *   the time of the call, with d_f = (n_taps + 1) / 2 the centre of the chain FIR's window, W the AFC window (0 = off),
+ *   D and T the channeliser's decimation and tap count:
+ *     GNUAIS_INPUT_AUDIO      mul = 1,  off = -d_f
+ *     GNUAIS_INPUT_IQ         mul = 1,  off = -d_f - W/2
+ *     GNUAIS_INPUT_WIDEBAND   mul = D,  off = (-d_f - W/2) * D + D - 1 - (T - 1) / 2     (GNUAIS_E_STATE if not configured)
+ *   The offsets are the delays of the stages as constants -- the nominal decision instant -- not a calibration against
+ *   a transmitter's clock.  The index may be negative for the first rows.
+ * gnuais_batch_info "frame_times" (0 / 1) and "rows" (n). */
+#define GNUAIS_INPUT_AUDIO    0
+#define GNUAIS_INPUT_IQ       1
+#define GNUAIS_INPUT_WIDEBAND 2
+int  gnuais_batch_frame_times(gnuais_batch *b, int on);
+int  gnuais_batch_drain_frames_timed(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
+int  gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long long *off);
+/* gnuais_nmea_from_frames() with an NMEA 4.10 TAG block in front of EVERY sentence of a frame whose time is known:
+ *   \c:<unix>*hh\!AIVDM,...      <unix> = epoch_s + floor((times[i] * mul + off) / rate_hz), decimal, floor also for
+ * negative values; hh = XOR of the characters between the backslashes up to the '*', two upper-case hex digits.
+ * times[i] = -1: no tag.  mul / off: gnuais_batch_time_map(); rate_hz: the rate of the INPUT samples (> 0); epoch_s:
+ * the UNIX second of input sample 0.  With the tags removed the bytes are those of gnuais_nmea_from_frames(); seqnr,
+ * out == NULL and GNUAIS_E_OVERFLOW as there.  Host code. */
+int  gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *times, int n_frames, uint8_t *seqnr,
+				    int n_channels, long long mul, long long off, long long rate_hz,
+				    long long epoch_s, char *out, size_t out_cap, size_t *out_len,
+				    int *n_sentences);
 
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
@@ -567,6 +626,10 @@ int  gnuais_node_sync(gnuais_node *nd);
 /* merged results: records of every device, channel = global index, reference order (channel, then time) */
 int  gnuais_node_pending_frames(gnuais_node *nd, int *n_out);
 int  gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int *n_out);
+/* the frames' receive times (gnuais_batch_frame_times) on every shard, and the merged drain with them: h_times[i]
+ * belongs to h_out[i]; global channel numbers and the reference's order as gnuais_node_drain_frames */
+int  gnuais_node_frame_times(gnuais_node *nd, int on);
+int  gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
 /* gnuais_batch_stream_nmea() on every shard (each from its own thread): texts[g] / lens[g] = shard g's sentences of
  * the call `stream_depth` calls ago (n_devices entries; valid until the next call).  Written out in shard order they
  * are the node's sentences in the reference's order for that call: shard g's channels all lie before shard g+1's and

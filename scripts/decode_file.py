@@ -15,6 +15,10 @@
                                                       # --iq / --wideband: remove each receiver's carrier error on the device
                                                       # (an SDR's oscillator), estimated over a window of that many samples;
                                                       # the measured errors go to stderr
+  ... --times [--start UNIX_SECONDS]
+                                                      # every sentence behind an NMEA TAG block "\\c:<unix>*hh\\" with the
+                                                      # second the frame was received in, counted in the file's own samples
+                                                      # from --start (the UNIX second of the file's first sample; default 0)
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -42,7 +46,13 @@ def main():
                     help="--iq / --wideband: carrier-error correction over a window of W samples (a multiple of 128; "
                          "2048 suits 48 kHz), 0 = off")
     ap.add_argument("--call", type=int, default=48000, help="frames per device call (at the chain's rate)")
+    ap.add_argument("--times", action="store_true",
+                    help="a TAG block with the UNIX second of reception in front of every sentence (the frame's receive time "
+                         "in input samples, gnuais_batch_frame_times)")
+    ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
+    if a.times and a.text:
+        sys.exit("--times tags NMEA sentences: not with --text")
     import torch
     from gnuais_amd import ReceiverBatch, io, messages_from_frames
     fmt = a.format
@@ -71,18 +81,32 @@ def main():
         b.afc(a.afc)
         x = afc_flush(x, a.afc // 2)
     seq = np.zeros(n_ch, dtype=np.uint8)
+    if a.times:
+        b.frame_times(True)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
             b.run_iq(d)
         else:
             b.run(d)
-        nmea, text = messages_from_frames(b.drain_frames(), seq)
-        sys.stdout.write((text if a.text else nmea).decode("ascii", "replace"))
+        write_sentences(a, b, seq, "iq" if a.iq else "audio", rate or 48000)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
     afc_report(a, b, 48000)
+
+
+def write_sentences(a, b, seq, kind, rate):
+    """what the batch has decoded since the last call, to stdout; rate: of the input samples (--times)"""
+    from gnuais_amd import messages_from_frames, nmea_tagged_from_frames
+    if a.times:
+        frames, times = b.drain_frames_timed()
+        mul, off = b.time_map(kind)
+        out = nmea_tagged_from_frames(frames, times, seq, mul, off, rate, a.start)
+    else:
+        nmea, text = messages_from_frames(b.drain_frames(), seq)
+        out = text if a.text else nmea
+    sys.stdout.write(out.decode("ascii", "replace"))
 
 
 def afc_flush(x, rows, fmt=None):
@@ -117,10 +141,11 @@ def decode_wideband(a, rate, x, fmt=None):
         b.afc(a.afc)
         x = afc_flush(x, a.afc // 2 * D, fmt)
     seq = np.zeros(n_ch, dtype=np.uint8)
+    if a.times:
+        b.frame_times(True)
     for part in io.chunks(x, a.call * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
-        nmea, text = messages_from_frames(b.drain_frames(), seq)
-        sys.stdout.write((text if a.text else nmea).decode("ascii", "replace"))
+        write_sentences(a, b, seq, "wideband", rate)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
