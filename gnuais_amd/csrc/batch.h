@@ -253,6 +253,12 @@ struct gnuais_batch {
     // carry (the last T-1 wide samples of each stream, double-buffered: a launch reads one and writes the other), the
     // wide-sample count n and the narrowband I/Q it writes for the discriminator, [max_len][N][2] (allocated on first use).
     int ch_K = 0, ch_D = 0, ch_T = 0, ch_R = 0, ch_NA = 0;  // ch_K == 0: not configured
+    // gnuais_batch_resampler (resampler.hip): out rate = in rate * ch_U / ch_D; ch_U == 1 with ch_D <= 64 is the integer
+    // channeliser and its kernels.  ch_H: the carry's rows, T - 1 there and ceil((T - 1) / U) here; ch_rational: the
+    // launch goes to resampler.hip (ch_poly then holds its pair table, ch_groups its group table)
+    int ch_U = 1, ch_H = 0;
+    bool ch_rational = false;
+    Buf<int32_t> ch_groups;
     int ch_per[CHAN_MAX_K] = {}, ch_off[CHAN_MAX_K] = {};
     Buf<uint32_t> ch_mix, ch_poly, ch_hist[2];
     Buf<int16_t> ch_taps;
@@ -269,10 +275,12 @@ struct gnuais_batch {
     Buf<int16_t> afc_delay, afc_est, afc_audio;
 };
 
-// Per chain row, `rows` input rows of `cols` columns of `bytes` bytes each; `stages`: bit s = the call passes stage s
+// Per `up` chain rows, `rows` input rows of `cols` columns of `bytes` bytes each (up > 1: the rational channeliser);
+// `stages`: bit s = the call passes stage s
 struct Form {
     int bytes, cols, rows;
     unsigned stages;
+    int up = 1;
     size_t bytes_of(int in_rows) const { return (size_t) bytes * (size_t) cols * (size_t) in_rows; }
 };
 

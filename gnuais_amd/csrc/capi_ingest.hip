@@ -2,6 +2,7 @@
 // carrier-error stage, channeliser with its host tables -- and the entries that take a form's input from device or
 // host memory and hand the audio to gnuais_batch_run (gnuais_capi.hip).  Host code only.
 #include "batch.h"
+#include "resample_plan.h"
 #include "wide_format.h"
 
 // fmt: the sample format of a wide column (GNUAIS_FMT_*); the narrowband forms are int16
@@ -10,7 +11,8 @@ static Form form(const gnuais_batch *b, FormId f, int fmt = GNUAIS_FMT_CS16)
     switch (f) {
     case AUDIO: return {2, b->N, 1, 1u << CHAIN};
     case IQ: return {4, b->N, 1, 1u << DISC | (b->afc_W ? 1u << AFC : 0u) | 1u << CHAIN};
-    default: return {wide_format_bytes(fmt), b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages};
+    default: return {wide_format_bytes(fmt), b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages,
+                 b->ch_U};
     }
 }
 
@@ -35,7 +37,7 @@ int gnuais::chan_zero_state(gnuais_batch *b)
 {
     if (b->ch_K)
         for (auto &p : b->ch_hist)
-            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) (b->ch_T - 1) * (size_t) (b->N / b->ch_K)));
+            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) b->ch_H * (size_t) (b->N / b->ch_K)));
     b->ch_cur = 0;
     b->ch_n = 0;
     b->last[CHAN].used = false;
@@ -225,15 +227,101 @@ int gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, 
     return GNUAIS_OK;
 }
 
+// What a configuration of the wide stage consists of, built on the host by gnuais_batch_channeliser (U = 1, its own
+// kernels) or gnuais_batch_resampler (resampler.hip) and put on the device by chan_install()
+struct ChanConfig {
+    int U = 1, D = 0, R = 0, K = 0, NA = 0, H = 0;
+    bool rational = false;
+    std::vector<int16_t> h, mix;
+    std::vector<uint32_t> poly;        // the fast form's tap pairs (either kernel's layout)
+    std::vector<int32_t> groups;       // resampler.hip's group table
+    int per[CHAN_MAX_K], off[CHAN_MAX_K], total = 0;
+};
+
+// the checks of rate and offsets both configurations share, in the name of the entry `who`: before the taps' checks
+static int chan_shape_check(const gnuais_batch *b, const char *who, int in_rate_hz, int n_offsets)
+{
+    char msg[200];
+    const char *what = nullptr;
+    if (in_rate_hz <= 0) what = "in_rate_hz must be > 0";
+    else if (n_offsets < 1 || n_offsets > CHAN_MAX_K) what = "n_offsets must be 1..32";
+    else if (b->N % n_offsets) what = "the batch's channel count is not a multiple of n_offsets";
+    if (what) {
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    return GNUAIS_OK;
+}
+
+// the mixer periods' check and the mixer tables (C lo, S hi): behind the taps' checks
+static int chan_mixers(const char *who, int in_rate_hz, const int32_t *offsets_hz, int n_offsets, ChanConfig &c)
+{
+    char msg[200];
+    c.K = n_offsets;
+    c.R = in_rate_hz;
+    c.total = 0;
+    for (int k = 0; k < c.K; ++k) {
+        c.per[k] = chan_period(in_rate_hz, offsets_hz[k]);
+        if (!c.per[k]) {
+            snprintf(msg, sizeof msg, "%s: offset %d Hz at %d Hz has a mixer period above 2^20", who, (int) offsets_hz[k],
+                     in_rate_hz);
+            return fail(GNUAIS_E_ARG, msg);
+        }
+        c.off[k] = c.total;
+        c.total += c.per[k];
+    }
+    c.mix.resize(2 * (size_t) c.total);
+    for (int k = 0; k < c.K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], c.per[k], c.mix.data() + 2 * (size_t) c.off[k]);
+    return GNUAIS_OK;
+}
+
+// the configuration onto the device (synchronises it); zeroes the carry and the sample count
+static int chan_install(gnuais_batch *b, const ChanConfig &c)
+{
+    if (int rc = set_device(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (Buf<uint32_t> *p : {&b->ch_mix, &b->ch_poly, &b->ch_hist[0], &b->ch_hist[1]}) HIP_TRY(p->release());
+    HIP_TRY(b->ch_taps.release());
+    HIP_TRY(b->ch_groups.release());
+    b->ch_K = 0;
+    const int T = (int) c.h.size();
+    const size_t M = (size_t) (b->N / c.K);
+    HIP_TRY(b->ch_mix.alloc(sizeof(uint32_t) * (size_t) c.total));
+    HIP_TRY(hipMemcpy(b->ch_mix, c.mix.data(), sizeof(uint32_t) * (size_t) c.total, hipMemcpyHostToDevice));
+    HIP_TRY(b->ch_taps.alloc(sizeof(int16_t) * (size_t) T));
+    HIP_TRY(hipMemcpy(b->ch_taps, c.h.data(), sizeof(int16_t) * (size_t) T, hipMemcpyHostToDevice));
+    if (!c.poly.empty()) {
+        HIP_TRY(b->ch_poly.alloc(sizeof(uint32_t) * c.poly.size()));
+        HIP_TRY(hipMemcpy(b->ch_poly, c.poly.data(), sizeof(uint32_t) * c.poly.size(), hipMemcpyHostToDevice));
+    }
+    if (!c.groups.empty()) {
+        HIP_TRY(b->ch_groups.alloc(sizeof(int32_t) * c.groups.size()));
+        HIP_TRY(hipMemcpy(b->ch_groups, c.groups.data(), sizeof(int32_t) * c.groups.size(), hipMemcpyHostToDevice));
+    }
+    if (c.H > 0)
+        for (auto &p : b->ch_hist) HIP_TRY(p.alloc(sizeof(uint32_t) * (size_t) c.H * M));
+    b->ch_K = c.K;
+    b->ch_U = c.U;
+    b->ch_D = c.D;
+    b->ch_T = T;
+    b->ch_H = c.H;
+    b->ch_R = c.R;
+    b->ch_NA = c.NA;
+    b->ch_rational = c.rational;
+    for (int k = 0; k < c.K; ++k) { b->ch_per[k] = c.per[k]; b->ch_off[k] = c.off[k]; }
+    if (int rc = chan_zero_state(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return GNUAIS_OK;
+}
+
 int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
                              const int16_t *taps, int n_taps)
 {
     if (!b || !offsets_hz) return fail(GNUAIS_E_ARG, "channeliser: NULL argument");
     if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser: decim must be 1..64");
-    if (in_rate_hz <= 0) return fail(GNUAIS_E_ARG, "channeliser: in_rate_hz must be > 0");
-    if (n_offsets < 1 || n_offsets > CHAN_MAX_K) return fail(GNUAIS_E_ARG, "channeliser: n_offsets must be 1..32");
-    if (b->N % n_offsets) return fail(GNUAIS_E_ARG, "channeliser: the batch's channel count is not a multiple of n_offsets");
-    std::vector<int16_t> h;
+    if (int rc = chan_shape_check(b, "channeliser", in_rate_hz, n_offsets)) return rc;
+    ChanConfig c;
+    std::vector<int16_t> &h = c.h;
     if (!taps || n_taps == 0) {
         chan_default_taps(decim, h);
     } else {
@@ -247,29 +335,13 @@ int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const i
         sum += std::abs((int) v);
     }
     if (sum > 65535) return fail(GNUAIS_E_ARG, "channeliser: sum |h| exceeds 65535");
-    const int K = n_offsets;
-    int per[CHAN_MAX_K], off[CHAN_MAX_K];
-    int total = 0;
-    for (int k = 0; k < K; ++k) {
-        per[k] = chan_period(in_rate_hz, offsets_hz[k]);
-        if (!per[k]) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "channeliser: offset %d Hz at %d Hz has a mixer period above 2^20", (int) offsets_hz[k],
-                     in_rate_hz);
-            return fail(GNUAIS_E_ARG, msg);
-        }
-        off[k] = total;
-        total += per[k];
-    }
-    // host tables: mixer words (C lo, S hi); the fast form's tap pairs POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q])
-    std::vector<int16_t> mix(2 * (size_t) total);
-    for (int k = 0; k < K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], per[k], mix.data() + 2 * (size_t) off[k]);
-    const int D = decim;
+    if (int rc = chan_mixers("channeliser", in_rate_hz, offsets_hz, n_offsets, c)) return rc;
+    // the fast form's tap pairs POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q])
+    const int D = decim, K = n_offsets;
     const int NA = channeliser_fast_na(K, T, D);
-    std::vector<uint32_t> poly;
     if (NA) {
         const int NP = (D + 1) / 2;
-        poly.assign((size_t) NP * NA, 0u);
+        c.poly.assign((size_t) NP * NA, 0u);
         auto tap = [&](int a, int r) -> int {
             if (r >= D) return 0;
             const int j = a * D + D - 1 - r;
@@ -277,33 +349,107 @@ int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const i
         };
         for (int q = 0; q < NP; ++q)
             for (int a = 0; a < NA; ++a)
-                poly[(size_t) q * NA + a] = (uint32_t) (uint16_t) tap(a, 2 * q) | ((uint32_t) (uint16_t) tap(a, 2 * q + 1) << 16);
+                c.poly[(size_t) q * NA + a] = (uint32_t) (uint16_t) tap(a, 2 * q) | ((uint32_t) (uint16_t) tap(a, 2 * q + 1) << 16);
     }
-    if (int rc = set_device(b)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    for (Buf<uint32_t> *p : {&b->ch_mix, &b->ch_poly, &b->ch_hist[0], &b->ch_hist[1]}) HIP_TRY(p->release());
-    HIP_TRY(b->ch_taps.release());
-    b->ch_K = 0;
-    const size_t M = (size_t) (b->N / K);
-    HIP_TRY(b->ch_mix.alloc(sizeof(uint32_t) * (size_t) total));
-    HIP_TRY(hipMemcpy(b->ch_mix, mix.data(), sizeof(uint32_t) * (size_t) total, hipMemcpyHostToDevice));
-    HIP_TRY(b->ch_taps.alloc(sizeof(int16_t) * (size_t) T));
-    HIP_TRY(hipMemcpy(b->ch_taps, h.data(), sizeof(int16_t) * (size_t) T, hipMemcpyHostToDevice));
-    if (NA) {
-        HIP_TRY(b->ch_poly.alloc(sizeof(uint32_t) * poly.size()));
-        HIP_TRY(hipMemcpy(b->ch_poly, poly.data(), sizeof(uint32_t) * poly.size(), hipMemcpyHostToDevice));
-    }
-    if (T > 1)
-        for (auto &p : b->ch_hist) HIP_TRY(p.alloc(sizeof(uint32_t) * (size_t) (T - 1) * M));
-    b->ch_K = K;
-    b->ch_D = D;
-    b->ch_T = T;
-    b->ch_R = in_rate_hz;
-    b->ch_NA = NA;
-    for (int k = 0; k < K; ++k) { b->ch_per[k] = per[k]; b->ch_off[k] = off[k]; }
-    if (int rc = chan_zero_state(b)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
+    c.U = 1;
+    c.D = D;
+    c.NA = NA;
+    c.H = T - 1;
+    return chan_install(b, c);
+}
+
+// ---- wideband in at a rational ratio U/D (include/gnuais_hip.h): resampler.hip, planned by resample_plan.cpp ----
+
+static int resampler_ratio_check(const char *who, int up, int down)
+{
+    static const char *const why[] = {"", "up must be 1..64", "down must be 2..1024", "up must be below down (no up-sampling)",
+                                      "up and down must have no common factor"};
+    const int r = resample_check_ratio(up, down);
+    if (!r) return GNUAIS_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, why[r]);
+    return fail(GNUAIS_E_ARG, msg);
+}
+
+static int resampler_taps_check(const char *who, int up, const int16_t *h, int T)
+{
+    static const char *const why[] = {"", "n_taps must be 1..16385", "a tap is -32768 (|h| <= 32767)",
+                                      "a phase's sum |h[j]|, j = phase mod up, exceeds 65535"};
+    const int r = resample_check_taps(up, h, T);
+    if (!r) return GNUAIS_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, why[r]);
+    return fail(GNUAIS_E_ARG, msg);
+}
+
+int gnuais_resampler_default_taps(int up, int down, int16_t *out, int cap, int *n_taps)
+{
+    if (int rc = resampler_ratio_check("resampler_default_taps", up, down)) return rc;
+    std::vector<int16_t> h;
+    resample_default_taps(up, down, h);
+    const int T = (int) h.size();
+    if (n_taps) *n_taps = T;
+    if (!out) return GNUAIS_OK;
+    if (cap < T) return fail(GNUAIS_E_ARG, "resampler_default_taps: cap < 16*down + 1");
+    memcpy(out, h.data(), sizeof(int16_t) * (size_t) T);
     return GNUAIS_OK;
+}
+
+int gnuais_resampler_plan(int up, int down, const int16_t *taps, int n_taps, int32_t *groups, int groups_cap,
+                          uint32_t *pairs, int pairs_cap, int *n_pairs, int *n_acc, int *carry)
+{
+    if (int rc = resampler_ratio_check("resampler_plan", up, down)) return rc;
+    std::vector<int16_t> h;
+    if (!taps || n_taps == 0) resample_default_taps(up, down, h);
+    else if (n_taps < 1 || n_taps > RESAMP_MAX_TAPS) return fail(GNUAIS_E_ARG, "resampler_plan: n_taps must be 1..16385");
+    else h.assign(taps, taps + n_taps);
+    if (int rc = resampler_taps_check("resampler_plan", up, h.data(), (int) h.size())) return rc;
+    ResamplePlan p;
+    // the stride the device's fast form reads (its one bucket); a longer prototype, the direct form's, at its own
+    const int na = std::max(((int) h.size() + down - 1) / down, RESAMP_FAST_NA);
+    resample_plan(up, down, h.data(), (int) h.size(), na, p);
+    if (n_pairs) *n_pairs = p.n_pairs;
+    if (n_acc) *n_acc = p.NA;
+    if (carry) *carry = p.H;
+    if (groups) {
+        if (groups_cap < 3 * up) return fail(GNUAIS_E_ARG, "resampler_plan: groups_cap < 3 * up");
+        memcpy(groups, p.groups.data(), sizeof(int32_t) * 3 * (size_t) up);
+    }
+    if (pairs) {
+        if ((long long) pairs_cap < (long long) p.pairs.size()) return fail(GNUAIS_E_ARG, "resampler_plan: pairs_cap < n_pairs * n_acc");
+        memcpy(pairs, p.pairs.data(), sizeof(uint32_t) * p.pairs.size());
+    }
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_resampler(gnuais_batch *b, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                           const int16_t *taps, int n_taps)
+{
+    if (!b || !offsets_hz) return fail(GNUAIS_E_ARG, "resampler: NULL argument");
+    if (int rc = resampler_ratio_check("resampler", up, down)) return rc;
+    // the integer channeliser's own configuration and kernels: one path for U = 1, D <= 64
+    if (up == 1 && down <= 64) return gnuais_batch_channeliser(b, down, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
+    if (int rc = chan_shape_check(b, "resampler", in_rate_hz, n_offsets)) return rc;
+    ChanConfig c;
+    if (!taps || n_taps == 0) resample_default_taps(up, down, c.h);
+    else if (n_taps < 1 || n_taps > RESAMP_MAX_TAPS) return fail(GNUAIS_E_ARG, "resampler: n_taps must be 1..16385");
+    else c.h.assign(taps, taps + n_taps);
+    const int T = (int) c.h.size();
+    if (int rc = resampler_taps_check("resampler", up, c.h.data(), T)) return rc;
+    if (int rc = chan_mixers("resampler", in_rate_hz, offsets_hz, n_offsets, c)) return rc;
+    c.U = up;
+    c.D = down;
+    c.rational = true;
+    c.NA = resampler_fast_na(c.K, T, down);
+    c.H = (T - 1 + up - 1) / up;
+    if (c.NA) {
+        ResamplePlan p;
+        resample_plan(up, down, c.h.data(), T, c.NA, p);
+        c.poly = std::move(p.pairs);
+        c.groups.resize(3 * (size_t) up);
+        memcpy(c.groups.data(), p.groups.data(), sizeof(int32_t) * 3 * (size_t) up);
+    }
+    return chan_install(b, c);
 }
 
 // The checks of the entries that take a form's input, in the name of the entry `who` (the device entries of the
@@ -321,9 +467,12 @@ static int check_input(const gnuais_batch *b, FormId id, const void *x, int len,
         snprintf(msg, sizeof msg, "%s: unknown sample format %d (GNUAIS_FMT_*)", who, fmt);
     } else if (!b->ch_K) {
         snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
-    } else if (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len) {
+    } else if (b->ch_U == 1 && (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len)) {
         snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
                  len, b->ch_D, b->ch_D);
+    } else if (len <= 0 || len % b->ch_D || (long long) (len / b->ch_D) * b->ch_U > b->max_len) {
+        snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of down = %d that gives at most max_len rows "
+                 "(len * %d / %d <= %d)", who, len, b->ch_D, b->ch_U, b->ch_D, b->max_len);
     } else if (reinterpret_cast<uintptr_t>(x) % (uintptr_t) wide_format_align(fmt)) {
         snprintf(msg, sizeof msg, "%s: %s wide samples must be %d-byte aligned", who, wide_format_name(fmt),
                  wide_format_align(fmt));
@@ -333,8 +482,42 @@ static int check_input(const gnuais_batch *b, FormId id, const void *x, int len,
     return fail(GNUAIS_E_ARG, msg);
 }
 
+// the launch of a batch configured by gnuais_batch_resampler with U > 1 or D > 64 (resampler.hip)
+static int resampler_launch(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, hipStream_t s)
+{
+    ResampLaunch a{};
+    a.in = d_wide;
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.hist = b->ch_hist[b->ch_cur];
+    a.mix = b->ch_mix;
+    a.pairs = b->ch_poly;
+    a.groups = b->ch_groups;
+    a.taps = b->ch_taps;
+    a.M = b->N / b->ch_K;
+    a.K = b->ch_K;
+    a.U = b->ch_U;
+    a.D = b->ch_D;
+    a.T = b->ch_T;
+    a.H = b->ch_H;
+    a.len = len;
+    const unsigned vec = a.K == 2 ? 8u : a.K == 4 ? 16u : 4u;       // as chan_launch
+    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : b->ch_NA;
+    if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(GNUAIS_E_ARG, "channelise: the output must be 4-byte aligned");
+    for (int k = 0; k < a.K; ++k) {
+        a.per[k] = b->ch_per[k];
+        a.off[k] = b->ch_off[k];
+        a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
+    }
+    HIP_TRY(launch_resampler(a, fmt, b->ch_hist[b->ch_cur ^ 1], s));
+    if (b->ch_H > 0) b->ch_cur ^= 1;
+    b->ch_n += (unsigned long long) len;
+    b->last[CHAN] = {s, true};
+    return GNUAIS_OK;
+}
+
 static int chan_launch(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, hipStream_t s)
 {
+    if (b->ch_rational) return resampler_launch(b, fmt, d_wide, len, d_out, s);
     ChanLaunch a{};
     a.in = d_wide;
     a.out = reinterpret_cast<uint32_t *>(d_out);
@@ -409,7 +592,7 @@ static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *s
         if (int rc = chan_launch(b, fmt, in, len, b->ch_iq, s)) return rc;
         x = b->ch_iq;
     }
-    len /= f.rows;
+    len = len / f.rows * f.up;
     if (disc) {
         if (int rc = disc_launch(b, x, len, b->iq_audio, s, afc)) return rc;
         x = b->iq_audio;

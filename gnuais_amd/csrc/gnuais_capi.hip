@@ -1027,6 +1027,9 @@ int gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long 
         return GNUAIS_OK;
     case GNUAIS_INPUT_WIDEBAND: {
         if (!b->ch_K) return fail(GNUAIS_E_STATE, "time_map: no channeliser configured (gnuais_batch_channeliser)");
+        if (b->ch_U > 1)
+            return fail(GNUAIS_E_STATE, "time_map: the wide stage resamples by a ratio up / down with up > 1: use "
+                                        "gnuais_batch_time_map_ratio");
         const long long D = b->ch_D, T = b->ch_T;
         *mul = D;
         *off = (-d_f - half_w) * D + D - 1 - (T - 1) / 2;
@@ -1035,6 +1038,21 @@ int gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long 
     default:
         return fail(GNUAIS_E_ARG, "time_map: kind must be GNUAIS_INPUT_AUDIO, _IQ or _WIDEBAND");
     }
+}
+
+// input sample index = floor((t * num + off) / den): gnuais_batch_time_map with the rational channeliser's ratio
+int gnuais_batch_time_map_ratio(const gnuais_batch *b, int kind, long long *num, long long *den, long long *off)
+{
+    if (!b || !num || !den || !off) return fail(GNUAIS_E_ARG, "time_map_ratio: argument");
+    if (kind != GNUAIS_INPUT_WIDEBAND || !b->ch_K || b->ch_U == 1) {      // den = 1: the integer map, with its checks
+        *den = 1;
+        return gnuais_batch_time_map(b, kind, num, off);
+    }
+    const long long d_f = (b->NT + 1) / 2, half_w = b->afc_W / 2, D = b->ch_D, T = b->ch_T;
+    *num = D;
+    *den = b->ch_U;
+    *off = (-d_f - half_w) * D + D - 1 - (T - 1) / 2;
+    return GNUAIS_OK;
 }
 
 int gnuais_batch_n_channels(const gnuais_batch *b) { return b ? b->N : 0; }

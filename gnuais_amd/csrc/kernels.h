@@ -184,6 +184,26 @@ hipError_t launch_channeliser(const ChanLaunch &a, int fmt, uint32_t *hist_out, 
 // the formats other than GNUAIS_FMT_CS16 (channeliser_fmt.hip); hipErrorInvalidValue for an unknown one
 hipError_t launch_channeliser_fmt(const ChanLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
 
+// ---- wideband in at a rational ratio: the U/D channeliser (resampler.hip; host planning in resample_plan.h) ----
+// in [len][M] pairs of format fmt -> out [len*U/D][M*K][2] int16, len a multiple of D, the definition in
+// include/gnuais_hip.h above gnuais_batch_resampler.  hist [H][M] words is the carry (the last H = ceil((T-1)/U) wide
+// samples, converted), read here; the launch writes the next one into hist_out (another buffer).
+struct ResampLaunch {
+    const void *in;        // [len][M] pairs in the launch's format
+    uint32_t *out;         // [len*U/D][M*K]
+    const uint32_t *hist;  // [H][M]
+    const uint32_t *mix;   // mixer tables as ChanLaunch::mix
+    const uint32_t *pairs; // fast form: ResamplePlan::pairs at NA accumulators
+    const int32_t *groups; // fast form: [U][3] = ResampGroup
+    const int16_t *taps;   // direct form: [T]
+    int M, K, U, D, T, H, len;
+    int NA;                // RESAMP_FAST_NA, 0 = direct form
+    int n_groups, seg_rows;                // set by launch_resampler
+    int per[CHAN_MAX_K], off[CHAN_MAX_K];
+    int ph0[CHAN_MAX_K];   // (n mod per[k]) of the call's first wide sample
+};
+hipError_t launch_resampler(const ResampLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
+
 // ---- f1 on the device (nmea_device.hip) ---------------------------------------
 size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);
 // frames: device gnuais_frame[n]; seq_in/seq_out: device u8[n_channels] (seq_out preloaded with

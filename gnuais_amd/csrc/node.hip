@@ -179,7 +179,7 @@ void pin_to_device_node(Shard &s)
 
 struct gnuais_node {
     int N = 0, max_len = 0;
-    int ch_K = 0, ch_D = 0;         // gnuais_node_channeliser (0: not configured)
+    int ch_K = 0, ch_D = 0, ch_U = 1;   // gnuais_node_channeliser / _resampler (ch_K == 0: not configured)
     std::vector<Shard *> shards;
     std::vector<gnuais_frame> scratch;
     std::string warnings;           // what create could not do without failing (one line per shard)
@@ -404,6 +404,33 @@ int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const in
     if (rc == GNUAIS_OK) {
         nd->ch_K = n_offsets;
         nd->ch_D = decim;
+        nd->ch_U = 1;
+    }
+    return rc;
+}
+
+int gnuais_node_resampler(gnuais_node *nd, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                          const int16_t *taps, int n_taps)
+{
+    if (!nd || !offsets_hz) return node_fail(GNUAIS_E_ARG, "node_resampler: NULL argument");
+    if (n_offsets < 1) return node_fail(GNUAIS_E_ARG, "node_resampler: n_offsets must be >= 1");
+    for (size_t i = 0; i < nd->shards.size(); ++i) {
+        const Shard &s = *nd->shards[i];
+        if (s.first % n_offsets || s.n % n_offsets) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "node_resampler: shard %zu (channels %d..%d) does not start and end on a multiple of "
+                     "n_offsets = %d", i, s.first, s.first + s.n - 1, n_offsets);
+            return node_fail(GNUAIS_E_ARG, msg);
+        }
+    }
+    nd->ch_K = 0;
+    const int rc = run_all(nd, [=](Shard &s, size_t) {
+        return gnuais_batch_resampler(s.b, up, down, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
+    });
+    if (rc == GNUAIS_OK) {
+        nd->ch_K = n_offsets;
+        nd->ch_D = down;
+        nd->ch_U = up;
     }
     return rc;
 }
@@ -414,13 +441,24 @@ int gnuais_node_afc(gnuais_node *nd, int window)
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_afc(s.b, window); });
 }
 
+// a wideband call's length against the node's configuration (gnuais_node_channeliser: U = 1; gnuais_node_resampler)
+static int wide_len_check(const gnuais_node *nd, int len, const char *who)
+{
+    if (len > 0 && len % nd->ch_D == 0 && (long long) (len / nd->ch_D) * nd->ch_U <= nd->max_len) return GNUAIS_OK;
+    char msg[240];
+    if (nd->ch_U == 1)
+        snprintf(msg, sizeof msg, "%s: len must be a positive multiple of the decimation, at most decim * max_len", who);
+    else
+        snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of down = %d that gives at most max_len rows "
+                 "(len * %d / %d <= %d)", who, len, nd->ch_D, nd->ch_U, nd->ch_D, nd->max_len);
+    return node_fail(GNUAIS_E_ARG, msg);
+}
+
 int gnuais_node_run_wideband_host(gnuais_node *nd, const int16_t *h_wide, int len)
 {
     if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: NULL argument");
-    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: no channeliser configured (gnuais_node_channeliser)");
-    if (len <= 0 || len % nd->ch_D || len / nd->ch_D > nd->max_len)
-        return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: len must be a positive multiple of the decimation, at most "
-                                       "decim * max_len");
+    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_host: no channeliser configured (gnuais_node_channeliser / _resampler)");
+    if (int rc = wide_len_check(nd, len, "node_run_wideband_host")) return rc;
     return run_staged(nd, WIDE, h_wide, len, "node_run_wideband_host", gnuais_batch_run_wideband);
 }
 
@@ -429,10 +467,8 @@ int gnuais_node_run_wideband_fmt_host(gnuais_node *nd, int fmt, const void *h_wi
     if (!nd || !h_wide) return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: NULL argument");
     if (gnuais_sample_format_bytes(fmt) < 0)
         return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: unknown sample format (GNUAIS_FMT_*)");
-    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: no channeliser configured (gnuais_node_channeliser)");
-    if (len <= 0 || len % nd->ch_D || len / nd->ch_D > nd->max_len)
-        return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: len must be a positive multiple of the decimation, at "
-                                       "most decim * max_len");
+    if (!nd->ch_K) return node_fail(GNUAIS_E_ARG, "node_run_wideband_fmt_host: no channeliser configured (gnuais_node_channeliser / _resampler)");
+    if (int rc = wide_len_check(nd, len, "node_run_wideband_fmt_host")) return rc;
     return run_staged(nd, WIDE, h_wide, len, "node_run_wideband_fmt_host", nullptr, fmt);
 }
 

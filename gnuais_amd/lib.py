@@ -48,6 +48,9 @@ SYMBOLS = {
     "gnuais_batch_afc_estimate": (_I, [_P, _P]),
     "gnuais_batch_afc_apply": (_I, [_P, _P, _I, _P, _P]),
     "gnuais_batch_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
+    "gnuais_batch_resampler": (_I, [_P, _I, _I, _I, _P, _I, _P, _I]),
+    "gnuais_resampler_default_taps": (_I, [_I, _I, _P, _I, C.POINTER(_I)]),
+    "gnuais_resampler_plan": (_I, [_I, _I, _P, _I, _P, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_batch_run_wideband": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_wideband_host": (_I, [_P, _P, _I]),
     "gnuais_batch_channelise": (_I, [_P, _P, _I, _P, _P]),
@@ -75,6 +78,7 @@ SYMBOLS = {
     "gnuais_batch_frame_times": (_I, [_P, _I]),
     "gnuais_batch_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_time_map": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "gnuais_batch_time_map_ratio": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_nmea_tagged_from_frames": (_I, [_P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
                                             _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I)]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
@@ -127,6 +131,7 @@ SYMBOLS = {
     "gnuais_node_run_iq_host": (_I, [_P, _P, _I]),
     "gnuais_node_run_iq": (_I, [_P, _P, _I, _P]),
     "gnuais_node_channeliser": (_I, [_P, _I, _I, _P, _I, _P, _I]),
+    "gnuais_node_resampler": (_I, [_P, _I, _I, _I, _P, _I, _P, _I]),
     "gnuais_node_run_wideband_host": (_I, [_P, _P, _I]),
     "gnuais_node_run_wideband_fmt_host": (_I, [_P, _I, _P, _I]),
     "gnuais_node_afc": (_I, [_P, _I]),

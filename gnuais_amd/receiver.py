@@ -141,6 +141,34 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_channeliser(self._h, int(decim), int(in_rate_hz), off.ctypes.data, int(off.size),
                                                  None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
         self._chan = (int(decim), int(off.size))
+        self._chan_up = 1
+
+    def resampler(self, up: int, down: int, in_rate_hz: int, offsets_hz, taps=None):
+        """Configure the wide stage at a rational ratio (gnuais_batch_resampler, defined in include/gnuais_hip.h): as
+        channeliser(), with the chain's rate = in_rate_hz * up / down (up < down, no common factor).  Wideband calls then
+        take len a multiple of `down` and give len * up / down rows.  taps: the int16 prototype at up * in_rate_hz, or
+        None for the default design.  up = 1 with down <= 64 is channeliser(down, ...)."""
+        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        assert off.ndim == 1 and off.size >= 1
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
+        check(self._lib.gnuais_batch_resampler(self._h, int(up), int(down), int(in_rate_hz), off.ctypes.data, int(off.size),
+                                               None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
+        self._chan = (int(down), int(off.size))
+        self._chan_up = int(up)
+
+    def channeliser_for_rate(self, in_rate_hz: int, offsets_hz, out_rate_hz: Optional[int] = None):
+        """Configure the wide stage for a capture at `in_rate_hz`: the ratio out_rate_hz / in_rate_hz (out_rate_hz: the
+        chain's rate, 48000 by default) reduced by its gcd, through channeliser() where it is 1 / D with D <= 64 and
+        through resampler() otherwise.  Returns (up, down)."""
+        import math
+        out = 48000 if out_rate_hz is None else int(out_rate_hz)
+        g = math.gcd(int(in_rate_hz), out)
+        up, down = out // g, int(in_rate_hz) // g
+        if up == 1 and down <= 64:
+            self.channeliser(down, in_rate_hz, offsets_hz)
+        else:
+            self.resampler(up, down, in_rate_hz, offsets_hz)
+        return up, down
 
     def _wide_shape_ok(self, x, n_rows):
         if not hasattr(self, "_chan"):                  # not configured: the library says so
@@ -199,17 +227,17 @@ class ReceiverBatch:
 
     def channelise(self, samples, fmt: Optional[str] = None):
         """The channeliser alone (gnuais_batch_channelise): int16 [len][n_channels / K][2] -> torch int16
-        [len / D][n_channels][2] on the device; advances the channeliser's state and nothing else.  fmt: as
+        [len / D][n_channels][2] ([len * U / D] behind resampler()) on the device; advances the channeliser's state and nothing else.  fmt: as
         run_wideband (gnuais_batch_channelise_fmt)."""
-        d = getattr(self, "_chan", (1, 1))[0]
+        d, up = getattr(self, "_chan", (1, 1))[0], getattr(self, "_chan_up", 1)
         if fmt is None:
             return self._stage(samples, lambda x: self._wide_shape_ok(x, int(x.shape[0])),
-                               lambda n: (n // d, self.n_channels, 2), self._lib.gnuais_batch_channelise)
+                               lambda n: (n // d * up, self.n_channels, 2), self._lib.gnuais_batch_channelise)
         import torch
         value, x = self._wide_native(samples, fmt)
         if not _is_torch(x):
             x = torch.from_numpy(x).to(f"cuda:{self.device}")
-        out = torch.empty((int(x.shape[0]) // d, self.n_channels, 2), dtype=torch.int16, device=x.device)
+        out = torch.empty((int(x.shape[0]) // d * up, self.n_channels, 2), dtype=torch.int16, device=x.device)
         stream = torch.cuda.current_stream(x.device)
         check(self._lib.gnuais_batch_channelise_fmt(self._h, value, x.data_ptr(), int(x.shape[0]), out.data_ptr(),
                                                     C.c_void_p(stream.cuda_stream)))
@@ -335,6 +363,14 @@ class ReceiverBatch:
         mul, off = C.c_longlong(0), C.c_longlong(0)
         check(self._lib.gnuais_batch_time_map(self._h, _lib.INPUT_KINDS[kind], C.byref(mul), C.byref(off)))
         return mul.value, off.value
+
+    def time_map_ratio(self, kind: str = "audio"):
+        """gnuais_batch_time_map_ratio(): (num, den, off) with input sample index = (t * num + off) // den (floor) for
+        the batch's configuration as it is now, whatever configured the wide stage; kind as time_map()."""
+        num, den, off = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.gnuais_batch_time_map_ratio(self._h, _lib.INPUT_KINDS[kind], C.byref(num), C.byref(den),
+                                                    C.byref(off)))
+        return num.value, den.value, off.value
 
     def drain_nmea(self, seqnr: np.ndarray):
         """The queued frames as !AIVDM sentences, formatted on the device (row f1); consumes them.

@@ -83,6 +83,17 @@ class ReceiverNode:
                                                       None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
         self._chan_k = int(off.size)
 
+    def resampler(self, up: int, down: int, in_rate_hz: int, offsets_hz, taps=None):
+        """Wideband in at a rational ratio (gnuais_node_resampler): ReceiverBatch.resampler on every shard, under
+        channeliser()'s rule for the shards."""
+        np = self._np
+        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
+        self._raise(self._lib.gnuais_node_resampler(self._h, int(up), int(down), int(in_rate_hz), off.ctypes.data,
+                                                    int(off.size), None if t is None else t.ctypes.data,
+                                                    0 if t is None else int(t.size)))
+        self._chan_k = int(off.size)
+
     def afc(self, window: int):
         """Carrier-error correction of I/Q input (gnuais_node_afc): ReceiverBatch.afc on every shard."""
         self._raise(self._lib.gnuais_node_afc(self._h, int(window)))
@@ -227,6 +238,16 @@ class ReceiverNode:
         mul, off = C.c_longlong(0), C.c_longlong(0)
         check(self._lib.gnuais_batch_time_map(bh, INPUT_KINDS[kind], C.byref(mul), C.byref(off)))
         return mul.value, off.value
+
+    def time_map_ratio(self, kind: str = "audio"):
+        """gnuais_batch_time_map_ratio() of the first shard: (num, den, off), index = (t * num + off) // den"""
+        from .lib import INPUT_KINDS, check
+        C = self._C
+        dev, first, n, bh = C.c_int(), C.c_int(), C.c_int(), C.c_void_p()
+        self._raise(self._lib.gnuais_node_shard(self._h, 0, C.byref(dev), C.byref(first), C.byref(n), C.byref(bh)))
+        num, den, off = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.gnuais_batch_time_map_ratio(bh, INPUT_KINDS[kind], C.byref(num), C.byref(den), C.byref(off)))
+        return num.value, den.value, off.value
 
     def counters(self):
         from .lib import COUNTERS_DTYPE

@@ -193,6 +193,22 @@ def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz
     return np.clip(np.rint(out), -32768, 32767).astype(np.int16), placed
 
 
+def make_resampled_wideband_stream(n_samples: int, up: int, down: int, offsets_hz, seed: int = SEED, stream: int = 0,
+                                   amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
+                                   offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False):
+    """One wide complex stream at rate_hz * down / up, for a channeliser that resamples by up / down to the chain's rate
+    (ReceiverBatch.resampler): make_wideband_stream() without its noise at rate_hz * down, every `up`-th sample of it
+    kept, then white Gaussian noise of `sigma` on I and Q from the same generator, rounded and clamped to int16.
+    Returns (int16[n_samples][2], [placed payloads of offset k, for each k])."""
+    x, placed = make_wideband_stream(n_samples * up, down, int(rate_hz) * down, offsets_hz, seed=seed, stream=stream,
+                                     amplitude=amplitude, sigma=0.0, occupancy=occupancy, offset_hz=offset_hz,
+                                     rate_hz=rate_hz, gated=gated)
+    out = x[::up].astype(np.float64)
+    if sigma > 0:
+        out += np.random.default_rng([seed, stream, 0x5744]).normal(0.0, sigma, out.shape)
+    return np.clip(np.rint(out), -32768, 32767).astype(np.int16), placed
+
+
 def make_base_streams(n_base: int, n_samples: int, **kw):
     """[n_base][n_samples] int16 + per-stream placed payload lists."""
     streams = np.empty((n_base, n_samples), dtype=np.int16)

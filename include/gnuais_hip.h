@@ -207,6 +207,45 @@ int  gnuais_batch_channelise(gnuais_batch *b, const int16_t *d_wide, int len, in
 int  gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_taps);
 int  gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, int cap, int *period);
 
+/* ---- wideband in at any sample rate: the channeliser at a rational ratio U/D ----------------------------------------
+ * Not in the reference.  For captures whose rate is no integer multiple of the chain's (250 k = 24/125 of 48 k, 1.024 M
+ * = 3/64, 2.048 M = 3/128, 2.5 M = 12/625, ...).  U = up, D = down, gcd(U, D) = 1, out rate = in rate * U / D; all
+ * integer as above, shapes, offsets, formats and n as above.  Limits: 1 <= U <= 64, U < D <= 1024.
+ *   Mixer: unchanged -- tables at the INPUT rate R, p = n mod P_k, the same rounding and saturation.
+ *   Filter: a prototype of int16 taps h[0..T-1] at the up-sampled rate U*R.  Narrowband row m, counted since reset or
+ *   configuration, ends on up-sampled tick u_m = m*D + D-1 (wide sample n sits on tick n*U):
+ *     acc = sum over the j in [0, T) with (u_m - j) mod U == 0 of  h[j] * mr[(u_m - j) / U]      (mr before sample 0 = 0)
+ *     out_re = sat16((acc + 16384) >> 15), the same for mi -> out_im
+ *   A call takes len wide samples, len a positive multiple of D with len*U/D <= max_len, and gives len*U/D rows: every
+ *   call starts on a period boundary (n a multiple of D, the row count a multiple of U).
+ *   Taps: 1 <= T <= 16385, |h[j]| <= 32767, and for EVERY phase phi in [0, U) the sum of |h[j]| over j = phi (mod U) is
+ *   <= 65535 (else GNUAIS_E_ARG): a row takes the taps of one phase, so the int32 argument above holds per row and any
+ *   order of the sums gives the same bits.
+ *   Default taps (taps == NULL or n_taps == 0): the formula above with D = down -- T = 16D + 1, the same window,
+ *   x[j] = 0.75 * (j - 8D) / D -- scaled by U:  h[j] = rnd(g[j] * 32768.0 * U / G)  (as written, left to right), the same
+ *   response at the output rate.  The DC gain of a phase, sum of h[j] over j = phi (mod U), then differs from phase to
+ *   phase by rounding: 32758 .. 32828 of 32768 over 24/125, 6/125, 3/64, 2/75, 3/125, 3/128, 12/625, 3/160, 2/125,
+ *   3/200, 1/125 and 3/625 (32761 .. 32773 at 24/125).  That is a property of the design, not an error; the largest
+ *   per-phase sum |h| is 48604 .. 48776 there (about 50500 at 5/6 and 2/3).
+ *   Carried per stream: the last H = ceil((T-1) / U) converted wide samples (T-1 at U = 1); per batch: n.
+ * gnuais_batch_resampler(up = 1, down <= 64) IS gnuais_batch_channeliser(down, ...): the same configuration, limits
+ * (T <= 1025, sum |h| <= 65535), messages and kernels.  Every wideband entry above and below -- _run_wideband[_fmt][_host],
+ * _channelise[_fmt], the node forms, the four sample formats, the AFC, frame times -- works unchanged on a batch
+ * configured here; gnuais_batch_channelise writes [len*U/D][N][2]. */
+int  gnuais_batch_resampler(gnuais_batch *b, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                            const int16_t *taps, int n_taps);
+/* host only, no batch: the default prototype for up / down into out[cap] (*n_taps = 16*down + 1) */
+int  gnuais_resampler_default_taps(int up, int down, int16_t *out, int cap, int *n_taps);
+/* host only, no batch, for tests: what the device's fast form is planned from (taps NULL / 0 = default).  Rows repeat with
+ * period U; row phase i takes the `size` wide samples from `first` on (relative to the period) since the row before:
+ * groups[i] = (first, size, base), first = floor((i*D - 1) / U) + 1.  pairs[(base + q) * n_acc + a] = (lo, hi) = the taps
+ * of samples k = first + 2q and k + 1 for the row a after this one, j = (i + a)*D + D-1 - k*U, 0 where j is outside
+ * [0, T) or the group has no sample k + 1; *n_acc = max(ceil(T / D), 17), the table's stride (17: the accumulators of
+ * the device's fast form, whose table this then is), *n_pairs = sum of ceil(size / 2), *carry = H.  Each
+ * output may be NULL; groups_cap and pairs_cap count elements (3*up and *n_pairs * *n_acc are needed). */
+int  gnuais_resampler_plan(int up, int down, const int16_t *taps, int n_taps, int32_t *groups, int groups_cap,
+                           uint32_t *pairs, int pairs_cap, int *n_pairs, int *n_acc, int *carry);
+
 /* ---- sample formats of wideband input: 8-bit and float SDR captures, converted where the channeliser loads them ----
  * Not in the reference.  A sample format says how one wide (I, Q) pair lies in memory and how each of its components
  * becomes the int16 v of the channeliser's definition above:
@@ -378,9 +417,14 @@ int  gnuais_batch_history(gnuais_batch *b, int16_t *h_out);
  *   D and T the channeliser's decimation and tap count:
  *     GNUAIS_INPUT_AUDIO      mul = 1,  off = -d_f
  *     GNUAIS_INPUT_IQ         mul = 1,  off = -d_f - W/2
- *     GNUAIS_INPUT_WIDEBAND   mul = D,  off = (-d_f - W/2) * D + D - 1 - (T - 1) / 2     (GNUAIS_E_STATE if not configured)
+ *     GNUAIS_INPUT_WIDEBAND   mul = D,  off = (-d_f - W/2) * D + D - 1 - (T - 1) / 2     (GNUAIS_E_STATE if not configured,
+ *                             and, naming the call below, if gnuais_batch_resampler configured a ratio with up > 1)
  *   The offsets are the delays of the stages as constants -- the nominal decision instant -- not a calibration against
  *   a transmitter's clock.  The index may be negative for the first rows.
+ * gnuais_batch_time_map_ratio(kind): the same for every configuration: the input sample index of chain row t is
+ *   floor((t * num + off) / den), floor also for negative values.  Audio and I/Q: den = 1, num and off as above.
+ *   Wideband: num = D, den = U, off = (-d_f - W/2) * D + D - 1 - (T - 1) div 2 with T the prototype's tap count -- the
+ *   map above at U = 1.
  * gnuais_batch_info "frame_times" (0 / 1) and "rows" (n). */
 #define GNUAIS_INPUT_AUDIO    0
 #define GNUAIS_INPUT_IQ       1
@@ -388,11 +432,13 @@ int  gnuais_batch_history(gnuais_batch *b, int16_t *h_out);
 int  gnuais_batch_frame_times(gnuais_batch *b, int on);
 int  gnuais_batch_drain_frames_timed(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
 int  gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long long *off);
+int  gnuais_batch_time_map_ratio(const gnuais_batch *b, int kind, long long *num, long long *den, long long *off);
 /* gnuais_nmea_from_frames() with an NMEA 4.10 TAG block in front of EVERY sentence of a frame whose time is known:
  *   \c:<unix>*hh\!AIVDM,...      <unix> = epoch_s + floor((times[i] * mul + off) / rate_hz), decimal, floor also for
  * negative values; hh = XOR of the characters between the backslashes up to the '*', two upper-case hex digits.
  * times[i] = -1: no tag.  mul / off: gnuais_batch_time_map(); rate_hz: the rate of the INPUT samples (> 0); epoch_s:
- * the UNIX second of input sample 0.  With the tags removed the bytes are those of gnuais_nmea_from_frames(); seqnr,
+ * the UNIX second of input sample 0.  With a map from gnuais_batch_time_map_ratio() pass mul = num, off and rate_hz = the
+ * input rate * den: floor(floor(a / den) / rate) = floor(a / (den * rate)), so no other entry is needed.  With the tags removed the bytes are those of gnuais_nmea_from_frames(); seqnr,
  * out == NULL and GNUAIS_E_OVERFLOW as there.  Host code. */
 int  gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *times, int n_frames, uint8_t *seqnr,
 				    int n_channels, long long mul, long long off, long long rate_hz,
@@ -611,6 +657,10 @@ int  gnuais_node_run(gnuais_node *nd, const int16_t *const *d_samples, int len, 
 int  gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len);
 /* the same with the pairs already on the devices: d_iq[i] = shard i's DEVICE slab int16 [len][n_channels of shard i][2] */
 int  gnuais_node_run_iq(gnuais_node *nd, const int16_t *const *d_iq, int len, void *const *streams);
+/* wideband in at a rational ratio (gnuais_batch_resampler): configures every shard, under gnuais_node_channeliser's rule;
+ * the node's wideband run calls then take len a multiple of down with len * up / down <= max_len */
+int  gnuais_node_resampler(gnuais_node *nd, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                           const int16_t *taps, int n_taps);
 /* wideband in (gnuais_batch_channeliser): configures every shard; a shard whose first channel or channel count is not a
  * multiple of n_offsets is GNUAIS_E_ARG (the message names it) */
 int  gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,

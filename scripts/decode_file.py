@@ -11,6 +11,10 @@
                                                       # .cf32 / .cfile, int16: .cs16): the format defaults to the one the
                                                       # extension names; the file goes to the device in its native format and
                                                       # is converted where the channeliser loads it
+  python scripts/decode_file.py rtl.cu8 --wideband auto --rate 2048000
+                                                      # any rate with 48000 / rate = U / D, U <= 64, D <= 1024 (250 k, 1.024 M,
+                                                      # 2 M, 2.048 M, 2.5 M, ...): the ratio comes from the rate, the device
+                                                      # resamples by U / D; the file's tail is trimmed to a multiple of D
   python scripts/decode_file.py iq.wav --iq --afc 2048
                                                       # --iq / --wideband: remove each receiver's carrier error on the device
                                                       # (an SDR's oscillator), estimated over a window of that many samples;
@@ -26,6 +30,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 
+def wideband_arg(v):
+    return "auto" if v == "auto" else int(v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path")
@@ -33,9 +41,10 @@ def main():
     ap.add_argument("--text", action="store_true")
     ap.add_argument("--iq", action="store_true", help="the channels are (I, Q) pairs: 2N channels decode as N receivers "
                                                       "through the device's FM discriminator")
-    ap.add_argument("--wideband", type=int, default=0, metavar="D",
+    ap.add_argument("--wideband", type=wideband_arg, default=0, metavar="D|auto",
                     help="the (I, Q) pairs are wide streams at D times the chain's rate: tune to every --offsets, "
-                         "decimate by D on the device, one receiver per stream and offset (receiver s*K + k)")
+                         "decimate by D on the device, one receiver per stream and offset (receiver s*K + k); auto: at "
+                         "any rate, resampled by the ratio U / D = 48000 / rate (gnuais_batch_resampler)")
     ap.add_argument("--offsets", default="-25000,25000", help="--wideband: offsets in Hz from the tuned frequency")
     ap.add_argument("--rate", type=int, default=0, help="--wideband with --raw: the input rate in Hz")
     ap.add_argument("--format", choices=["cu8", "cs8", "cs16", "cf32"], default=None,
@@ -45,7 +54,9 @@ def main():
     ap.add_argument("--afc", type=int, default=0, metavar="W",
                     help="--iq / --wideband: carrier-error correction over a window of W samples (a multiple of 128; "
                          "2048 suits 48 kHz), 0 = off")
-    ap.add_argument("--call", type=int, default=48000, help="frames per device call (at the chain's rate)")
+    ap.add_argument("--call", type=int, default=48000,
+                    help="frames per device call (at the chain's rate; --wideband auto: rounded down to whole periods of U rows, "
+                         "at least one)")
     ap.add_argument("--times", action="store_true",
                     help="a TAG block with the UNIX second of reception in front of every sentence (the frame's receive time "
                          "in input samples, gnuais_batch_frame_times)")
@@ -101,8 +112,8 @@ def write_sentences(a, b, seq, kind, rate):
     from gnuais_amd import messages_from_frames, nmea_tagged_from_frames
     if a.times:
         frames, times = b.drain_frames_timed()
-        mul, off = b.time_map(kind)
-        out = nmea_tagged_from_frames(frames, times, seq, mul, off, rate, a.start)
+        num, den, off = b.time_map_ratio(kind)         # index = (t * num + off) // den: floor(index / rate) in one division
+        out = nmea_tagged_from_frames(frames, times, seq, num, off, rate * den, a.start)
     else:
         nmea, text = messages_from_frames(b.drain_frames(), seq)
         out = text if a.text else nmea
@@ -126,30 +137,42 @@ def decode_wideband(a, rate, x, fmt=None):
     """x: int16 [len][2M] from a WAV or int16 file, or (fmt given) [len][M][2] in the format's own dtype"""
     import torch
     from gnuais_amd import ReceiverBatch, io, messages_from_frames
-    D = a.wideband
+    import math
+    if a.wideband == "auto":
+        if rate <= 0:
+            sys.exit(f"{a.path}: --wideband auto needs the input rate (--rate for raw files)")
+        U, D = 48000 // math.gcd(rate, 48000), rate // math.gcd(rate, 48000)
+        if (U >= D and (U, D) != (1, 1)) or U > 64 or D > 1024:       # 48000 itself: the channeliser at D = 1
+            sys.exit(f"{a.path}: input rate {rate} Hz is {D}/{U} of the chain's 48000 Hz: outside 1 <= U <= 64, U < D <= 1024")
+    else:
+        U, D = 1, a.wideband
     offsets = [int(v) for v in a.offsets.split(",") if v.strip()]
     if fmt is None and x.shape[1] % 2:
         sys.exit(f"{a.path}: --wideband needs an even channel count (I, Q per stream), the file has {x.shape[1]}")
-    if rate <= 0 or rate % D or rate // D != 48000:
+    if rate <= 0 or rate * U != 48000 * D:              # auto: true by construction
         sys.exit(f"{a.path}: input rate {rate} Hz / {D} is not the chain's 48000 Hz (--rate for raw files)")
     M = x.shape[1] if fmt else x.shape[1] // 2
     n_ch = M * len(offsets)
     x = x[: x.shape[0] // D * D].reshape(-1, M, 2)
-    b = ReceiverBatch(n_ch, max_len=a.call)
-    b.channeliser(D, rate, offsets)
+    b = ReceiverBatch(n_ch, max_len=max(a.call, U))
+    if a.wideband == "auto":
+        b.channeliser_for_rate(rate, offsets)
+    else:
+        b.channeliser(D, rate, offsets)
     if a.afc:
         b.afc(a.afc)
-        x = afc_flush(x, a.afc // 2 * D, fmt)
+        x = afc_flush(x, -(-(a.afc // 2) // U) * D, fmt)
     seq = np.zeros(n_ch, dtype=np.uint8)
     if a.times:
         b.frame_times(True)
-    for part in io.chunks(x, a.call * D):
+    # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
+    for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
         write_sentences(a, b, seq, "wideband", rate)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
-    afc_report(a, b, rate // D)
+    afc_report(a, b, 48000)
 
 
 if __name__ == "__main__":

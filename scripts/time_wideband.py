@@ -12,6 +12,13 @@
                                                   share of the byte and issue bounds
   ... --format cu8|cs8|cf32                       the same legs, --kernel-only and --summarise on wide samples of that format
                                                   (the int16 streams quantised to it), converted where the kernel loads them
+  python scripts/time_wideband.py --ratio U/D --kernel-only [--streams M] [--wide N] [--format F] --calls 20
+                                                  the rational channeliser (resampler.hip) alone at out rate = in rate * U / D
+                                                  on random samples, for rocprofv3 as above; 1/D with D <= 64 is the integer
+                                                  kernel, so `--ratio 1/21` and `--ratio 3/64` compare the two at nearly the
+                                                  same wide samples per output row
+  python scripts/time_wideband.py --summarise STATS.csv --ratio U/D [--streams M] [--wide N]
+                                                  the fast-form kernels of that stats file as ns per wide sample per stream
   python scripts/time_wideband.py --shape W2 --host-path [--streams M]
                                                   run_wideband_fmt_host on cu8 against run_wideband_host on the same samples
                                                   widened to int16, alternating legs: ms per call and GB/s over the bus
@@ -101,6 +108,45 @@ def summarise(path, shape, fmt="cs16"):
                 share_of_issue_bound=round(t_valu / ms, 3), valu_per_row_per_stream=valu_per_row(K, D, fmt=fmt))
 
 
+def ratio_shape(a):
+    """--ratio U/D: (U, D, streams, wide samples per call: --wide rounded down to a multiple of D)"""
+    U, D = (int(v) for v in a.ratio.split("/"))
+    return U, D, a.streams or 8192, a.wide // D * D
+
+
+def ratio_kernel_only(a):
+    import torch
+    from gnuais_amd import ReceiverBatch
+    U, D, M, n = ratio_shape(a)
+    K, rows = len(OFFSETS), n // D * U
+    dt = {"cs16": torch.int16, "cu8": torch.uint8, "cs8": torch.int8}.get(a.format)
+    if a.format == "cf32":
+        x = torch.rand((n, M, 2), device="cuda") * 2.0 - 1.0
+    else:
+        info = torch.iinfo(dt)
+        x = torch.randint(info.min, info.max + 1, (n, M, 2), dtype=dt, device="cuda")
+    b = ReceiverBatch(M * K, max_len=rows)
+    b.resampler(U, D, 1000 * D, OFFSETS)          # the mixer periods depend on the rate; any rate times the kernel alike
+    fmt = None if a.format == "cs16" else a.format
+    for _ in range(a.calls):
+        b.channelise(x, fmt=fmt)
+    torch.cuda.synchronize()
+    print(f"{a.calls} calls at {U}/{D}, {M} streams x {K} offsets, {n} wide samples -> {rows} rows, {a.format}")
+
+
+def summarise_ratio(a):
+    U, D, M, n = ratio_shape(a)
+    out = []
+    for r in csv.DictReader(open(a.summarise)):
+        name = r.get("Name", r.get("KernelName", ""))
+        if "resampler_kernel" in name or "channeliser_kernel" in name or "channeliser_fmt_kernel" in name:
+            per = lambda key: round(float(r.get(key, 0)) / (float(n) * M), 6)
+            out.append(dict(kernel=name, calls=int(r.get("Calls", 0)), ratio=a.ratio, streams=M, wide_samples=n,
+                            mean_ms=round(float(r.get("AverageNs", 0)) / 1e6, 4),
+                            ns_per_wide_sample_per_stream=dict(mean=per("AverageNs"), min=per("MinNs"), max=per("MaxNs"))))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=sorted(SHAPES), default="W3")
@@ -113,9 +159,16 @@ def main():
                          "one profiler run holds them side by side on one box and clock")
     ap.add_argument("--host-path", action="store_true", help="cu8 in native bytes against the same widened to int16")
     ap.add_argument("--streams", type=int, default=0, help="--host-path: streams instead of the shape's")
+    ap.add_argument("--ratio", metavar="U/D", help="the rational channeliser at this ratio (--kernel-only, --summarise)")
+    ap.add_argument("--wide", type=int, default=262144, help="--ratio: wide samples per call (rounded down to a multiple of D)")
     ap.add_argument("--out")
     a = ap.parse_args()
-    if a.summarise:
+    if a.ratio and a.summarise:
+        res = summarise_ratio(a)
+    elif a.ratio:
+        assert a.kernel_only, "--ratio times the kernel alone: with --kernel-only or --summarise"
+        return ratio_kernel_only(a)
+    elif a.summarise:
         res = summarise(a.summarise, a.shape, a.format)
     else:
         import torch
