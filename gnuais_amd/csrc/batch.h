@@ -95,6 +95,21 @@ struct Stream {
 
 } // namespace gnuais
 
+namespace gnuais {
+// The wide stage in front of the discriminator (wide_kernels.h): out rate = in rate * U / D, U = 1 for
+// gnuais_batch_channeliser.  The configuration, the device tables, the carry (the last H = ceil((T-1)/U) wide samples of
+// each stream, double-buffered: a launch reads hist[cur] and writes the other) and the wide-sample count n.
+struct WideStage {
+    int K = 0, U = 1, D = 0, T = 0, H = 0, R = 0, NA = 0;   // K == 0: not configured; NA: the fast form's accumulators, 0 = direct
+    int per[CHAN_MAX_K] = {}, off[CHAN_MAX_K] = {};
+    Buf<uint32_t> mix, poly, hist[2];
+    Buf<int32_t> groups;            // the fast form's group table at a rational ratio; none: the integer form's kernels
+    Buf<int16_t> taps;
+    int cur = 0;
+    unsigned long long n = 0;
+};
+} // namespace gnuais
+
 // The stages a call may pass through, in launch order: the channeliser, the discriminator, the carrier-error stage
 // (gnuais_batch_afc, when it is on), the chain (K1 .. K3)
 enum Stage { CHAN, DISC, AFC, CHAIN, N_STAGES };
@@ -237,7 +252,7 @@ struct gnuais_batch {
     // stage it passes through, when that stream is not s (drain()).  This covers two hazards.  A stage's carry goes
     // from launch to launch in stream order: the channeliser's history, the discriminator's previous pair, the chain's
     // FIR history and peaks.  And a stage in front of the chain overwrites an intermediate buffer whose reader is the
-    // next stage of the previous call, on that call's stream: ch_iq is read by the discriminator, iq_audio by K1 or the
+    // next stage of the previous call, on that call's stream: wide_iq is read by the discriminator, iq_audio by K1 or the
     // AFC stage, afc_audio by K1.  The AFC stage's delay line, block sums and estimates are carries of the first kind.
     struct { hipStream_t s = nullptr; bool used = false; } last[N_STAGES];
     int last_len = 0;
@@ -249,22 +264,10 @@ struct gnuais_batch {
     // pair an I/Q call saw, per channel -- and the audio it writes for the chain, [max_len][N] (allocated on first use).
     Buf<int16_t> iq_prev;                       // [N][2]
     Buf<int16_t> iq_audio;
-    // wideband in (gnuais_batch_channeliser / _run_wideband, channeliser.hip): the configuration, the device tables, the
-    // carry (the last T-1 wide samples of each stream, double-buffered: a launch reads one and writes the other), the
-    // wide-sample count n and the narrowband I/Q it writes for the discriminator, [max_len][N][2] (allocated on first use).
-    int ch_K = 0, ch_D = 0, ch_T = 0, ch_R = 0, ch_NA = 0;  // ch_K == 0: not configured
-    // gnuais_batch_resampler (resampler.hip): out rate = in rate * ch_U / ch_D; ch_U == 1 with ch_D <= 64 is the integer
-    // channeliser and its kernels.  ch_H: the carry's rows, T - 1 there and ceil((T - 1) / U) here; ch_rational: the
-    // launch goes to resampler.hip (ch_poly then holds its pair table, ch_groups its group table)
-    int ch_U = 1, ch_H = 0;
-    bool ch_rational = false;
-    Buf<int32_t> ch_groups;
-    int ch_per[CHAN_MAX_K] = {}, ch_off[CHAN_MAX_K] = {};
-    Buf<uint32_t> ch_mix, ch_poly, ch_hist[2];
-    Buf<int16_t> ch_taps;
-    int ch_cur = 0;
-    unsigned long long ch_n = 0;
-    Buf<int16_t> ch_iq;
+    // wideband in (gnuais_batch_channeliser / _resampler / _run_wideband): the wide stage, and the narrowband I/Q it
+    // writes for the discriminator, [max_len][N][2] (allocated on first use)
+    WideStage wide;
+    Buf<int16_t> wide_iq;
     // the carrier-error stage (gnuais_batch_afc, afc.hip; 0 = off): the window W, the rows n it has taken, the ring of
     // block sums [afc_nb][N][2], the delay line [W/2][N], the estimates of the last call [max_len/64 + 2][N] with the row
     // that serves the last output row (-1: none yet), and the corrected audio it writes for the chain, [max_len][N]

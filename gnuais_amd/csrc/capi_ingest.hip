@@ -11,8 +11,8 @@ static Form form(const gnuais_batch *b, FormId f, int fmt = GNUAIS_FMT_CS16)
     switch (f) {
     case AUDIO: return {2, b->N, 1, 1u << CHAIN};
     case IQ: return {4, b->N, 1, 1u << DISC | (b->afc_W ? 1u << AFC : 0u) | 1u << CHAIN};
-    default: return {wide_format_bytes(fmt), b->ch_K ? b->N / b->ch_K : 0, b->ch_D, 1u << CHAN | form(b, IQ).stages,
-                 b->ch_U};
+    default: return {wide_format_bytes(fmt), b->wide.K ? b->N / b->wide.K : 0, b->wide.D, 1u << CHAN | form(b, IQ).stages,
+                 b->wide.U};
     }
 }
 
@@ -32,14 +32,25 @@ static int alloc_checked(gnuais_batch *b, Buf<T> &p, size_t bytes, const char *w
     return GNUAIS_OK;
 }
 
-// the channeliser's carry and sample count (configuration kept)
+// a host table onto the device (none for an empty one)
+template <class T>
+static int to_device(Buf<T> &p, const std::vector<T> &v)
+{
+    if (v.empty()) return GNUAIS_OK;
+    HIP_TRY(p.alloc(sizeof(T) * v.size()));
+    HIP_TRY(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return GNUAIS_OK;
+}
+
+// the wide stage's carry and sample count (configuration kept)
 int gnuais::chan_zero_state(gnuais_batch *b)
 {
-    if (b->ch_K)
-        for (auto &p : b->ch_hist)
-            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) b->ch_H * (size_t) (b->N / b->ch_K)));
-    b->ch_cur = 0;
-    b->ch_n = 0;
+    WideStage &w = b->wide;
+    if (w.K)
+        for (auto &p : w.hist)
+            if (p) HIP_TRY(hipMemset(p, 0, sizeof(uint32_t) * (size_t) w.H * (size_t) (b->N / w.K)));
+    w.cur = 0;
+    w.n = 0;
     b->last[CHAN].used = false;
     return GNUAIS_OK;
 }
@@ -157,26 +168,10 @@ int gnuais_batch_afc_estimate(gnuais_batch *b, int16_t *h_out)
     return GNUAIS_OK;
 }
 
-// ---- wideband in (include/gnuais_hip.h): the channeliser (channeliser.hip) in front of the discriminator ----
+// ---- wideband in (include/gnuais_hip.h): the wide stage (wide_kernels.h, planned by resample_plan.cpp) in front of the
+// discriminator ----
 
 static long long rnd_away(double x) { return lround(x); }
-
-static int chan_default_taps(int D, std::vector<int16_t> &h)
-{
-    const int T = 16 * D + 1;
-    std::vector<double> g((size_t) T);
-    double G = 0.0;
-    for (int j = 0; j < T; ++j) {
-        const double w = 0.42 - 0.5 * cos(2.0 * M_PI * j / (T - 1)) + 0.08 * cos(4.0 * M_PI * j / (T - 1));
-        const double x = 0.75 * (j - 8 * D) / D;
-        const double s = (x == 0.0) ? 1.0 : sin(M_PI * x) / (M_PI * x);
-        g[(size_t) j] = w * s;
-        G += g[(size_t) j];
-    }
-    h.resize((size_t) T);
-    for (int j = 0; j < T; ++j) h[(size_t) j] = (int16_t) rnd_away(g[(size_t) j] * 32768.0 / G);
-    return T;
-}
 
 static long long gcd_ll(long long a, long long b)
 {
@@ -207,7 +202,8 @@ int gnuais_channeliser_default_taps(int decim, int16_t *out, int cap, int *n_tap
 {
     if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser_default_taps: decim must be 1..64");
     std::vector<int16_t> h;
-    const int T = chan_default_taps(decim, h);
+    resample_default_taps(1, decim, h);
+    const int T = (int) h.size();
     if (n_taps) *n_taps = T;
     if (!out) return GNUAIS_OK;
     if (cap < T) return fail(GNUAIS_E_ARG, "channeliser_default_taps: cap < 16*decim + 1");
@@ -227,18 +223,7 @@ int gnuais_channeliser_mixer_table(int in_rate_hz, int offset_hz, int16_t *out, 
     return GNUAIS_OK;
 }
 
-// What a configuration of the wide stage consists of, built on the host by gnuais_batch_channeliser (U = 1, its own
-// kernels) or gnuais_batch_resampler (resampler.hip) and put on the device by chan_install()
-struct ChanConfig {
-    int U = 1, D = 0, R = 0, K = 0, NA = 0, H = 0;
-    bool rational = false;
-    std::vector<int16_t> h, mix;
-    std::vector<uint32_t> poly;        // the fast form's tap pairs (either kernel's layout)
-    std::vector<int32_t> groups;       // resampler.hip's group table
-    int per[CHAN_MAX_K], off[CHAN_MAX_K], total = 0;
-};
-
-// the checks of rate and offsets both configurations share, in the name of the entry `who`: before the taps' checks
+// the checks of rate and offsets both entries share, in the name of the entry `who`: before the taps' checks
 static int chan_shape_check(const gnuais_batch *b, const char *who, int in_rate_hz, int n_offsets)
 {
     char msg[200];
@@ -253,62 +238,54 @@ static int chan_shape_check(const gnuais_batch *b, const char *who, int in_rate_
     return GNUAIS_OK;
 }
 
-// the mixer periods' check and the mixer tables (C lo, S hi): behind the taps' checks
-static int chan_mixers(const char *who, int in_rate_hz, const int32_t *offsets_hz, int n_offsets, ChanConfig &c)
+// Behind an entry's own checks of the ratio and of the prototype h, in the name of the entry `who`: the mixer periods'
+// check, the mixer tables (C lo, S hi) and the plan (resample_plan.h; na: the fast form's accumulators for the entry's
+// kernels, 0 = the direct form; `rational`: with the group table), then all of it onto the device (synchronises it);
+// zeroes the carry and the sample count.  A failure behind the checks leaves the stage unconfigured.
+static int wide_configure(gnuais_batch *b, const char *who, int up, int down, int in_rate_hz, const int32_t *offsets_hz,
+                          int n_offsets, const std::vector<int16_t> &h, int na, bool rational)
 {
     char msg[200];
-    c.K = n_offsets;
-    c.R = in_rate_hz;
-    c.total = 0;
-    for (int k = 0; k < c.K; ++k) {
-        c.per[k] = chan_period(in_rate_hz, offsets_hz[k]);
-        if (!c.per[k]) {
+    const int K = n_offsets, T = (int) h.size();
+    int per[CHAN_MAX_K], off[CHAN_MAX_K], total = 0;
+    for (int k = 0; k < K; ++k) {
+        per[k] = chan_period(in_rate_hz, offsets_hz[k]);
+        if (!per[k]) {
             snprintf(msg, sizeof msg, "%s: offset %d Hz at %d Hz has a mixer period above 2^20", who, (int) offsets_hz[k],
                      in_rate_hz);
             return fail(GNUAIS_E_ARG, msg);
         }
-        c.off[k] = c.total;
-        c.total += c.per[k];
+        off[k] = total;
+        total += per[k];
     }
-    c.mix.resize(2 * (size_t) c.total);
-    for (int k = 0; k < c.K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], c.per[k], c.mix.data() + 2 * (size_t) c.off[k]);
-    return GNUAIS_OK;
-}
+    std::vector<int16_t> mix(2 * (size_t) total);
+    for (int k = 0; k < K; ++k) chan_mixer(in_rate_hz, offsets_hz[k], per[k], mix.data() + 2 * (size_t) off[k]);
+    ResamplePlan p;
+    if (na) resample_plan(up, down, h.data(), T, na, p);
+    std::vector<int32_t> groups;
+    if (na && rational)
+        for (const ResampGroup &g : p.groups) groups.insert(groups.end(), {g.first, g.size, g.base});
 
-// the configuration onto the device (synchronises it); zeroes the carry and the sample count
-static int chan_install(gnuais_batch *b, const ChanConfig &c)
-{
     if (int rc = set_device(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    for (Buf<uint32_t> *p : {&b->ch_mix, &b->ch_poly, &b->ch_hist[0], &b->ch_hist[1]}) HIP_TRY(p->release());
-    HIP_TRY(b->ch_taps.release());
-    HIP_TRY(b->ch_groups.release());
-    b->ch_K = 0;
-    const int T = (int) c.h.size();
-    const size_t M = (size_t) (b->N / c.K);
-    HIP_TRY(b->ch_mix.alloc(sizeof(uint32_t) * (size_t) c.total));
-    HIP_TRY(hipMemcpy(b->ch_mix, c.mix.data(), sizeof(uint32_t) * (size_t) c.total, hipMemcpyHostToDevice));
-    HIP_TRY(b->ch_taps.alloc(sizeof(int16_t) * (size_t) T));
-    HIP_TRY(hipMemcpy(b->ch_taps, c.h.data(), sizeof(int16_t) * (size_t) T, hipMemcpyHostToDevice));
-    if (!c.poly.empty()) {
-        HIP_TRY(b->ch_poly.alloc(sizeof(uint32_t) * c.poly.size()));
-        HIP_TRY(hipMemcpy(b->ch_poly, c.poly.data(), sizeof(uint32_t) * c.poly.size(), hipMemcpyHostToDevice));
-    }
-    if (!c.groups.empty()) {
-        HIP_TRY(b->ch_groups.alloc(sizeof(int32_t) * c.groups.size()));
-        HIP_TRY(hipMemcpy(b->ch_groups, c.groups.data(), sizeof(int32_t) * c.groups.size(), hipMemcpyHostToDevice));
-    }
-    if (c.H > 0)
-        for (auto &p : b->ch_hist) HIP_TRY(p.alloc(sizeof(uint32_t) * (size_t) c.H * M));
-    b->ch_K = c.K;
-    b->ch_U = c.U;
-    b->ch_D = c.D;
-    b->ch_T = T;
-    b->ch_H = c.H;
-    b->ch_R = c.R;
-    b->ch_NA = c.NA;
-    b->ch_rational = c.rational;
-    for (int k = 0; k < c.K; ++k) { b->ch_per[k] = c.per[k]; b->ch_off[k] = c.off[k]; }
+    b->wide = WideStage{};
+    WideStage w;
+    HIP_TRY(w.mix.alloc(sizeof(uint32_t) * (size_t) total));
+    HIP_TRY(hipMemcpy(w.mix, mix.data(), sizeof(uint32_t) * (size_t) total, hipMemcpyHostToDevice));
+    if (int rc = to_device(w.taps, h)) return rc;
+    if (int rc = to_device(w.poly, p.pairs)) return rc;
+    if (int rc = to_device(w.groups, groups)) return rc;
+    w.H = (T - 1 + up - 1) / up;
+    if (w.H > 0)
+        for (auto &q : w.hist) HIP_TRY(q.alloc(sizeof(uint32_t) * (size_t) w.H * (size_t) (b->N / K)));
+    w.K = K;
+    w.U = up;
+    w.D = down;
+    w.T = T;
+    w.R = in_rate_hz;
+    w.NA = na;
+    for (int k = 0; k < K; ++k) { w.per[k] = per[k]; w.off[k] = off[k]; }
+    b->wide = std::move(w);
     if (int rc = chan_zero_state(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return GNUAIS_OK;
@@ -320,45 +297,18 @@ int gnuais_batch_channeliser(gnuais_batch *b, int decim, int in_rate_hz, const i
     if (!b || !offsets_hz) return fail(GNUAIS_E_ARG, "channeliser: NULL argument");
     if (decim < 1 || decim > 64) return fail(GNUAIS_E_ARG, "channeliser: decim must be 1..64");
     if (int rc = chan_shape_check(b, "channeliser", in_rate_hz, n_offsets)) return rc;
-    ChanConfig c;
-    std::vector<int16_t> &h = c.h;
-    if (!taps || n_taps == 0) {
-        chan_default_taps(decim, h);
-    } else {
-        if (n_taps < 1 || n_taps > 1025) return fail(GNUAIS_E_ARG, "channeliser: n_taps must be 1..1025");
-        h.assign(taps, taps + n_taps);
-    }
-    const int T = (int) h.size();
-    long long sum = 0;
-    for (int16_t v : h) {
-        if (v == -32768) return fail(GNUAIS_E_ARG, "channeliser: a tap is -32768 (|h| <= 32767)");
-        sum += std::abs((int) v);
-    }
-    if (sum > 65535) return fail(GNUAIS_E_ARG, "channeliser: sum |h| exceeds 65535");
-    if (int rc = chan_mixers("channeliser", in_rate_hz, offsets_hz, n_offsets, c)) return rc;
-    // the fast form's tap pairs POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q])
-    const int D = decim, K = n_offsets;
-    const int NA = channeliser_fast_na(K, T, D);
-    if (NA) {
-        const int NP = (D + 1) / 2;
-        c.poly.assign((size_t) NP * NA, 0u);
-        auto tap = [&](int a, int r) -> int {
-            if (r >= D) return 0;
-            const int j = a * D + D - 1 - r;
-            return j < T ? h[(size_t) j] : 0;
-        };
-        for (int q = 0; q < NP; ++q)
-            for (int a = 0; a < NA; ++a)
-                c.poly[(size_t) q * NA + a] = (uint32_t) (uint16_t) tap(a, 2 * q) | ((uint32_t) (uint16_t) tap(a, 2 * q + 1) << 16);
-    }
-    c.U = 1;
-    c.D = D;
-    c.NA = NA;
-    c.H = T - 1;
-    return chan_install(b, c);
+    std::vector<int16_t> h;
+    if (!taps || n_taps == 0) resample_default_taps(1, decim, h);
+    else if (n_taps < 1 || n_taps > 1025) return fail(GNUAIS_E_ARG, "channeliser: n_taps must be 1..1025");
+    else h.assign(taps, taps + n_taps);
+    // U = 1: the one phase is the whole prototype
+    static const char *const why[] = {"", "", "channeliser: a tap is -32768 (|h| <= 32767)", "channeliser: sum |h| exceeds 65535"};
+    if (const int r = resample_check_taps(1, h.data(), (int) h.size())) return fail(GNUAIS_E_ARG, why[r]);
+    return wide_configure(b, "channeliser", 1, decim, in_rate_hz, offsets_hz, n_offsets, h,
+                          channeliser_fast_na(n_offsets, (int) h.size(), decim), false);
 }
 
-// ---- wideband in at a rational ratio U/D (include/gnuais_hip.h): resampler.hip, planned by resample_plan.cpp ----
+// ---- wideband in at a rational ratio U/D (include/gnuais_hip.h) ----
 
 static int resampler_ratio_check(const char *who, int up, int down)
 {
@@ -430,26 +380,13 @@ int gnuais_batch_resampler(gnuais_batch *b, int up, int down, int in_rate_hz, co
     // the integer channeliser's own configuration and kernels: one path for U = 1, D <= 64
     if (up == 1 && down <= 64) return gnuais_batch_channeliser(b, down, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
     if (int rc = chan_shape_check(b, "resampler", in_rate_hz, n_offsets)) return rc;
-    ChanConfig c;
-    if (!taps || n_taps == 0) resample_default_taps(up, down, c.h);
+    std::vector<int16_t> h;
+    if (!taps || n_taps == 0) resample_default_taps(up, down, h);
     else if (n_taps < 1 || n_taps > RESAMP_MAX_TAPS) return fail(GNUAIS_E_ARG, "resampler: n_taps must be 1..16385");
-    else c.h.assign(taps, taps + n_taps);
-    const int T = (int) c.h.size();
-    if (int rc = resampler_taps_check("resampler", up, c.h.data(), T)) return rc;
-    if (int rc = chan_mixers("resampler", in_rate_hz, offsets_hz, n_offsets, c)) return rc;
-    c.U = up;
-    c.D = down;
-    c.rational = true;
-    c.NA = resampler_fast_na(c.K, T, down);
-    c.H = (T - 1 + up - 1) / up;
-    if (c.NA) {
-        ResamplePlan p;
-        resample_plan(up, down, c.h.data(), T, c.NA, p);
-        c.poly = std::move(p.pairs);
-        c.groups.resize(3 * (size_t) up);
-        memcpy(c.groups.data(), p.groups.data(), sizeof(int32_t) * 3 * (size_t) up);
-    }
-    return chan_install(b, c);
+    else h.assign(taps, taps + n_taps);
+    if (int rc = resampler_taps_check("resampler", up, h.data(), (int) h.size())) return rc;
+    return wide_configure(b, "resampler", up, down, in_rate_hz, offsets_hz, n_offsets, h,
+                          resampler_fast_na(n_offsets, (int) h.size(), down), true);
 }
 
 // The checks of the entries that take a form's input, in the name of the entry `who` (the device entries of the
@@ -465,14 +402,14 @@ static int check_input(const gnuais_batch *b, FormId id, const void *x, int len,
         snprintf(msg, sizeof msg, "%s: len out of range%s", who, host ? "" : " (max_len)");
     } else if (!wide_format_bytes(fmt)) {
         snprintf(msg, sizeof msg, "%s: unknown sample format %d (GNUAIS_FMT_*)", who, fmt);
-    } else if (!b->ch_K) {
+    } else if (!b->wide.K) {
         snprintf(msg, sizeof msg, "%s: no channeliser configured (call gnuais_batch_channeliser first)", who);
-    } else if (b->ch_U == 1 && (len <= 0 || len % b->ch_D || len / b->ch_D > b->max_len)) {
+    } else if (b->wide.U == 1 && (len <= 0 || len % b->wide.D || len / b->wide.D > b->max_len)) {
         snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of the decimation %d, at most %d * max_len", who,
-                 len, b->ch_D, b->ch_D);
-    } else if (len <= 0 || len % b->ch_D || (long long) (len / b->ch_D) * b->ch_U > b->max_len) {
+                 len, b->wide.D, b->wide.D);
+    } else if (len <= 0 || len % b->wide.D || (long long) (len / b->wide.D) * b->wide.U > b->max_len) {
         snprintf(msg, sizeof msg, "%s: len %d must be a positive multiple of down = %d that gives at most max_len rows "
-                 "(len * %d / %d <= %d)", who, len, b->ch_D, b->ch_U, b->ch_D, b->max_len);
+                 "(len * %d / %d <= %d)", who, len, b->wide.D, b->wide.U, b->wide.D, b->max_len);
     } else if (reinterpret_cast<uintptr_t>(x) % (uintptr_t) wide_format_align(fmt)) {
         snprintf(msg, sizeof msg, "%s: %s wide samples must be %d-byte aligned", who, wide_format_name(fmt),
                  wide_format_align(fmt));
@@ -482,66 +419,36 @@ static int check_input(const gnuais_batch *b, FormId id, const void *x, int len,
     return fail(GNUAIS_E_ARG, msg);
 }
 
-// the launch of a batch configured by gnuais_batch_resampler with U > 1 or D > 64 (resampler.hip)
-static int resampler_launch(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, hipStream_t s)
-{
-    ResampLaunch a{};
-    a.in = d_wide;
-    a.out = reinterpret_cast<uint32_t *>(d_out);
-    a.hist = b->ch_hist[b->ch_cur];
-    a.mix = b->ch_mix;
-    a.pairs = b->ch_poly;
-    a.groups = b->ch_groups;
-    a.taps = b->ch_taps;
-    a.M = b->N / b->ch_K;
-    a.K = b->ch_K;
-    a.U = b->ch_U;
-    a.D = b->ch_D;
-    a.T = b->ch_T;
-    a.H = b->ch_H;
-    a.len = len;
-    const unsigned vec = a.K == 2 ? 8u : a.K == 4 ? 16u : 4u;       // as chan_launch
-    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : b->ch_NA;
-    if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(GNUAIS_E_ARG, "channelise: the output must be 4-byte aligned");
-    for (int k = 0; k < a.K; ++k) {
-        a.per[k] = b->ch_per[k];
-        a.off[k] = b->ch_off[k];
-        a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
-    }
-    HIP_TRY(launch_resampler(a, fmt, b->ch_hist[b->ch_cur ^ 1], s));
-    if (b->ch_H > 0) b->ch_cur ^= 1;
-    b->ch_n += (unsigned long long) len;
-    b->last[CHAN] = {s, true};
-    return GNUAIS_OK;
-}
-
 static int chan_launch(gnuais_batch *b, int fmt, const void *d_wide, int len, int16_t *d_out, hipStream_t s)
 {
-    if (b->ch_rational) return resampler_launch(b, fmt, d_wide, len, d_out, s);
-    ChanLaunch a{};
+    WideStage &w = b->wide;
+    WideLaunch a{};
     a.in = d_wide;
     a.out = reinterpret_cast<uint32_t *>(d_out);
-    a.hist = b->ch_hist[b->ch_cur];
-    a.mix = b->ch_mix;
-    a.poly = b->ch_poly;
-    a.taps = b->ch_taps;
-    a.M = b->N / b->ch_K;
-    a.K = b->ch_K;
-    a.D = b->ch_D;
-    a.T = b->ch_T;
+    a.hist = w.hist[w.cur];
+    a.mix = w.mix;
+    a.poly = w.poly;
+    a.groups = w.groups;
+    a.taps = w.taps;
+    a.M = b->N / w.K;
+    a.K = w.K;
+    a.U = w.U;
+    a.D = w.D;
+    a.T = w.T;
+    a.H = w.H;
     a.len = len;
     // the fast form stores K words per lane as one vector: the output must be aligned to it (else the direct form)
     const unsigned vec = a.K == 2 ? 8u : a.K == 4 ? 16u : 4u;
-    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : b->ch_NA;
+    a.NA = (reinterpret_cast<uintptr_t>(d_out) % vec) ? 0 : w.NA;
     if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(GNUAIS_E_ARG, "channelise: the output must be 4-byte aligned");
     for (int k = 0; k < a.K; ++k) {
-        a.per[k] = b->ch_per[k];
-        a.off[k] = b->ch_off[k];
-        a.ph0[k] = (int) (b->ch_n % (unsigned long long) b->ch_per[k]);
+        a.per[k] = w.per[k];
+        a.off[k] = w.off[k];
+        a.ph0[k] = (int) (w.n % (unsigned long long) w.per[k]);
     }
-    HIP_TRY(launch_channeliser(a, fmt, b->ch_hist[b->ch_cur ^ 1], s));
-    if (b->ch_T > 1) b->ch_cur ^= 1;
-    b->ch_n += (unsigned long long) len;
+    HIP_TRY(launch_wide(a, fmt, w.hist[w.cur ^ 1], s));
+    if (w.H > 0) w.cur ^= 1;
+    w.n += (unsigned long long) len;
     b->last[CHAN] = {s, true};
     return GNUAIS_OK;
 }
@@ -581,7 +488,7 @@ static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *s
     if (int rc = drain(b, f.stages, s)) return rc;
     // the channeliser writes max_len rows of the I/Q form, the discriminator and the AFC max_len rows of the audio form
     if (chan)
-        if (int rc = alloc_checked(b, b->ch_iq, form(b, IQ).bytes_of(b->max_len), who, "the channeliser's I/Q")) return rc;
+        if (int rc = alloc_checked(b, b->wide_iq, form(b, IQ).bytes_of(b->max_len), who, "the channeliser's I/Q")) return rc;
     if (disc)
         if (int rc = alloc_checked(b, b->iq_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the discriminator's audio"))
             return rc;
@@ -589,8 +496,8 @@ static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *s
         if (int rc = alloc_checked(b, b->afc_audio, form(b, AUDIO).bytes_of(b->max_len), who, "the AFC's audio")) return rc;
     const int16_t *x = static_cast<const int16_t *>(in);
     if (chan) {
-        if (int rc = chan_launch(b, fmt, in, len, b->ch_iq, s)) return rc;
-        x = b->ch_iq;
+        if (int rc = chan_launch(b, fmt, in, len, b->wide_iq, s)) return rc;
+        x = b->wide_iq;
     }
     len = len / f.rows * f.up;
     if (disc) {

@@ -1026,11 +1026,11 @@ int gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long 
         *off = -d_f - half_w;
         return GNUAIS_OK;
     case GNUAIS_INPUT_WIDEBAND: {
-        if (!b->ch_K) return fail(GNUAIS_E_STATE, "time_map: no channeliser configured (gnuais_batch_channeliser)");
-        if (b->ch_U > 1)
+        if (!b->wide.K) return fail(GNUAIS_E_STATE, "time_map: no channeliser configured (gnuais_batch_channeliser)");
+        if (b->wide.U > 1)
             return fail(GNUAIS_E_STATE, "time_map: the wide stage resamples by a ratio up / down with up > 1: use "
                                         "gnuais_batch_time_map_ratio");
-        const long long D = b->ch_D, T = b->ch_T;
+        const long long D = b->wide.D, T = b->wide.T;
         *mul = D;
         *off = (-d_f - half_w) * D + D - 1 - (T - 1) / 2;
         return GNUAIS_OK;
@@ -1044,13 +1044,13 @@ int gnuais_batch_time_map(const gnuais_batch *b, int kind, long long *mul, long 
 int gnuais_batch_time_map_ratio(const gnuais_batch *b, int kind, long long *num, long long *den, long long *off)
 {
     if (!b || !num || !den || !off) return fail(GNUAIS_E_ARG, "time_map_ratio: argument");
-    if (kind != GNUAIS_INPUT_WIDEBAND || !b->ch_K || b->ch_U == 1) {      // den = 1: the integer map, with its checks
+    if (kind != GNUAIS_INPUT_WIDEBAND || !b->wide.K || b->wide.U == 1) {      // den = 1: the integer map, with its checks
         *den = 1;
         return gnuais_batch_time_map(b, kind, num, off);
     }
-    const long long d_f = (b->NT + 1) / 2, half_w = b->afc_W / 2, D = b->ch_D, T = b->ch_T;
+    const long long d_f = (b->NT + 1) / 2, half_w = b->afc_W / 2, D = b->wide.D, T = b->wide.T;
     *num = D;
-    *den = b->ch_U;
+    *den = b->wide.U;
     *off = (-d_f - half_w) * D + D - 1 - (T - 1) / 2;
     return GNUAIS_OK;
 }

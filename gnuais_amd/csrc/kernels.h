@@ -161,48 +161,34 @@ hipError_t launch_afc_estimate(const int64_t *blk, int nb, int N, int16_t *est, 
 hipError_t launch_afc_apply(const int16_t *audio, int16_t *delay, const int16_t *est, long long j_lo, int16_t *out, int N,
                             int len, int W, unsigned long long n0, hipStream_t stream);
 
-// ---- wideband in: the channeliser (channeliser.hip) -------------------------------------
-// in [len][M] pairs of sample format fmt (GNUAIS_FMT_*, wide_format.h) -> out [len/D][M*K][2] int16, the definition in
-// include/gnuais_hip.h.  hist [T-1][M] words is the carry (the last T-1 wide samples, converted to int16 pairs), read
-// here; the launch writes the next one into hist_out (another buffer).
+// ---- wideband in: the wide stage (wide_launch.hip over wide_kernels.h; host planning in resample_plan.h) ----
+// in [len][M] pairs of sample format fmt (GNUAIS_FMT_*, wide_format.h) -> out [len*U/D][M*K][2] int16, len a multiple
+// of D, the definitions in include/gnuais_hip.h (gnuais_batch_channeliser: U = 1; gnuais_batch_resampler).  hist [H][M]
+// words is the carry (the last H = ceil((T-1)/U) wide samples, converted to int16 pairs), read here; the launch writes
+// the next one into hist_out (another buffer).
 constexpr int CHAN_MAX_K = 32;       // offsets per stream
-struct ChanLaunch {
+struct WideLaunch {
     const void *in;        // [len][M] pairs in the launch's format; as int16: (I lo, Q hi)
-    uint32_t *out;         // [len/D][M*K]
-    const uint32_t *hist;  // [T-1][M]
-    const uint32_t *mix;   // mixer tables, (C lo, S hi), offset k's at mix + off[k], per[k] entries
-    const uint32_t *poly;  // fast form: [(D+1)/2][NA] tap pairs (channeliser.hip)
-    const int16_t *taps;   // direct form: [T]
-    int M, K, D, T, len;
-    int NA;                // fast form's accumulators per offset (channeliser_fast_na), 0 = direct form
-    int n_groups, seg_rows;                // set by launch_channeliser
-    int per[CHAN_MAX_K], off[CHAN_MAX_K];
-    int ph0[CHAN_MAX_K];   // (n mod per[k]) of the call's first wide sample
-};
-int channeliser_fast_na(int K, int T, int D);    // 0: no fast form for this shape
-hipError_t launch_channeliser(const ChanLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
-// the formats other than GNUAIS_FMT_CS16 (channeliser_fmt.hip); hipErrorInvalidValue for an unknown one
-hipError_t launch_channeliser_fmt(const ChanLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
-
-// ---- wideband in at a rational ratio: the U/D channeliser (resampler.hip; host planning in resample_plan.h) ----
-// in [len][M] pairs of format fmt -> out [len*U/D][M*K][2] int16, len a multiple of D, the definition in
-// include/gnuais_hip.h above gnuais_batch_resampler.  hist [H][M] words is the carry (the last H = ceil((T-1)/U) wide
-// samples, converted), read here; the launch writes the next one into hist_out (another buffer).
-struct ResampLaunch {
-    const void *in;        // [len][M] pairs in the launch's format
     uint32_t *out;         // [len*U/D][M*K]
     const uint32_t *hist;  // [H][M]
-    const uint32_t *mix;   // mixer tables as ChanLaunch::mix
-    const uint32_t *pairs; // fast form: ResamplePlan::pairs at NA accumulators
-    const int32_t *groups; // fast form: [U][3] = ResampGroup
+    const uint32_t *mix;   // mixer tables, (C lo, S hi), offset k's at mix + off[k], per[k] entries
+    const uint32_t *poly;  // fast form: the tap pairs, ResamplePlan::pairs at NA accumulators
     const int16_t *taps;   // direct form: [T]
-    int M, K, U, D, T, H, len;
-    int NA;                // RESAMP_FAST_NA, 0 = direct form
-    int n_groups, seg_rows;                // set by launch_resampler
+    int M, K, D, T, len;
+    int NA;                // fast form's accumulators per offset (channeliser_fast_na / resampler_fast_na), 0 = direct form
+    int n_groups, seg_rows;                // set by launch_wide
     int per[CHAN_MAX_K], off[CHAN_MAX_K];
     int ph0[CHAN_MAX_K];   // (n mod per[k]) of the call's first wide sample
+    const int32_t *groups; // fast form at a rational ratio: [U][3] = ResampGroup; null: the integer form (U = 1, groups of D)
+    int U, H;              // H = T - 1 at U = 1
 };
-hipError_t launch_resampler(const ResampLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
+hipError_t launch_wide(const WideLaunch &a, int fmt, uint32_t *hist_out, hipStream_t stream);
+// The launches of format F's kernels (wide_kernels.h), each defined once in the build, by the unit that holds those
+// kernels: the integer fast form and the direct and carry kernels of int16 input in channeliser.hip, those of the other
+// formats in channeliser_fmt.hip, the rational fast form of every format in resampler.hip.
+template <int F, bool RATIONAL> hipError_t wide_fast_launch(const WideLaunch &a, dim3 grid, hipStream_t stream);
+template <int F> void wide_direct_launch(const WideLaunch &a, dim3 grid, hipStream_t stream);
+template <int F> void wide_carry_launch(const WideLaunch &a, uint32_t *hist_out, hipStream_t stream);
 
 // ---- f1 on the device (nmea_device.hip) ---------------------------------------
 size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);

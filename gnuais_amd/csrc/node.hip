@@ -383,56 +383,45 @@ int gnuais_node_run_iq_host(gnuais_node *nd, const int16_t *h_iq, int len)
     return run_staged(nd, IQ, h_iq, len, "node_run_iq_host", gnuais_batch_run_iq);
 }
 
-int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
-                            const int16_t *taps, int n_taps)
+// gnuais_node_channeliser / _resampler: the shards' rule, then `configure` on every shard's batch; `who`: the entry's name
+static int node_wide_configure(gnuais_node *nd, const char *who, int up, int down, const int32_t *offsets_hz, int n_offsets,
+                               const std::function<int(gnuais_batch *)> &configure)
 {
-    if (!nd || !offsets_hz) return node_fail(GNUAIS_E_ARG, "node_channeliser: NULL argument");
-    if (n_offsets < 1) return node_fail(GNUAIS_E_ARG, "node_channeliser: n_offsets must be >= 1");
+    if (!nd || !offsets_hz) return node_fail(GNUAIS_E_ARG, std::string(who) + ": NULL argument");
+    if (n_offsets < 1) return node_fail(GNUAIS_E_ARG, std::string(who) + ": n_offsets must be >= 1");
     for (size_t i = 0; i < nd->shards.size(); ++i) {
         const Shard &s = *nd->shards[i];
         if (s.first % n_offsets || s.n % n_offsets) {
             char msg[200];
-            snprintf(msg, sizeof msg, "node_channeliser: shard %zu (channels %d..%d) does not start and end on a multiple of "
-                     "n_offsets = %d", i, s.first, s.first + s.n - 1, n_offsets);
+            snprintf(msg, sizeof msg, "%s: shard %zu (channels %d..%d) does not start and end on a multiple of "
+                     "n_offsets = %d", who, i, s.first, s.first + s.n - 1, n_offsets);
             return node_fail(GNUAIS_E_ARG, msg);
         }
     }
     nd->ch_K = 0;
-    const int rc = run_all(nd, [=](Shard &s, size_t) {
-        return gnuais_batch_channeliser(s.b, decim, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
-    });
-    if (rc == GNUAIS_OK) {
-        nd->ch_K = n_offsets;
-        nd->ch_D = decim;
-        nd->ch_U = 1;
-    }
-    return rc;
-}
-
-int gnuais_node_resampler(gnuais_node *nd, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
-                          const int16_t *taps, int n_taps)
-{
-    if (!nd || !offsets_hz) return node_fail(GNUAIS_E_ARG, "node_resampler: NULL argument");
-    if (n_offsets < 1) return node_fail(GNUAIS_E_ARG, "node_resampler: n_offsets must be >= 1");
-    for (size_t i = 0; i < nd->shards.size(); ++i) {
-        const Shard &s = *nd->shards[i];
-        if (s.first % n_offsets || s.n % n_offsets) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "node_resampler: shard %zu (channels %d..%d) does not start and end on a multiple of "
-                     "n_offsets = %d", i, s.first, s.first + s.n - 1, n_offsets);
-            return node_fail(GNUAIS_E_ARG, msg);
-        }
-    }
-    nd->ch_K = 0;
-    const int rc = run_all(nd, [=](Shard &s, size_t) {
-        return gnuais_batch_resampler(s.b, up, down, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
-    });
+    const int rc = run_all(nd, [&](Shard &s, size_t) { return configure(s.b); });
     if (rc == GNUAIS_OK) {
         nd->ch_K = n_offsets;
         nd->ch_D = down;
         nd->ch_U = up;
     }
     return rc;
+}
+
+int gnuais_node_channeliser(gnuais_node *nd, int decim, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                            const int16_t *taps, int n_taps)
+{
+    return node_wide_configure(nd, "node_channeliser", 1, decim, offsets_hz, n_offsets, [=](gnuais_batch *b) {
+        return gnuais_batch_channeliser(b, decim, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
+    });
+}
+
+int gnuais_node_resampler(gnuais_node *nd, int up, int down, int in_rate_hz, const int32_t *offsets_hz, int n_offsets,
+                          const int16_t *taps, int n_taps)
+{
+    return node_wide_configure(nd, "node_resampler", up, down, offsets_hz, n_offsets, [=](gnuais_batch *b) {
+        return gnuais_batch_resampler(b, up, down, in_rate_hz, offsets_hz, n_offsets, taps, n_taps);
+    });
 }
 
 int gnuais_node_afc(gnuais_node *nd, int window)

@@ -1,4 +1,4 @@
-// resample_plan.cpp -- the rational channeliser's host planning (resample_plan.h).  Plain C++.
+// resample_plan.cpp -- the wide stage's host planning (resample_plan.h).  Plain C++.
 #include "resample_plan.h"
 
 #include <math.h>
@@ -93,6 +93,15 @@ int resampler_fast_na(int K, int T, int D)
 {
     if (K < 1 || K > 4) return 0;
     return (T + D - 1) / D <= RESAMP_FAST_NA ? RESAMP_FAST_NA : 0;
+}
+
+int channeliser_fast_na(int K, int T, int D)
+{
+    const int na = (T + D - 1) / D;
+    if (K < 1 || K > 4) return 0;
+    for (int b : {4, 8, 17}) if (na <= b) return b;
+    if (na <= 33 && K <= 2) return 33;
+    return 0;
 }
 
 } // namespace gnuais

@@ -1,6 +1,6 @@
-// resample_plan.h -- what the host decides before the rational U/D channeliser (resampler.hip) can run: the default
-// prototype, the checks of a prototype, and the two tables the fast form reads.  Everything here depends on
-// (U, D, T, taps) alone.  Plain C++, no HIP: resample_plan.cpp is also built for the CPU under ASan + UBSan by
+// resample_plan.h -- what the host decides before the wide stage (wide_kernels.h) can run, at an integer ratio (U = 1,
+// gnuais_batch_channeliser) and at a rational one (gnuais_batch_resampler): the default prototype, the checks of a
+// prototype, the fast form's accumulators and the two tables it reads.  Everything here depends on (U, D, T, taps) alone.  Plain C++, no HIP: resample_plan.cpp is also built for the CPU under ASan + UBSan by
 // tests/test_resampler_cpu.py (tests/c/resample_plan_main.cpp), like fir_plan.cpp.  The definition is in
 // include/gnuais_hip.h above gnuais_batch_resampler.
 //
@@ -8,6 +8,8 @@
 // tick n*U.  Sample n belongs to GROUP g when g*D <= n*U < (g+1)*D: the samples that arrive between the ends of rows
 // g-1 and g.  It feeds rows g + a, a = 0 .. NA-1 (NA = ceil(T / D)), with tap j = (g + a)*D + D-1 - n*U.  Groups repeat
 // with period U rows = D samples: for g = c*U + i the first sample is c*D + first[i] and the taps depend on i alone.
+// At U = 1 there is one group, the D samples from g*D on, and the pair table is the integer channeliser's
+// POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q]).
 #pragma once
 #include <stdint.h>
 
@@ -43,5 +45,7 @@ int resample_check_taps(int up, const int16_t *h, int T);
 void resample_plan(int up, int down, const int16_t *h, int T, int na, ResamplePlan &p);
 // the fast form's accumulators per offset for this shape (RESAMP_FAST_NA), 0 = the direct form
 int resampler_fast_na(int K, int T, int D);
+// the same for gnuais_batch_channeliser, whose fast form has more buckets: 4, 8, 17, and 33 for K <= 2
+int channeliser_fast_na(int K, int T, int D);
 
 } // namespace gnuais

@@ -1,6 +1,6 @@
 // wide_format.h -- the sample formats of wideband input (include/gnuais_hip.h, GNUAIS_FMT_*): how one wide (I, Q) pair
 // lies in memory and how it becomes the int16 pair of the channeliser's definition.  The one statement of each
-// conversion: the kernels (channeliser_body.h) and the host's gnuais_convert_samples (wide_format.cpp) both call these.
+// conversion: the kernels (wide_kernels.h) and the host's gnuais_convert_samples (wide_format.cpp) both call these.
 // Plain C++ for host and device; no HIP needed to include it.
 #pragma once
 #include <stdint.h>

@@ -130,31 +130,29 @@ class ReceiverBatch:
         return self._stage(samples, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
                            lambda n: (n, self.n_channels), self._lib.gnuais_batch_afc_apply)
 
+    def _wide_configure(self, fn, ratio, in_rate_hz, offsets_hz, taps):
+        """channeliser() / resampler(): the library entry `fn` with its ratio arguments, then the rate, offsets and taps"""
+        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        assert off.ndim == 1 and off.size >= 1
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
+        check(fn(self._h, *ratio, int(in_rate_hz), off.ctypes.data, int(off.size),
+                 None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
+        self._chan = (ratio[-1], int(off.size))
+        self._chan_up = ratio[0] if len(ratio) == 2 else 1
+
     def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
         """Configure the wideband channeliser (gnuais_batch_channeliser, defined in include/gnuais_hip.h): the batch's
         n_channels receivers become n_channels / K wide streams x K offsets (receiver s*K + k = stream s at
         offsets_hz[k]), decimated by `decim` from `in_rate_hz`.  taps: int16 sequence, or None for the default design.
         Zeroes the channeliser's carry and sample count."""
-        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
-        assert off.ndim == 1 and off.size >= 1
-        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
-        check(self._lib.gnuais_batch_channeliser(self._h, int(decim), int(in_rate_hz), off.ctypes.data, int(off.size),
-                                                 None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
-        self._chan = (int(decim), int(off.size))
-        self._chan_up = 1
+        self._wide_configure(self._lib.gnuais_batch_channeliser, (int(decim),), in_rate_hz, offsets_hz, taps)
 
     def resampler(self, up: int, down: int, in_rate_hz: int, offsets_hz, taps=None):
         """Configure the wide stage at a rational ratio (gnuais_batch_resampler, defined in include/gnuais_hip.h): as
         channeliser(), with the chain's rate = in_rate_hz * up / down (up < down, no common factor).  Wideband calls then
         take len a multiple of `down` and give len * up / down rows.  taps: the int16 prototype at up * in_rate_hz, or
         None for the default design.  up = 1 with down <= 64 is channeliser(down, ...)."""
-        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
-        assert off.ndim == 1 and off.size >= 1
-        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
-        check(self._lib.gnuais_batch_resampler(self._h, int(up), int(down), int(in_rate_hz), off.ctypes.data, int(off.size),
-                                               None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
-        self._chan = (int(down), int(off.size))
-        self._chan_up = int(up)
+        self._wide_configure(self._lib.gnuais_batch_resampler, (int(up), int(down)), in_rate_hz, offsets_hz, taps)
 
     def channeliser_for_rate(self, in_rate_hz: int, offsets_hz, out_rate_hz: Optional[int] = None):
         """Configure the wide stage for a capture at `in_rate_hz`: the ratio out_rate_hz / in_rate_hz (out_rate_hz: the

@@ -73,26 +73,23 @@ class ReceiverNode:
         self._run_host(samples, lambda x: x.ndim == 3 and x.shape[1] == self.n_channels and x.shape[2] == 2,
                        self._lib.gnuais_node_run_iq_host)
 
-    def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
-        """Wideband in (gnuais_node_channeliser): ReceiverBatch.channeliser on every shard; every shard's first channel
-        and channel count must be multiples of len(offsets_hz)."""
+    def _wide_configure(self, fn, ratio, in_rate_hz, offsets_hz, taps):
         np = self._np
         off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
         t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
-        self._raise(self._lib.gnuais_node_channeliser(self._h, int(decim), int(in_rate_hz), off.ctypes.data, int(off.size),
-                                                      None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
+        self._raise(fn(self._h, *ratio, int(in_rate_hz), off.ctypes.data, int(off.size),
+                       None if t is None else t.ctypes.data, 0 if t is None else int(t.size)))
         self._chan_k = int(off.size)
+
+    def channeliser(self, decim: int, in_rate_hz: int, offsets_hz, taps=None):
+        """Wideband in (gnuais_node_channeliser): ReceiverBatch.channeliser on every shard; every shard's first channel
+        and channel count must be multiples of len(offsets_hz)."""
+        self._wide_configure(self._lib.gnuais_node_channeliser, (int(decim),), in_rate_hz, offsets_hz, taps)
 
     def resampler(self, up: int, down: int, in_rate_hz: int, offsets_hz, taps=None):
         """Wideband in at a rational ratio (gnuais_node_resampler): ReceiverBatch.resampler on every shard, under
         channeliser()'s rule for the shards."""
-        np = self._np
-        off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
-        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16)
-        self._raise(self._lib.gnuais_node_resampler(self._h, int(up), int(down), int(in_rate_hz), off.ctypes.data,
-                                                    int(off.size), None if t is None else t.ctypes.data,
-                                                    0 if t is None else int(t.size)))
-        self._chan_k = int(off.size)
+        self._wide_configure(self._lib.gnuais_node_resampler, (int(up), int(down)), in_rate_hz, offsets_hz, taps)
 
     def afc(self, window: int):
         """Carrier-error correction of I/Q input (gnuais_node_afc): ReceiverBatch.afc on every shard."""

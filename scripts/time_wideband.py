@@ -12,13 +12,14 @@
                                                   share of the byte and issue bounds
   ... --format cu8|cs8|cf32                       the same legs, --kernel-only and --summarise on wide samples of that format
                                                   (the int16 streams quantised to it), converted where the kernel loads them
-  python scripts/time_wideband.py --ratio U/D --kernel-only [--streams M] [--wide N] [--format F] --calls 20
-                                                  the rational channeliser (resampler.hip) alone at out rate = in rate * U / D
-                                                  on random samples, for rocprofv3 as above; 1/D with D <= 64 is the integer
-                                                  kernel, so `--ratio 1/21` and `--ratio 3/64` compare the two at nearly the
-                                                  same wide samples per output row
+  python scripts/time_wideband.py --ratio U/D --kernel-only [--streams M] [--wide N] [--format F] [--offsets K] --calls 20
+                                                  the wide stage alone at out rate = in rate * U / D on random samples, for
+                                                  rocprofv3 as above; 1/D with D <= 64 is the integer form, so `--ratio 1/21`
+                                                  and `--ratio 3/64` compare the two at nearly the same wide samples per
+                                                  output row; --offsets 5 (K > 4) times the direct form
   python scripts/time_wideband.py --summarise STATS.csv --ratio U/D [--streams M] [--wide N]
-                                                  the fast-form kernels of that stats file as ns per wide sample per stream
+                                                  the wide stage's kernels of that stats file (fast, direct, carry) as ns per
+                                                  wide sample per stream
   python scripts/time_wideband.py --shape W2 --host-path [--streams M]
                                                   run_wideband_fmt_host on cu8 against run_wideband_host on the same samples
                                                   widened to int16, alternating legs: ms per call and GB/s over the bus
@@ -35,6 +36,7 @@ import numpy as np
 
 SHAPES = {"W3": (8192, 2, 6, 288000), "W2": (128, 2, 6, 288000)}
 OFFSETS = [-25000, 25000]
+RATIO_OFFSETS = [-25000, 25000, 12000, 0, -7000]     # --ratio --offsets K: the first K
 PAIR_BYTES = {"cs16": 4, "cu8": 2, "cs8": 2, "cf32": 8}
 PEAK_TBS = 8.0
 LANE_OPS_PER_S = 256 * 4 * 16 * 2.4e9    # as scripts/time_iq.py
@@ -85,11 +87,12 @@ def quantise(xd, fmt):
 
 
 def fmt_name(kernel_name, fmt):
-    """whether a rocprofv3 kernel name is the fast form's kernel of format fmt"""
-    if fmt == "cs16":
-        return "channeliser_kernel" in kernel_name
-    f = {"cu8": 1, "cs8": 2, "cf32": 3}[fmt]
-    return "channeliser_fmt_kernel" in kernel_name and kernel_name.replace(" ", "").split(">")[0].endswith(f",{f}")
+    """whether a rocprofv3 kernel name is the fast form's kernel of format fmt: channeliser_kernel<K, NA, F, RATIONAL>"""
+    f = {"cs16": 0, "cu8": 1, "cs8": 2, "cf32": 3}[fmt]
+    if "channeliser_kernel<" not in kernel_name:
+        return False
+    args = kernel_name.replace(" ", "").split("channeliser_kernel<")[1].split(">")[0].split(",")
+    return len(args) == 4 and args[2] == str(f)
 
 
 def summarise(path, shape, fmt="cs16"):
@@ -118,7 +121,8 @@ def ratio_kernel_only(a):
     import torch
     from gnuais_amd import ReceiverBatch
     U, D, M, n = ratio_shape(a)
-    K, rows = len(OFFSETS), n // D * U
+    offsets = RATIO_OFFSETS[:a.offsets]
+    K, rows = len(offsets), n // D * U
     dt = {"cs16": torch.int16, "cu8": torch.uint8, "cs8": torch.int8}.get(a.format)
     if a.format == "cf32":
         x = torch.rand((n, M, 2), device="cuda") * 2.0 - 1.0
@@ -126,7 +130,7 @@ def ratio_kernel_only(a):
         info = torch.iinfo(dt)
         x = torch.randint(info.min, info.max + 1, (n, M, 2), dtype=dt, device="cuda")
     b = ReceiverBatch(M * K, max_len=rows)
-    b.resampler(U, D, 1000 * D, OFFSETS)          # the mixer periods depend on the rate; any rate times the kernel alike
+    b.resampler(U, D, 1000 * D, offsets)          # the mixer periods depend on the rate; any rate times the kernel alike
     fmt = None if a.format == "cs16" else a.format
     for _ in range(a.calls):
         b.channelise(x, fmt=fmt)
@@ -139,7 +143,7 @@ def summarise_ratio(a):
     out = []
     for r in csv.DictReader(open(a.summarise)):
         name = r.get("Name", r.get("KernelName", ""))
-        if "resampler_kernel" in name or "channeliser_kernel" in name or "channeliser_fmt_kernel" in name:
+        if "channeliser_kernel" in name or "channeliser_direct_kernel" in name or "channeliser_carry_kernel" in name:
             per = lambda key: round(float(r.get(key, 0)) / (float(n) * M), 6)
             out.append(dict(kernel=name, calls=int(r.get("Calls", 0)), ratio=a.ratio, streams=M, wide_samples=n,
                             mean_ms=round(float(r.get("AverageNs", 0)) / 1e6, 4),
@@ -160,6 +164,8 @@ def main():
     ap.add_argument("--host-path", action="store_true", help="cu8 in native bytes against the same widened to int16")
     ap.add_argument("--streams", type=int, default=0, help="--host-path: streams instead of the shape's")
     ap.add_argument("--ratio", metavar="U/D", help="the rational channeliser at this ratio (--kernel-only, --summarise)")
+    ap.add_argument("--offsets", type=int, default=2, choices=range(1, len(RATIO_OFFSETS) + 1),
+                    help="--ratio: offsets per stream; 5 takes the direct form")
     ap.add_argument("--wide", type=int, default=262144, help="--ratio: wide samples per call (rounded down to a multiple of D)")
     ap.add_argument("--out")
     a = ap.parse_args()

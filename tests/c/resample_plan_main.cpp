@@ -1,9 +1,11 @@
-// resample_plan_main.cpp -- gnuais_amd/csrc/resample_plan.cpp (the rational channeliser's host planning: plain C++, no
-// GPU) on the CPU under ASan + UBSan, built and run by tests/test_resampler_cpu.py.  For each "up down" pair on the
-// command line: the default prototype, its checks and its tables at the fast form's 17 accumulators, and the
-// invariants of the tables; prints one line per ratio.
+// resample_plan_main.cpp -- gnuais_amd/csrc/resample_plan.cpp (the wide stage's host planning: plain C++, no GPU) on the
+// CPU under ASan + UBSan, built and run by tests/test_resampler_cpu.py.  For each "up down" pair on the command line:
+// the default prototype, its checks and its tables at the fast form's 17 accumulators, and the invariants of the
+// tables; prints one line per ratio.  "poly K D T": the integer channeliser's plan for K offsets, decimation D and the
+// T taps h[j] = (j * 7919 + 13) % 4001 - 2000 -- a line "NA n_pairs", then the pair table, one row of NA words per line.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -17,8 +19,22 @@ static int fail(const char *what, int up, int down)
     return 1;
 }
 
+static int poly(int K, int D, int T)
+{
+    std::vector<int16_t> h((size_t) T);
+    for (int j = 0; j < T; ++j) h[(size_t) j] = (int16_t) ((j * 7919 + 13) % 4001 - 2000);
+    const int na = channeliser_fast_na(K, T, D);
+    ResamplePlan p;
+    if (na) resample_plan(1, D, h.data(), T, na, p);
+    printf("%d %d\n", na, p.n_pairs);
+    for (int q = 0; q < p.n_pairs; ++q)
+        for (int a = 0; a < na; ++a) printf("%u%c", p.pairs[(size_t) q * (size_t) na + (size_t) a], a + 1 < na ? ' ' : '\n');
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 5 && !strcmp(argv[1], "poly")) return poly(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]));
     for (int a = 1; a + 1 < argc; a += 2) {
         const int up = atoi(argv[a]), down = atoi(argv[a + 1]);
         if (resample_check_ratio(up, down)) return fail("ratio refused", up, down);

@@ -1,5 +1,5 @@
 """NumPy restatement of the wideband channeliser (include/gnuais_hip.h, above gnuais_batch_channeliser) in int64 -- the
-yardstick the device's channeliser.hip is held to bit for bit.  The tables use Python's libm-backed math module, as the
+yardstick the device's wide stage (wide_kernels.h) is held to bit for bit.  The tables use Python's libm-backed math module, as the
 library's host code uses the C library.  Test code only."""
 import functools
 import math
@@ -113,7 +113,7 @@ class Channeliser:
 
 
 def fast_na(K: int, T: int, D: int) -> int:
-    """channeliser_fast_na() (channeliser.hip): the fast form's accumulators per offset, 0 = the direct form"""
+    """channeliser_fast_na() (resample_plan.cpp): the fast form's accumulators per offset, 0 = the direct form"""
     na = (T + D - 1) // D
     if K < 1 or K > 4:
         return 0

@@ -1,8 +1,8 @@
 """The rational channeliser's configuration matrix, shared by the CPU tests (tests/test_resampler_cpu.py) and the device
-tests (tests/test_resampler_gpu.py): the smallest shapes at which resampler.hip can go wrong.  It reaches every
-resampler_kernel<K, 17, F> instance, the direct form and the carry copy of every format.
+tests (tests/test_resampler_gpu.py): the smallest shapes at which the wide stage's rational form can go wrong.  It reaches
+every channeliser_kernel<K, 17, F, true> instance, the direct form and the carry copy of every format.
 
-  ratios   2/3 (groups of 2 and 1: the lone-sample pair), 5/6, 3/64, 3/128 (groups of 43, 43, 42), 24/125
+  ratios   2/3 (groups of 2 and 1: the lone-sample pair), 5/6, 3/64, 3/128 (groups of 43, 43, 42), 24/125, 1/65 (U = 1)
   streams  1, 3, 65 (a partial second wave), 130 (two stream groups and a partial third)
   offsets  K = 1..4 on the fast form, K = 5 on the direct form
   taps     the default design (T = 16 D + 1, ceil(T / D) = 17), and custom prototypes with T at both edges of the one
@@ -95,6 +95,10 @@ CASES = [
     Case("r3_64_T1", 3, 64, 3, 2, (1, 3, 2), T=1),
     Case("r3_64_T1088_fast_edge", 3, 64, 3, 2, (1, 3, 44), T=17 * 64),
     Case("r3_64_T1089_direct", 3, 64, 3, 2, (1, 3, 5), T=17 * 64 + 1),
+    # U = 1 past the integer entry's D <= 64: the edge between the two configurations (one group of 65; the carry is
+    # 1040 rows, so a one-period call is shorter than it)
+    Case("r1_65_m3_k2", 1, 65, 3, 2, (1, 3, 20, 0, 2)),
+    Case("r1_65_m3_k5_direct", 1, 65, 3, 5, (1, 3, 6)),
 ]
 CASE_IDS = [c.name for c in CASES]
 

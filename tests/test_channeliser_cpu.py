@@ -231,17 +231,23 @@ def test_the_matrix_picks_the_forms_it_names():
 
 
 def test_the_matrix_reaches_every_instance_in_the_build():
-    """Every channeliser_kernel<K, NA> the build holds is reached by a case of the matrix, and the direct and carry
-    kernels are there: a new bucket or instance fails here until the matrix tests it."""
+    """Every int16 channeliser_kernel<K, NA, 0, false> the build holds is reached by a case of the matrix, and the int16
+    direct and carry kernels are there, once in the whole build: a new bucket or instance fails here until the matrix
+    tests it."""
     import re
     s_path = os.path.join(ROOT, "gnuais_amd", "csrc", "build", "channeliser.s")
     if not os.path.exists(s_path):
         pytest.skip("channeliser.s not built (make -C gnuais_amd/csrc)")
     isa = open(s_path).read()
-    built = {(int(k), int(na)) for k, na in re.findall(r"channeliser_kernelILi(\d+)ELi(\d+)EEEv", isa)}
-    assert len(built) == 14, sorted(built)
+    fast = re.findall(r"\.amdhsa_kernel \S*channeliser_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)EEEv", isa)
+    assert {(f, r) for _, _, f, r in fast} == {("0", "0")}, "channeliser.s holds the int16 integer-ratio instances only"
+    built = {(int(k), int(na)) for k, na, _, _ in fast}
+    assert len(fast) == len(built) == 14, sorted(fast)
     assert built == {(c.K, c.na) for c in chan_cases.CASES if c.na}
-    assert "channeliser_direct_kernel" in isa and "channeliser_carry_kernel" in isa
+    units = {n: open(os.path.join(os.path.dirname(s_path), n + ".s")).read() for n in ("channeliser_fmt", "resampler")}
+    for form in ("direct", "carry"):
+        sym = rf"\.amdhsa_kernel \S*channeliser_{form}_kernelILi0EEEv"
+        assert len(re.findall(sym, isa)) == 1 and not any(re.findall(sym, u) for u in units.values()), form
     assert {c.direct_reason for c in chan_cases.CASES if not c.na} == {"K>4", "ceil(T/D)>33", "ceil(T/D)>17,K>2"}
 
 

@@ -131,18 +131,49 @@ def test_plan_with_custom_taps_and_a_longer_prototype(L):
         assert np.array_equal(groups, w[0]) and np.array_equal(pairs, w[1])
 
 
-def test_host_planning_under_the_sanitizers(tmp_path):
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
     """resample_plan.cpp is plain C++: built for the CPU with ASan + UBSan behind tests/c/resample_plan_main.cpp"""
-    exe = str(tmp_path / "resample_plan.bin")
+    exe = str(tmp_path_factory.mktemp("plan") / "resample_plan.bin")
     subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17",
                            "-Wall", "-Werror", "-ffp-contract=off", "-I", CSRC, os.path.join(ROOT, "tests", "c", "resample_plan_main.cpp"),
                            os.path.join(CSRC, "resample_plan.cpp"), "-o", exe, "-lm"])
+    return exe
+
+
+SANITIZER_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+
+
+def test_host_planning_under_the_sanitizers(plan_exe):
     args = [str(v) for r in cases.HOST_RATIOS + [(1, 1024), (64, 65), (63, 1024)] for v in r]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe] + args, capture_output=True, timeout=120, env=env)
+    p = subprocess.run([plan_exe] + args, capture_output=True, timeout=120, env=SANITIZER_ENV)
     assert p.returncode == 0, p.stdout.decode() + p.stderr.decode()
     lines = p.stdout.decode().split("\n")
     assert "3/128 T 2049 NA 17 H 683 pairs 65" in lines and "2/3 T 49 NA 17 H 24 pairs 2" in lines, lines
+
+
+@pytest.mark.parametrize("D", [1, 5, 6, 64])
+def test_the_integer_pair_table_is_the_plan_at_up_1(plan_exe, D):
+    """what gnuais_batch_channeliser puts on the device for its fast form: resample_plan() at U = 1 with
+    channeliser_fast_na() accumulators is POLY[q][a] = (h[aD + D-1-2q], h[aD + D-2-2q]), zero where the tap index is
+    >= T or the group's odd last sample has no partner.  T at both edges of every bucket: NA * D and NA * D - 1"""
+    for K, NA in ((1, 4), (3, 8), (4, 17), (2, 33)):
+        for T in (NA * D, NA * D - 1):
+            p = subprocess.run([plan_exe, "poly", str(K), str(D), str(T)], capture_output=True, timeout=60, env=SANITIZER_ENV)
+            assert p.returncode == 0, p.stdout.decode() + p.stderr.decode()
+            lines = p.stdout.decode().strip().split("\n")
+            assert lines[0].split() == [str(chan_ref.fast_na(K, T, D)), str((D + 1) // 2)], (K, D, T, lines[0])
+            na = int(lines[0].split()[0])
+            assert na == NA
+            got = np.array([[int(v) for v in ln.split()] for ln in lines[1:]], dtype=np.uint32)
+            h = ((np.arange(T) * 7919 + 13) % 4001 - 2000).astype(np.int16)
+
+            def tap(j, r):
+                return int(h[j]) & 0xffff if r < D and 0 <= j < T else 0
+
+            want = np.array([[tap(a * D + D - 1 - 2 * q, 2 * q) | tap(a * D + D - 2 - 2 * q, 2 * q + 1) << 16
+                              for a in range(na)] for q in range((D + 1) // 2)], dtype=np.uint32)
+            assert got.shape == want.shape and np.array_equal(got, want), (K, D, T)
 
 
 def test_bad_arguments_are_refused(L):
@@ -398,19 +429,26 @@ def test_slot_of_every_decoded_frame_at_3_128(W):
 
 def test_resampler_build_is_checked_and_holds_exactly_the_instances_the_matrix_reaches():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "$(CHECK_RES) $(BUILD)/resampler.s resampler" in mk
+    assert "$(CHECK_RES) $(BUILD)/resampler.s channeliser" in mk
     objs = mk.split("OBJS :=")[1].split("\n\n")[0]
     assert "$(BUILD)/resampler.o" in objs and "$(BUILD)/resample_plan.o" in objs
     s_path = os.path.join(CSRC, "build", "resampler.s")
     assert os.path.exists(s_path), "resampler.s not built (make -C gnuais_amd/csrc)"
     isa = open(s_path).read()
-    built = {(int(k), int(na), int(f)) for k, na, f in re.findall(r"resampler_kernelILi(\d+)ELi(\d+)ELi(\d+)EEEv", isa)}
+    found = re.findall(r"\.amdhsa_kernel \S*channeliser_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)EEEv", isa)
+    assert {r for _, _, _, r in found} == {"1"}, "resampler.s holds the rational instances only"
+    built = {(int(k), int(na), int(f)) for k, na, f, _ in found}
     fast, direct = cases.instances_reached()
     assert built == fast, (sorted(built - fast), sorted(fast - built))
-    assert len(built) == 16
-    assert {int(f) for f in re.findall(r"resampler_direct_kernelILi(\d+)EEEv", isa)} == direct == {0, 1, 2, 3}
-    assert {int(f) for f in re.findall(r"resampler_carry_kernelILi(\d+)EEEv", isa)} == {0, 1, 2, 3}
+    assert len(found) == len(built) == 16
+    # the direct form and the carry copy are the integer ratio's: each format's exists exactly once in the whole build
+    units = [isa] + [open(os.path.join(CSRC, "build", name)).read() for name in ("channeliser.s", "channeliser_fmt.s")]
+    for form in ("direct", "carry"):
+        sym = rf"\.amdhsa_kernel \S*channeliser_{form}_kernelILi(\d+)EEEv"
+        assert sorted(int(f) for u in units for f in re.findall(sym, u)) == [0, 1, 2, 3], form
+        assert not re.findall(sym, isa), form
+    assert direct == {0, 1, 2, 3}
     assert "v_dot2c_i32_i16" in isa
-    # a translation unit of its own: the integer channeliser's objects hold none of it
-    for name in ("channeliser.s", "channeliser_fmt.s"):
-        assert "resampler" not in open(os.path.join(CSRC, "build", name)).read()
+    # a translation unit of its own: the integer ratio's objects hold no rational instance
+    for u in units[1:]:
+        assert not re.findall(r"channeliser_kernelILi\d+ELi\d+ELi\d+ELb1E", u)

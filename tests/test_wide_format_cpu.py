@@ -224,35 +224,43 @@ def test_bad_format_arguments_are_refused_without_a_device(L):
 
 def test_the_format_kernels_are_built_checked_and_reached_by_the_matrix():
     """channeliser_fmt.s holds exactly the cs16 set of (K, NA) instances for each of cu8, cs8 and cf32 (42 fast-form
-    kernels), a direct and a carry kernel per format, and v_dot2c_i32_i16; its Makefile line runs the resource check;
-    and tests/wide_format_cases.py reaches every one of them, as the cs16 rule of test_channeliser_cpu.py asks"""
+    kernels), a direct and a carry kernel per format -- each exactly once in the whole build -- and v_dot2c_i32_i16; its
+    Makefile line runs the resource check; and tests/wide_format_cases.py reaches every one of them, as the cs16 rule
+    of test_channeliser_cpu.py asks"""
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "$(CHECK_RES) $(BUILD)/channeliser_fmt.s channeliser_fmt" in mk
+    assert "$(CHECK_RES) $(BUILD)/channeliser_fmt.s channeliser" in mk
     assert "$(BUILD)/channeliser_fmt.o" in mk.split("OBJS :=")[1].split("\n\n")[0]
     assert "$(BUILD)/wide_format.o" in mk.split("OBJS :=")[1].split("\n\n")[0]
     s_path = os.path.join(CSRC, "build", "channeliser_fmt.s")
     assert os.path.exists(s_path), "channeliser_fmt.s not built (make -C gnuais_amd/csrc)"
     isa = open(s_path).read()
-    built = {(int(k), int(na), int(f)) for k, na, f in
-             re.findall(r"channeliser_fmt_kernelILi(\d+)ELi(\d+)ELi(\d+)EEEv", isa)}
+    fast = re.findall(r"\.amdhsa_kernel \S*channeliser_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)EEEv", isa)
+    assert {r for _, _, _, r in fast} == {"0"}, "channeliser_fmt.s holds integer-ratio instances only"
+    built = {(int(k), int(na), int(f)) for k, na, f, _ in fast}
     cs16 = {(c.K, c.na) for c in chan_cases.CASES if c.na}
-    assert len(cs16) == 14 and len(built) == 42, sorted(built)
+    assert len(cs16) == 14 and len(fast) == len(built) == 42, sorted(built)
     assert built == {(K, na, VALUE[fmt]) for K, na in cs16 for fmt in cases.FORMATS}
     assert built == {(c.K, c.na, VALUE[fmt]) for fmt, c in cases.CASES if c.na}
     want_f = {VALUE[fmt] for fmt in cases.FORMATS}
-    assert {int(f) for f in re.findall(r"channeliser_fmt_direct_kernelILi(\d+)EEEv", isa)} == want_f
-    assert {int(f) for f in re.findall(r"channeliser_fmt_carry_kernelILi(\d+)EEEv", isa)} == want_f
+    others = [open(os.path.join(CSRC, "build", n)).read() for n in ("channeliser.s", "resampler.s")]
+    for form in ("direct", "carry"):
+        sym = rf"\.amdhsa_kernel \S*channeliser_{form}_kernelILi(\d+)EEEv"
+        here = [int(f) for f in re.findall(sym, isa)]
+        assert sorted(here) == sorted(want_f), (form, here)                   # each format's, once
+        assert not any(int(f) in want_f for o in others for f in re.findall(sym, o)), form
     for fmt in cases.FORMATS:
         assert {c.direct_reason for f, c in cases.CASES if f == fmt and not c.na} == \
             {"K>4", "ceil(T/D)>33", "ceil(T/D)>17,K>2"}, fmt
     assert "v_dot2c_i32_i16" in isa
     assert "v_perm_b32" in isa and "v_rndne_f32" in isa          # the byte placement and the fp32 rounding
-    assert "channeliser_fmt" not in open(os.path.join(CSRC, "build", "channeliser.s")).read()
+    cs16_unit = open(os.path.join(CSRC, "build", "channeliser.s")).read()
+    assert not re.findall(r"channeliser\w*_kernelILi\d+ELi\d+ELi[123]E", cs16_unit) and \
+        not re.findall(r"channeliser_(?:direct|carry)_kernelILi[123]E", cs16_unit)   # none of these formats' kernels there
 
 
 def test_the_kernels_and_the_host_share_the_header_of_the_formulas():
     """the kernels and gnuais_convert_samples both take the conversions from wide_format.h"""
-    for name in ("channeliser_body.h", "wide_format.cpp"):
+    for name in ("wide_kernels.h", "wide_format.cpp"):
         assert '#include "wide_format.h"' in open(os.path.join(CSRC, name)).read(), name
 
 
