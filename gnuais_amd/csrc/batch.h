@@ -201,6 +201,11 @@ struct gnuais_batch {
     bool frame_times = false;
     unsigned long long rows = 0;
     Buf<int64_t> times;                         // [frame_cap], allocated when the feature is first switched on
+    // The repair of CRC-failed candidates (gnuais_batch_repair, hdlc_repair.hip; off by default): while it is on, one
+    // more launch behind each K3 -- in front of the frame_time launch -- appends the repaired frames to ring 0 (a batch
+    // with the feature on does not stream) and counts them per channel.
+    bool repair = false;
+    Buf<int32_t> repaired;                      // [N], allocated (zeroed) when the feature is first switched on
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)

@@ -298,6 +298,8 @@ static int stream_setup(gnuais_batch *b)
     const size_t text_cap = (size_t) b->frame_cap * 164;        // a full ring of two-sentence frames
     if (b->frame_times) return fail(GNUAIS_E_STATE, "stream_nmea: the batch times its frames (gnuais_batch_frame_times); "
                                                     "the streamed delivery carries no times");
+    if (b->repair) return fail(GNUAIS_E_STATE, "stream_nmea: the batch repairs frames (gnuais_batch_repair); the streamed "
+                                               "delivery's order table describes the CRC stage's records only");
     if (int rc = gnuais_batch_sync(b)) return rc;
     // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
     // allocation) is repeated by the next call without leaking what the failed one had made

@@ -337,6 +337,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
+    if (b->repaired) HIP_TRY(hipMemset(b->repaired, 0, sizeof(int32_t) * N));
     for (int q = 0; q < gnuais_batch::HB; ++q) HIP_TRY(hipMemset(b->maxval[q], 0, sizeof(int) * N));
     b->max_cur = 0;
     b->max_last = 0;
@@ -375,6 +376,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         // and streams stay allocated for the next streaming call.
         if (value != 0 && b->frame_times)
             return fail(GNUAIS_E_STATE, "streaming: the batch times its frames (gnuais_batch_frame_times); the streamed delivery carries no times");
+        if (value != 0 && b->repair)
+            return fail(GNUAIS_E_STATE, "streaming: the batch repairs frames (gnuais_batch_repair); the streamed delivery's order table describes the CRC stage's records only");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
         if (b->streaming) {
             if (int rc = gnuais_batch_sync(b)) return rc;
@@ -473,6 +476,17 @@ static FrameTimeLaunch fill_frame_times(const gnuais_batch *b, const HdlcLaunch 
     return t;
 }
 
+// the launch behind the K3 described by h, in front of its frame_time launch
+static RepairLaunch fill_repair(const gnuais_batch *b, const HdlcLaunch &h)
+{
+    RepairLaunch r;
+    r.cand = h.cand; r.cand_first = h.cand_first; r.cand_count = h.cand_count;
+    r.repaired = b->repaired;
+    r.frames = h.frames; r.frame_count = h.frame_count; r.frame_cap = h.frame_cap;
+    r.N = h.N; r.K = h.K;
+    return r;
+}
+
 // K1 + carry: the kernel and its thresholds are plan_fir()'s choice (fir_plan.cpp).  The specialised kernels update
 // the history and clear the next peak buffer themselves; the generic fallback needs the two helper launches.
 static int run_fir(gnuais_batch *b, const int16_t *x, int len, float *dump, hipStream_t s, int k)
@@ -550,6 +564,10 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     if (pl && sD != sC) HIP_TRY(hipStreamWaitEvent(sD, b->e_done[3][k], 0));
     if (tm) HIP_TRY(hipEventRecord(ev[9], sD));
     if (b->stage_mask & 16) HIP_TRY(launch_hdlc_crc(h, sD));
+    // the repair of what K3 counted in lostframes: behind K3, in front of the times (repaired frames get theirs) and of
+    // e_done[4][k], which is what the reuse of set k (cand_first, cand_count) and, where K3 has a stream of its own, the
+    // next deframer launch (the candidate slots) wait for
+    if (b->repair && (b->stage_mask & 16)) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), sD));
     // the frames' receive times: behind K3 and in front of e_done[4][k], which is what the reuse of set k (segcnt) and,
     // where K3 has a stream of its own, the next deframer launch (ctl) wait for
     if (b->frame_times && (b->stage_mask & 16)) HIP_TRY(launch_frame_times(fill_frame_times(b, h, len), sD));
@@ -784,6 +802,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         fill_hdlc(b, h, 0);
         HIP_TRY(b->hdlc_variant ? launch_hdlc_events(h, nullptr) : launch_hdlc_deframe(h, nullptr));
         HIP_TRY(launch_hdlc_crc(h, nullptr));
+        if (b->repair) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), nullptr));
         if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
@@ -983,6 +1002,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "segments")) *value = b->n_seg;
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
+    else if (!strcmp(name, "repair")) *value = b->repair;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now
         *value = -1;
@@ -1008,6 +1028,33 @@ int gnuais_batch_frame_times(gnuais_batch *b, int on)
         HIP_TRY(hipMemset(b->times, 0xff, sizeof(int64_t) * (size_t) b->frame_cap));
     }
     b->frame_times = on != 0;
+    return GNUAIS_OK;
+}
+
+// The repair of CRC-failed candidates on / off (definition in include/gnuais_hip.h).  Synchronises: no call is in flight
+// when the switch turns, so every K3 either has its repair launch behind it or has not.
+int gnuais_batch_repair(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "repair: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "repair: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    if (on) HIP_TRY(b->repaired.ensure(sizeof(int32_t) * (size_t) b->N, true));
+    b->repair = on != 0;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_repaired(gnuais_batch *b, int32_t *h_out)
+{
+    if (!b || !h_out) return fail(GNUAIS_E_ARG, "repaired: argument");
+    if (!b->repaired) {                         // never switched on: nothing repaired
+        if (int rc = gnuais_batch_sync(b)) return rc;
+        std::fill(h_out, h_out + b->N, 0);
+        return GNUAIS_OK;
+    }
+    std::vector<int32_t> v;
+    if (int rc = read_out(b, b->repaired, (size_t) b->N, v)) return rc;
+    std::copy(v.begin(), v.end(), h_out);
     return GNUAIS_OK;
 }
 

@@ -236,4 +236,20 @@ hipError_t nmea_format(const struct gnuais_frame *frames, int n, int n_channels,
                        uint8_t *seq_out, char *out, size_t out_cap, void *scratch, size_t scratch_bytes,
                        uint32_t *h_info, hipStream_t s);
 
+// ---- repair of the candidates K3 counted in lostframes (hdlc_repair.hip; definition in include/gnuais_hip.h) ----
+// One launch behind that call's K3, on its stream, in front of the frame_time launch and before the call's hand-off set
+// (cand_first, cand_count) and the candidate slots can be reused.  Appends the repaired frames to the ring through
+// frame_count[0] (overflow: frame_count[1]) and counts them in repaired[channel].
+struct RepairLaunch {
+    const uint32_t *cand;          // as in HdlcLaunch, of the K3 launch it follows
+    const uint32_t *cand_first;
+    const uint32_t *cand_count;
+    int32_t *repaired;             // [N]
+    void *frames;                  // gnuais_frame[frame_cap]
+    uint32_t *frame_count;
+    uint32_t frame_cap;
+    int N, K;
+};
+hipError_t launch_hdlc_repair(const RepairLaunch &a, hipStream_t stream);
+
 } // namespace gnuais

@@ -517,6 +517,18 @@ int gnuais_node_frame_times(gnuais_node *nd, int on)
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_times(s.b, on); });
 }
 
+int gnuais_node_repair(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_repair: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_repair(s.b, on); });
+}
+
+int gnuais_node_repaired(gnuais_node *nd, int32_t *h_out)
+{
+    if (!nd || !h_out) return node_fail(GNUAIS_E_ARG, "node_repaired: argument");
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_repaired(s.b, h_out + s.first); });
+}
+
 static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
 
 int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int *n_out)

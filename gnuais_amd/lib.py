@@ -23,6 +23,7 @@ FSM_DTYPE = np.dtype([("state", "<i4"), ("nstartsign", "<i4"), ("antallpreamble"
                       ("antallenner", "<i4"), ("bitstuff", "<i4"), ("last", "<i4"),
                       ("bufferpos", "<i4")])
 assert FRAME_DTYPE.itemsize == 64
+FRAME_REPAIRED = 0x40         # GNUAIS_FRAME_REPAIRED: frame flags bit 6
 
 # kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
 INPUT_KINDS = {"audio": 0, "iq": 1, "wideband": 2}
@@ -81,6 +82,9 @@ SYMBOLS = {
     "gnuais_batch_time_map_ratio": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_nmea_tagged_from_frames": (_I, [_P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
                                             _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I)]),
+    "gnuais_batch_repair": (_I, [_P, _I]),
+    "gnuais_batch_repaired": (_I, [_P, _P]),
+    "gnuais_repair_candidate": (_I, [_P, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
     "gnuais_batch_counters": (_I, [_P, _P]),
     "gnuais_batch_total_received": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -140,6 +144,8 @@ SYMBOLS = {
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_frame_times": (_I, [_P, _I]),
     "gnuais_node_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_repair": (_I, [_P, _I]),
+    "gnuais_node_repaired": (_I, [_P, _P]),
     "gnuais_node_stream_nmea": (_I, [_P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_node_discard_frames": (_I, [_P]),
     "gnuais_node_counters": (_I, [_P, _P]),

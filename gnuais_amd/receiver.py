@@ -344,6 +344,18 @@ class ReceiverBatch:
         include/gnuais_hip.h); one more small launch per call.  Synchronises.  Not on a streaming batch."""
         check(self._lib.gnuais_batch_frame_times(self._h, int(bool(on))))
 
+    def repair(self, on: bool = True):
+        """gnuais_batch_repair(): from now on a frame that fails the CRC by one symbol error (two adjacent bits) is
+        repaired on the device and delivered with flags bit 6 set (the definition is in include/gnuais_hip.h); one more
+        launch per call.  Synchronises.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_repair(self._h, int(bool(on))))
+
+    def repaired(self) -> np.ndarray:
+        """gnuais_batch_repaired(): int32 [n_channels], the repairs per channel since create / reset"""
+        out = np.zeros(self.n_channels, dtype=np.int32)
+        check(self._lib.gnuais_batch_repaired(self._h, out.ctypes.data))
+        return out
+
     def drain_frames_timed(self):
         """gnuais_batch_drain_frames_timed(): (frames, int64 times), times[i] the receive time of frames[i] in chain rows
         since create / reset, -1 where there is none (decode_bits, or appended while the feature was off)."""

@@ -216,6 +216,16 @@ class ReceiverNode:
         """gnuais_batch_frame_times() on every shard"""
         self._raise(self._lib.gnuais_node_frame_times(self._h, int(bool(on))))
 
+    def repair(self, on: bool = True):
+        """gnuais_batch_repair() on every shard"""
+        self._raise(self._lib.gnuais_node_repair(self._h, int(bool(on))))
+
+    def repaired(self):
+        """gnuais_node_repaired(): int32 [n_channels], the repairs per global channel"""
+        out = self._np.zeros(self.n_channels, dtype=self._np.int32)
+        self._raise(self._lib.gnuais_node_repaired(self._h, out.ctypes.data))
+        return out
+
     def drain_frames_timed(self):
         """gnuais_node_drain_frames_timed(): (frames, int64 times), as drain_frames with every record's receive time"""
         from .lib import FRAME_DTYPE

@@ -41,9 +41,12 @@ typedef struct gnuais_frame {
 	uint8_t  payload[53];  /* nbits/8 bytes used, rest zero                     */
 	uint8_t  flags;        /* bit0: CRC ok (always set for delivered frames);
 	                          bits 5:1 = bits 36:32 of end_bit: the 37-bit stamp
-	                          wraps after 165 days of 9600 bit/s                */
+	                          wraps after 165 days of 9600 bit/s;
+	                          bit 6 (GNUAIS_FRAME_REPAIRED): the frame failed the
+	                          CRC as received and was repaired (gnuais_batch_repair) */
 	uint16_t nbits;        /* bufferpos - 22, src/protodec.c:1096               */
 } gnuais_frame;
+#define GNUAIS_FRAME_REPAIRED 0x40   /* gnuais_frame.flags: repaired by gnuais_batch_repair / gnuais_repair_candidate */
 
 /* One entry of the reference's position cache, struct cache_ent (src/cache.h:27-56), strings
  * inline: what the cache holds for one MMSI after the per-type decoders called cache_position /
@@ -351,7 +354,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "first_effective_tap",
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
- * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset) */
+ * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
+ * "repair" (gnuais_batch_repair(); 0 = off) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
 /* ---- results ------------------------------------------------------------------
@@ -444,6 +448,49 @@ int  gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *t
 				    int n_channels, long long mul, long long off, long long rate_hz,
 				    long long epoch_s, char *out, size_t out_cap, size_t *out_len,
 				    int *n_sentences);
+
+/* ---- repair of frames that fail the CRC by one symbol error ---------------------------------------------------------
+ * The slicer decides line levels and the NRZI decoder differentiates them, so one wrong level decision is two adjacent
+ * wrong bits in the stream the deframer sees.  The reference counts such a frame in lostframes and drops it
+ * (src/protodec.c:1105-1108); with the repair on, the frame is looked for among the neighbours of what was received.
+ * Off by default: while off, a call launches exactly what it launches without this section.
+ *   Candidate.  A record of the deframer's candidate ring that is counted in lostframes: it reached its stop bit with
+ *     bufferpos - 22 > 0 and its CRC is wrong.  Its raw bits are r[0 .. rawlen): the bits the deframer saw in ST_DATA,
+ *     stuffed zeros included, up to and including the fifth 1 of the closing flag; the sixth 1 is not among them.
+ *   Trial p, 0 <= p <= rawlen - 2: r' = r with bits p and p + 1 inverted; ST_DATA of the reference
+ *     (src/protodec.c:995-1027, from antallenner = 0, bitstuff = 0, last = 0, bufferpos = 0) runs over r', followed by
+ *     one more bit of value 1.
+ *   A trial is well formed when that appended bit, and no bit before it, takes the machine to ST_STOPSIGN; bufferpos
+ *     never reaches 449; n' = bufferpos - 22 > 0; and n' mod 8 = 0.
+ *   A trial passes when it is well formed and protodec_calculate_crc(n') holds on its buffer (the CRC over n'/8 + 2
+ *     bytes).
+ *   Outcome.  The candidate is repaired iff exactly one trial passes; with none or with several it stays lost.  (Two
+ *     trials that leave the stuffing alone cannot both pass: (1 + x)(1 + x^k) is no multiple of the CRC polynomial for
+ *     k < 32767.  Several can pass only where a trial makes or destroys a stuffed zero.)  Single-bit flips and two or
+ *     more symbol errors are not tried.
+ *   The repaired frame is the record the frame would have had, had the deframer stored r': channel; end_bit and
+ *     flags[5:1] of the candidate; nbits = n'; payload as for any frame; flags bit 0 and bit 6 (GNUAIS_FRAME_REPAIRED)
+ *     set.  It joins the frame ring like any frame (same capacity, same overflow report), takes its place by (channel,
+ *     37-bit stamp) in every drain, gets a receive time when gnuais_batch_frame_times is on, and is folded into vessel
+ *     tables and sentences like any frame: a consumer that wants received frames only tests bit 6.
+ *   Counters.  receivedframes, lostframes and lostframes2 do not move: the frame stays counted in lostframes.  A
+ *     per-channel int32 counter `repaired` counts the repairs; gnuais_batch_reset() zeroes it,
+ *     gnuais_batch_protodec_reset() keeps it.
+ *   False repairs.  A frame with more than one symbol error is accepted wrongly with probability about trials / 65536
+ *     (under one per cent); no message-type plausibility check is made.
+ * gnuais_batch_repair(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE on a streaming batch, and
+ *   while it is on the batch cannot start streaming (gnuais_batch_stream_nmea, gnuais_batch_autotune_delivery and
+ *   set_option("streaming", 1) return GNUAIS_E_STATE): the streamed delivery's order table describes the CRC stage's
+ *   records only.  One more launch follows every call's CRC stage while it is on (and every chunk of
+ *   gnuais_batch_decode_bits).
+ * gnuais_batch_repaired(): h_out[c] = repairs on channel c since create / reset.  Synchronises.
+ * gnuais_repair_candidate(): the same repair of one candidate on the host, from its raw bits (one per byte, bit 0
+ *   counts; n_raw <= 576).  Returns the number of passing trials, or GNUAIS_E_ARG; when that number is 1, payload[53]
+ *   (zero behind nbits / 8 bytes), *nbits = n' and *pos = p are written.  It does not ask whether r itself passes.
+ *   Host code, no device. */
+int  gnuais_batch_repair(gnuais_batch *b, int on);
+int  gnuais_batch_repaired(gnuais_batch *b, int32_t *h_out /* [n_channels] */);
+int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload[53], int *nbits, int *pos);
 
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
@@ -680,6 +727,9 @@ int  gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int
  * belongs to h_out[i]; global channel numbers and the reference's order as gnuais_node_drain_frames */
 int  gnuais_node_frame_times(gnuais_node *nd, int on);
 int  gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
+/* gnuais_batch_repair() on every shard, and the repairs per global channel */
+int  gnuais_node_repair(gnuais_node *nd, int on);
+int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);
 /* gnuais_batch_stream_nmea() on every shard (each from its own thread): texts[g] / lens[g] = shard g's sentences of
  * the call `stream_depth` calls ago (n_devices entries; valid until the next call).  Written out in shard order they
  * are the node's sentences in the reference's order for that call: shard g's channels all lie before shard g+1's and

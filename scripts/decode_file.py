@@ -23,6 +23,10 @@
                                                       # every sentence behind an NMEA TAG block "\\c:<unix>*hh\\" with the
                                                       # second the frame was received in, counted in the file's own samples
                                                       # from --start (the UNIX second of the file's first sample; default 0)
+  ... --repair
+                                                      # frames that fail the CRC by one symbol error (two adjacent bits) are
+                                                      # repaired on the device (gnuais_batch_repair) and printed like any
+                                                      # frame; the summary on stderr counts them and names each one
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -60,6 +64,9 @@ def main():
     ap.add_argument("--times", action="store_true",
                     help="a TAG block with the UNIX second of reception in front of every sentence (the frame's receive time "
                          "in input samples, gnuais_batch_frame_times)")
+    ap.add_argument("--repair", action="store_true",
+                    help="repair frames that fail the CRC by one symbol error (gnuais_batch_repair); the summary on stderr "
+                         "counts them and names each by receiver and closing bit")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
     if a.times and a.text:
@@ -94,6 +101,8 @@ def main():
     seq = np.zeros(n_ch, dtype=np.uint8)
     if a.times:
         b.frame_times(True)
+    if a.repair:
+        b.repair(True)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -104,6 +113,7 @@ def main():
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
+    repair_report(a, b)
     afc_report(a, b, 48000)
 
 
@@ -115,8 +125,14 @@ def write_sentences(a, b, seq, kind, rate):
         num, den, off = b.time_map_ratio(kind)         # index = (t * num + off) // den: floor(index / rate) in one division
         out = nmea_tagged_from_frames(frames, times, seq, num, off, rate * den, a.start)
     else:
-        nmea, text = messages_from_frames(b.drain_frames(), seq)
+        frames = b.drain_frames()
+        nmea, text = messages_from_frames(frames, seq)
         out = text if a.text else nmea
+    if a.repair:
+        from gnuais_amd.lib import FRAME_REPAIRED
+        a.repaired_frames = getattr(a, "repaired_frames", []) + [
+            (int(f["channel"]), int(f["end_bit"]) | ((int(f["flags"]) >> 1 & 31) << 32), int(f["nbits"]))
+            for f in frames[(frames["flags"] & FRAME_REPAIRED) != 0]]
     sys.stdout.write(out.decode("ascii", "replace"))
 
 
@@ -125,6 +141,15 @@ def afc_flush(x, rows, fmt=None):
     A format's zero is 0 for cs16, cs8 and cf32; no cu8 byte converts to 0 (zero lies at 127.5), so cu8 is flushed with
     128, which converts to +128: a constant, like zero, and 0.4 % of full scale."""
     return np.concatenate([x, np.full((rows,) + x.shape[1:], 128 if fmt == "cu8" else 0, dtype=x.dtype)])
+
+
+def repair_report(a, b):
+    """--repair: how many of the CRC errors came back, and which sentences they are"""
+    if a.repair:
+        sys.stderr.write(f"{int(b.repaired().sum())} of the CRC errors repaired (one symbol error each; they are among the "
+                         "sentences above)\n")
+        for c, e, n in getattr(a, "repaired_frames", []):
+            sys.stderr.write(f"  repaired: receiver {c}, closing bit {e}, {n} bits\n")
 
 
 def afc_report(a, b, rate):
@@ -165,6 +190,8 @@ def decode_wideband(a, rate, x, fmt=None):
     seq = np.zeros(n_ch, dtype=np.uint8)
     if a.times:
         b.frame_times(True)
+    if a.repair:
+        b.repair(True)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
@@ -172,6 +199,7 @@ def decode_wideband(a, rate, x, fmt=None):
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
+    repair_report(a, b)
     afc_report(a, b, 48000)
 
 
