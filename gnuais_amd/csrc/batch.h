@@ -206,6 +206,15 @@ struct gnuais_batch {
     // with the feature on does not stream) and counts them per channel.
     bool repair = false;
     Buf<int32_t> repaired;                      // [N], allocated (zeroed) when the feature is first switched on
+    // One record per transmission (gnuais_batch_unique, frame_unique.hip; 0 = off): the window in rows, the open
+    // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
+    // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the
+    // stage's scratch, which grows on first use like nmea_scratch.  Nothing runs per call; only
+    // gnuais_batch_drain_frames_unique touches any of it.
+    int uq_window = 0, uq_hash_bits = 64, uq_cur = 0, uq_n_tail = 0;
+    long long uq_late = 0;
+    Buf<uint32_t> uq_tail[2];
+    Buf<void> uq_scratch;
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)

@@ -268,6 +268,72 @@ int gnuais_batch_drain_frames_timed(gnuais_batch *b, gnuais_frame *h_out, int64_
     return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr, h_times ? h_times : &none_t);
 }
 
+// One record per transmission (gnuais_batch_unique): the queued frames and the open clusters of earlier drains go
+// through frame_unique.hip; the primaries, their times and the copies cross PCIe once.  The carried state -- the tail,
+// the late count -- moves only when everything has succeeded.
+int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                     int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
+        return fail(GNUAIS_E_ARG, "drain_frames_unique: argument");
+    *n_out = 0;
+    if (!b->uq_window) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch does not merge duplicates (gnuais_batch_unique)");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch is streaming (gnuais_batch_stream_nmea)");
+    Pending pend;
+    if (int rc = read_pending(b, pend)) return rc;
+    const uint32_t have = pend.have;
+    if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_frames_unique: buffers too small (one entry per pending frame always suffices)");
+    const size_t m = (size_t) b->uq_n_tail + have;
+    if (m) {                                    // without frames the tail still ages
+        if (have)
+            if (int rc = ensure_post_buffers(b, have)) return rc;
+        const size_t need = unique_scratch_bytes((int) m);
+        HIP_TRY(b->uq_scratch.grow(need, need / 4));
+        Buf<uint32_t> &next = b->uq_tail[b->uq_cur ^ 1];
+        HIP_TRY(next.grow(64 * m, 16 * m));
+        auto bits_of = [](unsigned long long v) { int n = 1; while (v >> n) ++n; return n; };
+        UniqueLaunch a;
+        a.frames = b->ring[0];
+        a.times = b->times;
+        a.have = (int) have;
+        a.tail = b->uq_tail[b->uq_cur];
+        a.n_tail = b->uq_n_tail;
+        a.tail_out = next;
+        a.window = b->uq_window;
+        a.rows = (long long) b->rows;
+        a.hash_bits = b->uq_hash_bits;
+        a.ch_bits = bits_of((unsigned long long) (b->N - 1));
+        a.time_bits = bits_of(b->rows);          // t + 1 <= rows
+        a.scratch = b->uq_scratch;
+        a.scratch_bytes = b->uq_scratch.bytes;
+        // the text buffer holds 164 bytes per frame: a record, its time and its copies fit side by side
+        a.out_frames = reinterpret_cast<gnuais_frame *>(b->d_text.p);
+        a.out_times = reinterpret_cast<int64_t *>(a.out_frames + have);
+        a.out_copies = reinterpret_cast<int32_t *>(a.out_times + have);
+        uint32_t info[UNIQUE_INFO_WORDS] = {0};
+        for (int exact = 0; exact < 2; ++exact) {
+            HIP_TRY(unique_cluster_enqueue(a, exact != 0, nullptr));
+            HIP_TRY(hipMemcpy(info, unique_info(a.scratch), sizeof info, hipMemcpyDeviceToHost));
+            if (!info[UNIQUE_INFO_COLLISION]) break;        // else: two keys share a hash -- once more, by the keys themselves
+        }
+        const uint32_t np = info[UNIQUE_INFO_PRIMARIES];
+        if (np > have || info[UNIQUE_INFO_TAIL] > m) return fail(GNUAIS_E_HIP, "drain_frames_unique: the stage's counts are out of range");
+        if (np) {
+            HIP_TRY(unique_deliver_enqueue(a, (int) np, nullptr));
+            HIP_TRY(hipMemcpy(h_out, a.out_frames, sizeof(gnuais_frame) * np, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h_times, a.out_times, sizeof(int64_t) * np, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+        }
+        unsigned long long late = 0;
+        memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
+        b->uq_cur ^= 1;
+        b->uq_n_tail = (int) info[UNIQUE_INFO_TAIL];
+        b->uq_late += (long long) late;
+        *n_out = (int) np;
+    }
+    return finish_drain(b, pend, "drain_frames_unique", "; results are incomplete");
+}
+
 int gnuais_batch_drain_nmea(gnuais_batch *b, uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len,
                             int *n_sentences, int *n_frames)
 {
@@ -300,6 +366,8 @@ static int stream_setup(gnuais_batch *b)
                                                     "the streamed delivery carries no times");
     if (b->repair) return fail(GNUAIS_E_STATE, "stream_nmea: the batch repairs frames (gnuais_batch_repair); the streamed "
                                                "delivery's order table describes the CRC stage's records only");
+    if (b->uq_window) return fail(GNUAIS_E_STATE, "stream_nmea: the batch merges duplicates (gnuais_batch_unique); the "
+                                                  "streamed delivery has no such stage");
     if (int rc = gnuais_batch_sync(b)) return rc;
     // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
     // allocation) is repeated by the next call without leaking what the failed one had made

@@ -1,0 +1,149 @@
+// frame_unique.cpp -- gnuais_uniq: the duplicate merge of the definition in include/gnuais_hip.h (gnuais_batch_unique)
+// on the host, one drain per push.  It is the exact statement the device stage (frame_unique.hip) must equal bit for
+// bit, and what a node runs over the merged timed drain of its shards.  Plain C++, no HIP.
+#include "frame_unique.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "../../include/gnuais_hip.h"
+
+using namespace gnuais::uniq;
+
+namespace {
+
+struct Key {
+    uint32_t w[KEY_WORDS];
+    bool operator==(const Key &o) const { return memcmp(w, o.w, sizeof w) == 0; }
+    bool operator<(const Key &o) const { return memcmp(w, o.w, sizeof w) < 0; }
+};
+
+struct Tail {
+    Key key;
+    long long t_last;
+};
+
+// a member of the sort: a tail entry (src < 0) or frame `src` of the push
+struct Member {
+    Key key;
+    long long t;
+    uint32_t channel;
+    int src;
+};
+
+struct Primary {
+    uint64_t order;             // output_word()
+    int src, copies;
+};
+
+Key key_of(const gnuais_frame &f)
+{
+    uint32_t rec[16];
+    memcpy(rec, &f, sizeof rec);
+    Key k;
+    for (int i = 0; i < KEY_WORDS; ++i) k.w[i] = key_word(rec, i);
+    return k;
+}
+
+} // namespace
+
+struct gnuais_uniq {
+    long long window = 0, late = 0;
+    std::vector<Tail> tail;
+};
+
+extern "C" {
+
+int gnuais_uniq_create(gnuais_uniq **out, long long window)
+{
+    if (!out) return GNUAIS_E_ARG;
+    *out = nullptr;
+    if (window <= 0) return GNUAIS_E_ARG;
+    gnuais_uniq *u = new (std::nothrow) gnuais_uniq;
+    if (!u) return GNUAIS_E_ARG;
+    u->window = window;
+    *out = u;
+    return GNUAIS_OK;
+}
+
+void gnuais_uniq_destroy(gnuais_uniq *u) { delete u; }
+
+int gnuais_uniq_reset(gnuais_uniq *u)
+{
+    if (!u) return GNUAIS_E_ARG;
+    u->tail.clear();
+    u->late = 0;
+    return GNUAIS_OK;
+}
+
+long long gnuais_uniq_late(const gnuais_uniq *u) { return u ? u->late : 0; }
+
+int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, int n, long long rows,
+                     gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out)
+{
+    if (!u || !n_out || n < 0 || cap < 0 || rows < 0 || (n > 0 && (!frames || !times)) ||
+        (cap > 0 && (!out || !out_times || !out_copies)))
+        return GNUAIS_E_ARG;
+    *n_out = 0;
+    const long long W = u->window;
+    std::vector<Member> mem;
+    std::vector<Primary> prim;
+    mem.reserve(u->tail.size() + (size_t) n);
+    for (const Tail &t : u->tail) mem.push_back(Member{t.key, t.t_last, 0u, -1});
+    for (int i = 0; i < n; ++i) {
+        if (times[i] < 0) {             // untimed: a cluster by itself
+            uint32_t rec[16];
+            memcpy(rec, &frames[i], sizeof rec);
+            prim.push_back(Primary{output_word(-1, frames[i].channel, stamp37(rec)), i, 1});
+        } else {
+            mem.push_back(Member{key_of(frames[i]), times[i], frames[i].channel, i});
+        }
+    }
+    // key, then the member order (t, channel); a tail entry lies before every frame of this push (t_last < rows <= t)
+    std::sort(mem.begin(), mem.end(), [](const Member &a, const Member &b) {
+        if (!(a.key == b.key)) return a.key < b.key;
+        if (a.t != b.t) return a.t < b.t;
+        if ((a.src < 0) != (b.src < 0)) return a.src < 0;
+        return a.channel < b.channel;
+    });
+    std::vector<Tail> tail;
+    long long late = 0;
+    for (size_t s = 0; s < mem.size();) {
+        size_t e = s + 1;
+        while (e < mem.size() && mem[e].key == mem[s].key && mem[e].t - mem[e - 1].t <= W) ++e;
+        const bool from_tail = mem[s].src < 0;
+        const int size = (int) (e - s) - (from_tail ? 1 : 0);
+        if (from_tail) {
+            late += size;               // copies of a transmission an earlier push delivered
+        } else {
+            // the first member in (repaired, t, channel): the earliest intact one, else the earliest
+            size_t p = s;
+            for (size_t j = s; j < e; ++j) {
+                uint32_t rec[16];
+                memcpy(rec, &frames[mem[j].src], sizeof rec);
+                if (!repaired_bit(rec)) { p = j; break; }
+            }
+            prim.push_back(Primary{output_word(mem[p].t, mem[p].channel, 0), mem[p].src, size});
+        }
+        if (mem[e - 1].t + W >= rows) tail.push_back(Tail{mem[s].key, mem[e - 1].t});
+        s = e;
+    }
+    if (prim.size() > (size_t) cap) return GNUAIS_E_ARG;        // nothing consumed: tail and late are as they were
+    std::sort(prim.begin(), prim.end(), [](const Primary &a, const Primary &b) {
+        return a.order != b.order ? a.order < b.order : a.src < b.src;
+    });
+    for (size_t j = 0; j < prim.size(); ++j) {
+        out[j] = frames[prim[j].src];
+        out_times[j] = times[prim[j].src];
+        out_copies[j] = prim[j].copies;
+    }
+    u->tail.swap(tail);
+    u->late += late;
+    *n_out = (int) prim.size();
+    return GNUAIS_OK;
+}
+
+} // extern "C"

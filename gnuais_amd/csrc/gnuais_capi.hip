@@ -338,6 +338,8 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
     if (b->repaired) HIP_TRY(hipMemset(b->repaired, 0, sizeof(int32_t) * N));
+    b->uq_n_tail = 0;                           // gnuais_batch_unique: no open cluster, nothing late (the window stays)
+    b->uq_late = 0;
     for (int q = 0; q < gnuais_batch::HB; ++q) HIP_TRY(hipMemset(b->maxval[q], 0, sizeof(int) * N));
     b->max_cur = 0;
     b->max_last = 0;
@@ -378,6 +380,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
             return fail(GNUAIS_E_STATE, "streaming: the batch times its frames (gnuais_batch_frame_times); the streamed delivery carries no times");
         if (value != 0 && b->repair)
             return fail(GNUAIS_E_STATE, "streaming: the batch repairs frames (gnuais_batch_repair); the streamed delivery's order table describes the CRC stage's records only");
+        if (value != 0 && b->uq_window)
+            return fail(GNUAIS_E_STATE, "streaming: the batch merges duplicates (gnuais_batch_unique); the streamed delivery has no such stage");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
         if (b->streaming) {
             if (int rc = gnuais_batch_sync(b)) return rc;
@@ -409,6 +413,9 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         b->pll_variant = value;
     } else if (!strcmp(name, "hdlc_variant")) {
         b->hdlc_variant = value != 0;
+    } else if (!strcmp(name, "unique_hash_bits")) {  // tests: a truncated hash forces the duplicate merge's exact path
+        if (value < 1 || value > 64) return fail(GNUAIS_E_ARG, "unique_hash_bits must be 1..64");
+        b->uq_hash_bits = value;
     } else if (!strcmp(name, "hdlc_lpw")) {
         if (value < 1 || value > 64) return fail(GNUAIS_E_ARG, "hdlc_lpw must be 1..64");
         b->hdlc_lpw = value;
@@ -1003,6 +1010,8 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
     else if (!strcmp(name, "repair")) *value = b->repair;
+    else if (!strcmp(name, "unique")) *value = b->uq_window;
+    else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now
         *value = -1;
@@ -1022,6 +1031,9 @@ int gnuais_batch_frame_times(gnuais_batch *b, int on)
     if (!b) return fail(GNUAIS_E_ARG, "frame_times: NULL batch");
     if (b->streaming) return fail(GNUAIS_E_STATE, "frame_times: the batch is streaming (gnuais_batch_stream_nmea); "
                                                   "set_option(\"streaming\", 0) leaves that mode");
+    if (!on && b->uq_window)
+        return fail(GNUAIS_E_STATE, "frame_times: the batch merges duplicates by their times (gnuais_batch_unique); "
+                                    "gnuais_batch_unique(b, 0) first");
     if (int rc = gnuais_batch_sync(b)) return rc;
     if (on && !b->frame_times) {
         HIP_TRY(b->times.ensure(sizeof(int64_t) * (size_t) b->frame_cap));
@@ -1041,6 +1053,30 @@ int gnuais_batch_repair(gnuais_batch *b, int on)
     if (int rc = gnuais_batch_sync(b)) return rc;
     if (on) HIP_TRY(b->repaired.ensure(sizeof(int32_t) * (size_t) b->N, true));
     b->repair = on != 0;
+    return GNUAIS_OK;
+}
+
+// The duplicate merge on / off (definition in include/gnuais_hip.h).  Nothing runs per call, so the switch only sets
+// the window and empties the carried state; it synchronises like the other switches.
+int gnuais_batch_unique(gnuais_batch *b, int window_rows)
+{
+    if (!b || window_rows < 0) return fail(GNUAIS_E_ARG, "unique: NULL batch or a negative window");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "unique: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (window_rows && !b->frame_times)
+        return fail(GNUAIS_E_STATE, "unique: the batch does not time its frames (gnuais_batch_frame_times): copies are "
+                                    "merged by their receive times");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    b->uq_window = window_rows;
+    b->uq_n_tail = 0;
+    b->uq_late = 0;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_unique_late(gnuais_batch *b, long long *late)
+{
+    if (!b || !late) return fail(GNUAIS_E_ARG, "unique_late: argument");
+    *late = b->uq_late;
     return GNUAIS_OK;
 }
 

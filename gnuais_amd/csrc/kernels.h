@@ -252,4 +252,38 @@ struct RepairLaunch {
 };
 hipError_t launch_hdlc_repair(const RepairLaunch &a, hipStream_t stream);
 
+// ---- one record per transmission: the duplicate merge of a drain (frame_unique.hip; definition in include/gnuais_hip.h) ----
+// Entries = [tail | ring]: n_tail open clusters of earlier drains (16 words each: t_last, then the key as a record
+// holds it) and the `have` frames of the ring with their times.  unique_cluster_enqueue() queues everything up to the
+// compacted primaries and the next tail (tail_out: room for n_tail + have entries, another buffer than tail) and leaves
+// UNIQUE_INFO_WORDS words at unique_info(scratch); `exact`: group by the key words themselves instead of the hash --
+// what the caller repeats the call with when the collision word came back set (nothing of the first attempt is kept).
+// unique_deliver_enqueue() then sorts the n_primaries into output order and gathers out_frames / out_times / out_copies.
+constexpr int UNIQUE_INFO_COLLISION = 0;    // != 0: equal hashes with unequal keys were seen
+constexpr int UNIQUE_INFO_CLUSTERS = 1;
+constexpr int UNIQUE_INFO_PRIMARIES = 2;    // records to deliver
+constexpr int UNIQUE_INFO_TAIL = 3;         // entries written to tail_out
+constexpr int UNIQUE_INFO_LATE = 4;         // two words: late copies of this drain (uint64)
+constexpr int UNIQUE_INFO_WORDS = 8;
+struct UniqueLaunch {
+    const void *frames;            // gnuais_frame[have]: the ring
+    const int64_t *times;          // [have], by ring slot
+    int have;
+    const void *tail;              // [n_tail][16] words
+    int n_tail;
+    void *tail_out;
+    long long window, rows;        // W, and the batch's row count at the drain
+    int hash_bits;                 // 1..64: bits of the hash in use (set_option("unique_hash_bits"))
+    int ch_bits, time_bits;        // channel < 2^ch_bits, t + 1 < 2^time_bits: the width of the member-order word
+    void *scratch;
+    size_t scratch_bytes;          // >= unique_scratch_bytes(n_tail + have)
+    struct gnuais_frame *out_frames;
+    int64_t *out_times;
+    int32_t *out_copies;
+};
+size_t unique_scratch_bytes(int n_entries);
+uint32_t *unique_info(void *scratch);
+hipError_t unique_cluster_enqueue(const UniqueLaunch &a, bool exact, hipStream_t s);
+hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStream_t s);
+
 } // namespace gnuais

@@ -183,6 +183,11 @@ struct gnuais_node {
     std::vector<Shard *> shards;
     std::vector<gnuais_frame> scratch;
     std::string warnings;           // what create could not do without failing (one line per shard)
+    // gnuais_node_unique: copies on different shards must merge and the shards exchange nothing, so the node merges on
+    // the host -- the timed drain of every shard into these buffers, then one gnuais_uniq over the union
+    gnuais_uniq *uq = nullptr;
+    std::vector<gnuais_frame> uq_frames;
+    std::vector<int64_t> uq_times;
 };
 
 extern "C" {
@@ -218,6 +223,7 @@ static int run_all(gnuais_node *nd, const std::function<int(Shard &, size_t)> &f
 void gnuais_node_destroy(gnuais_node *nd)
 {
     if (!nd) return;
+    gnuais_uniq_destroy(nd->uq);
     for (Shard *s : nd->shards) {
         if (s->w.th.joinable()) {
             s->w.submit([s] {
@@ -310,6 +316,7 @@ int gnuais_node_shard(const gnuais_node *nd, int i, int *device, int *first_chan
 int gnuais_node_reset(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_reset: NULL");
+    if (nd->uq) (void) gnuais_uniq_reset(nd->uq);
     return run_all(nd, [](Shard &s, size_t) { return gnuais_batch_reset(s.b); });
 }
 
@@ -514,6 +521,7 @@ int gnuais_node_pending_frames(gnuais_node *nd, int *n_out)
 int gnuais_node_frame_times(gnuais_node *nd, int on)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_frame_times: NULL node");
+    if (!on && nd->uq) return node_fail(GNUAIS_E_STATE, "node_frame_times: the node merges duplicates by their times (gnuais_node_unique)");
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_times(s.b, on); });
 }
 
@@ -581,6 +589,54 @@ static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, in
         w += cnt[i];
     }
     *n_out = w;
+    return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
+}
+
+// One record per transmission over the whole node (gnuais_batch_unique's definition): the merged timed drain, then the
+// host object.  window_rows = 0 switches it off; switching clears the tail and the late count.
+int gnuais_node_unique(gnuais_node *nd, int window_rows)
+{
+    if (!nd || window_rows < 0) return node_fail(GNUAIS_E_ARG, "node_unique: NULL node or a negative window");
+    if (window_rows)
+        for (Shard *s : nd->shards) {
+            double on = 0;
+            if (gnuais_batch_info(s->b, "frame_times", &on) != GNUAIS_OK || on == 0)
+                return node_fail(GNUAIS_E_STATE, "node_unique: the node does not time its frames (gnuais_node_frame_times)");
+        }
+    gnuais_uniq_destroy(nd->uq);
+    nd->uq = nullptr;
+    if (window_rows && gnuais_uniq_create(&nd->uq, window_rows) != GNUAIS_OK)
+        return node_fail(GNUAIS_E_ARG, "node_unique: the merge object could not be made");
+    return GNUAIS_OK;
+}
+
+int gnuais_node_unique_late(gnuais_node *nd, long long *late)
+{
+    if (!nd || !late) return node_fail(GNUAIS_E_ARG, "node_unique_late: argument");
+    *late = gnuais_uniq_late(nd->uq);
+    return GNUAIS_OK;
+}
+
+int gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                    int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: argument");
+    *n_out = 0;
+    if (!nd->uq) return node_fail(GNUAIS_E_STATE, "node_drain_frames_unique: the node does not merge duplicates (gnuais_node_unique)");
+    int total = 0;
+    if (int rc = gnuais_node_pending_frames(nd, &total)) return rc;
+    if (total > max) return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: buffers too small (one entry per pending frame always suffices)");
+    nd->uq_frames.resize((size_t) total + 1);
+    nd->uq_times.resize((size_t) total + 1);
+    int got = 0;
+    const int rc = node_drain(nd, nd->uq_frames.data(), nd->uq_times.data(), total, &got);
+    if (rc != GNUAIS_OK && rc != GNUAIS_E_OVERFLOW) return rc;
+    double rows = 0;                    // a node's run calls give every shard the same rows
+    if (gnuais_batch_info(nd->shards[0]->b, "rows", &rows) != GNUAIS_OK) return node_fail(GNUAIS_E_STATE, "node_drain_frames_unique: rows");
+    if (gnuais_uniq_push(nd->uq, nd->uq_frames.data(), nd->uq_times.data(), got, (long long) rows, h_out, h_times,
+                         h_copies, max, n_out) != GNUAIS_OK)
+        return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: the merge refused its input");
     return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
 }
 

@@ -367,6 +367,30 @@ class ReceiverBatch:
                                                         C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy()
 
+    def unique(self, window: int):
+        """gnuais_batch_unique(): window > 0 rows: drain_frames_unique() delivers each transmission once (equal frames
+        whose receive times chain within the window; the definition is in include/gnuais_hip.h); 0: off.  Needs
+        frame_times(); clears the carried state.  Synchronises.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_unique(self._h, int(window)))
+
+    def drain_frames_unique(self):
+        """gnuais_batch_drain_frames_unique(): (frames, int64 times, int32 copies): one record per transmission -- the
+        earliest intact copy and its own time -- and how many copies this drain merged into it"""
+        n = max(self.pending_frames(), 1)
+        out = np.zeros(n, dtype=FRAME_DTYPE)
+        times = np.zeros(n, dtype=np.int64)
+        copies = np.zeros(n, dtype=np.int32)
+        got = C.c_int()
+        check(self._lib.gnuais_batch_drain_frames_unique(self._h, out.ctypes.data, times.ctypes.data, copies.ctypes.data,
+                                                         n, C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy()
+
+    def unique_late(self) -> int:
+        """gnuais_batch_unique_late(): copies that arrived after a drain had delivered their transmission"""
+        v = C.c_longlong()
+        check(self._lib.gnuais_batch_unique_late(self._h, C.byref(v)))
+        return v.value
+
     def time_map(self, kind: str = "audio"):
         """gnuais_batch_time_map(): (mul, off) with input sample index = t * mul + off for the batch's configuration as
         it is now; kind: "audio", "iq" or "wideband"."""
@@ -649,3 +673,45 @@ def tile_channels(base, n_channels: int):
     check(_lib.load().gnuais_tile_channels(base.data_ptr(), k, n, out.data_ptr(), n_channels,
                                            C.c_void_p(stream)))
     return out
+
+
+class Uniq:
+    """gnuais_uniq: the duplicate merge of gnuais_batch_unique() as a host object, no device (include/gnuais_hip.h).
+    push() is one drain of the definition."""
+
+    def __init__(self, window: int):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.gnuais_uniq_create(C.byref(self._h), int(window))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_uniq_create: the window must be > 0")
+
+    def close(self):
+        if self._h:
+            self._lib.gnuais_uniq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        self._lib.gnuais_uniq_reset(self._h)
+
+    def late(self) -> int:
+        return int(self._lib.gnuais_uniq_late(self._h))
+
+    def push(self, frames: np.ndarray, times: np.ndarray, rows: int, cap: Optional[int] = None):
+        """-> (frames, times, copies) of the clusters this drain delivers; cap: room offered (default: enough)"""
+        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        times = np.ascontiguousarray(times, dtype=np.int64)
+        assert frames.ndim == 1 and times.shape == frames.shape
+        n = int(frames.size)
+        cap = n if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=FRAME_DTYPE)
+        out_t = np.zeros(max(cap, 1), dtype=np.int64)
+        out_c = np.zeros(max(cap, 1), dtype=np.int32)
+        got = C.c_int()
+        rc = self._lib.gnuais_uniq_push(self._h, frames.ctypes.data, times.ctypes.data, n, int(rows), out.ctypes.data,
+                                        out_t.ctypes.data, out_c.ctypes.data, cap, C.byref(got))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_uniq_push: argument, or more records than cap")
+        return out[: got.value].copy(), out_t[: got.value].copy(), out_c[: got.value].copy()

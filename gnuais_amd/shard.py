@@ -236,6 +236,27 @@ class ReceiverNode:
                                                              self._C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy()
 
+    def unique(self, window: int):
+        """gnuais_node_unique(): each transmission once over the whole node (merged on the host: the shards exchange
+        nothing); window in rows, 0 = off.  Needs frame_times()."""
+        self._raise(self._lib.gnuais_node_unique(self._h, int(window)))
+
+    def drain_frames_unique(self):
+        """gnuais_node_drain_frames_unique(): (frames, int64 times, int32 copies), one record per transmission"""
+        from .lib import FRAME_DTYPE
+        np_ = self._np
+        n = max(self.pending_frames(), 1)
+        out, times, copies = np_.zeros(n, dtype=FRAME_DTYPE), np_.zeros(n, dtype=np_.int64), np_.zeros(n, dtype=np_.int32)
+        got = self._C.c_int()
+        self._raise(self._lib.gnuais_node_drain_frames_unique(self._h, out.ctypes.data, times.ctypes.data,
+                                                              copies.ctypes.data, n, self._C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy()
+
+    def unique_late(self) -> int:
+        t = self._C.c_longlong()
+        self._raise(self._lib.gnuais_node_unique_late(self._h, self._C.byref(t)))
+        return t.value
+
     def time_map(self, kind: str = "audio"):
         """gnuais_batch_time_map() of the first shard: every shard has the node's configuration"""
         from .lib import INPUT_KINDS, check

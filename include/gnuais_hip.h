@@ -355,7 +355,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
- * "repair" (gnuais_batch_repair(); 0 = off) */
+ * "repair" (gnuais_batch_repair(); 0 = off), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
+ * (gnuais_batch_unique_late()) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
 /* ---- results ------------------------------------------------------------------
@@ -491,6 +492,65 @@ int  gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *t
 int  gnuais_batch_repair(gnuais_batch *b, int on);
 int  gnuais_batch_repaired(gnuais_batch *b, int32_t *h_out /* [n_channels] */);
 int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload[53], int *nbits, int *pos);
+
+/* ---- each transmission once: the copies several receivers hear, merged on the delivery side ----------------------------
+ * Not in the reference (one process, one or two receivers).  A batch is thousands of receivers with overlapping cover,
+ * and most transmissions are heard by more than one of them; every copy is a frame of its own in the drains above.
+ * With a window W set, gnuais_batch_drain_frames_unique() delivers one record per cluster of equal frames, with the
+ * number of copies.  Off by default; nothing runs per call, the stage is the drain; every other entry is unchanged.
+ *   Key of a frame: nbits and the 53 payload bytes.  channel, end_bit and flags are not part of it: a repaired and an
+ *     intact copy share a key.
+ *   Member order: within one key, the frames with t >= 0 (gnuais_batch_frame_times) ordered by (t, channel).  The order
+ *     is total: two frames of one channel never share a t, the slices of a segment map to strictly increasing rows.
+ *   Chain rule: with W > 0 rows, member i belongs to the cluster of member i - 1 iff t_i - t_{i-1} <= W.  A cluster is
+ *     a maximal run: a chain may span more than W from its first to its last member.
+ *   Primary: the first member of the cluster in the order (flags bit 6, t, channel) -- the earliest intact copy, or the
+ *     earliest repaired one when all are repaired.  The delivered record and time are the primary's own, unchanged;
+ *     copies = the cluster's size.
+ *   Untimed frames: a frame with t = -1 (gnuais_batch_decode_bits, or appended while times were off) is a cluster by
+ *     itself, copies = 1.
+ *   Output order: the t = -1 frames first, in the plain drain's order (channel, then the 37-bit stamp); the rest by
+ *     (t, channel) of the primary.
+ *   Across drains: let n = "rows" at the drain.  THE PROPERTY RELIED ON: every time of a drain lies in [rows before the
+ *     first call it covers, n), so every frame of a later drain has t >= n (a frame's time is a row of the call that
+ *     closed it; tests/test_unique_cpu.py asserts it on the times' reference).  A cluster whose last member has
+ *     t_last + W >= n stays open as a tail entry (key, t_last).  In the next drain a tail entry is a virtual first
+ *     member of its key: frames that chain onto it are late copies of a transmission already delivered -- they are not
+ *     delivered, they are counted in a 64-bit counter `late`, and they move t_last forward.  Tail entries with
+ *     t_last + W < n are dropped at the end of a drain.  So for any placement of the drains, sum(copies) + late = the
+ *     frames gnuais_batch_drain_frames_timed() would have delivered, and the set of clusters is that of one drain over
+ *     everything; only copies against late, and which member is the primary, depend on the cuts.
+ *   State: gnuais_batch_reset() and switching the feature (off, on, or to another window) clear the tail and `late`;
+ *     gnuais_batch_protodec_reset() keeps both.  Frames consumed by any other drain, or dropped by
+ *     gnuais_batch_discard_frames(), are never seen by the stage.
+ *   Clocks: all channels of a batch share the row clock; aligning receivers whose captures start at different
+ *     instants is the caller's business.
+ *   Exactness: the device groups by a 64-bit hash of the key and then compares the keys themselves; where two
+ *     different keys share a hash the drain repeats its grouping by the key words, so the result is the definition's
+ *     for every input (set_option("unique_hash_bits", k) truncates the hash to k bits to exercise that path).  No
+ *     result depends on the order in which the frames entered the ring.
+ * gnuais_batch_unique(window_rows): > 0 switches the feature on with that window, 0 off; synchronises.  GNUAIS_E_STATE
+ *   unless frame times are on, and on a streaming batch.  While it is on, gnuais_batch_frame_times(b, 0) and the three
+ *   ways into streaming return GNUAIS_E_STATE.
+ * gnuais_batch_drain_frames_unique(): consumes the queued frames like gnuais_batch_drain_frames(); h_out[i], h_times[i],
+ *   h_copies[i] describe cluster i.  GNUAIS_E_STATE while the feature is off; GNUAIS_E_ARG, consuming nothing, when max
+ *   is smaller than the number of pending frames (the upper bound); overflow and watchdog are reported late, as there.
+ *   76 bytes per delivered record cross PCIe.
+ * gnuais_batch_unique_late(): `late` since the feature was switched on / the last reset.
+ * gnuais_uniq: the same merge as a host object, no device: _push() is one drain of the definition over frames[n] /
+ *   times[n] in any order with rows = n of the definition; at most cap records are written (GNUAIS_E_ARG, with the
+ *   object unchanged, when the push would deliver more).  The device drain equals it bit for bit. */
+int  gnuais_batch_unique(gnuais_batch *b, int window_rows);
+int  gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                      int *n_out);
+int  gnuais_batch_unique_late(gnuais_batch *b, long long *late);
+typedef struct gnuais_uniq gnuais_uniq;
+int  gnuais_uniq_create(gnuais_uniq **out, long long window);
+void gnuais_uniq_destroy(gnuais_uniq *u);
+int  gnuais_uniq_reset(gnuais_uniq *u);
+int  gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, int n, long long rows,
+                      gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out);
+long long gnuais_uniq_late(const gnuais_uniq *u);
 
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
@@ -629,6 +689,7 @@ int  gnuais_batch_mean_timing(gnuais_batch *b, float *ms5, int *n_calls);
  *   "hdlc_lpw"      channels per deframer wave, 1..64 (default by channel count: as few as keep the launch at <= 512 waves --
  *                   1, 2, 4, 8 or 16 -- up to 1536 channels, 16 up to 8192, 64 where the batch fills the chip)
  *   "streaming"     0 leaves the streamed delivery (gnuais_batch_stream_nmea switches it on)
+ *   "unique_hash_bits" bits of the duplicate merge's hash in use, 1..64 (default 64); tests force hash collisions with few
  *   "timing_stride" with set_timing on, time every n-th call only (the event records of a timed call cost stream time)
  *   "stage_mask"    measurement only: bit 0 FIR/slicer, 1 PLL/NRZI, 3 deframer, 4 unstuff/CRC; results are wrong unless 0x1f */
 int  gnuais_batch_set_option(gnuais_batch *b, const char *name, int value);
@@ -730,6 +791,15 @@ int  gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_
 /* gnuais_batch_repair() on every shard, and the repairs per global channel */
 int  gnuais_node_repair(gnuais_node *nd, int on);
 int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);
+/* gnuais_batch_unique()'s definition over the whole node.  Copies on different shards must merge, and the shards
+ * exchange nothing (no collective): so the node form is gnuais_node_drain_frames_timed() into a host buffer followed by
+ * one gnuais_uniq kept in the node -- the merge itself runs on the host here, not on the devices.  _unique() needs
+ * gnuais_node_frame_times on (else GNUAIS_E_STATE), which then cannot be switched off; gnuais_node_reset() clears the
+ * tail and `late`.  The shards' own gnuais_batch_unique stays off. */
+int  gnuais_node_unique(gnuais_node *nd, int window_rows);
+int  gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                     int *n_out);
+int  gnuais_node_unique_late(gnuais_node *nd, long long *late);
 /* gnuais_batch_stream_nmea() on every shard (each from its own thread): texts[g] / lens[g] = shard g's sentences of
  * the call `stream_depth` calls ago (n_devices entries; valid until the next call).  Written out in shard order they
  * are the node's sentences in the reference's order for that call: shard g's channels all lie before shard g+1's and

@@ -27,6 +27,13 @@
                                                       # frames that fail the CRC by one symbol error (two adjacent bits) are
                                                       # repaired on the device (gnuais_batch_repair) and printed like any
                                                       # frame; the summary on stderr counts them and names each one
+  ... --unique ROWS [--verbose]
+                                                      # several receivers of the file hear the same transmissions (overlapping
+                                                      # stations, the two offsets of one stream): each transmission is printed
+                                                      # once -- equal frames whose receive times chain within ROWS rows are
+                                                      # merged on the device (gnuais_batch_unique) and the earliest intact copy
+                                                      # is printed.  Implies --times.  --verbose: "copies N" per transmission on
+                                                      # stderr; the summary counts copies and late copies
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -67,8 +74,15 @@ def main():
     ap.add_argument("--repair", action="store_true",
                     help="repair frames that fail the CRC by one symbol error (gnuais_batch_repair); the summary on stderr "
                          "counts them and names each by receiver and closing bit")
+    ap.add_argument("--unique", type=int, default=0, metavar="ROWS",
+                    help="print each transmission once: merge equal frames whose receive times chain within ROWS rows of the "
+                         "chain's clock (gnuais_batch_unique; 128 suits receivers of one site); implies --times")
+    ap.add_argument("--verbose", action="store_true", help="--unique: the copies of every printed transmission, on stderr")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
+    if a.unique < 0:
+        sys.exit("--unique takes a window in rows, > 0")
+    a.times = a.times or a.unique > 0
     if a.times and a.text:
         sys.exit("--times tags NMEA sentences: not with --text")
     import torch
@@ -103,6 +117,8 @@ def main():
         b.frame_times(True)
     if a.repair:
         b.repair(True)
+    if a.unique:
+        b.unique(a.unique)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -120,8 +136,16 @@ def main():
 def write_sentences(a, b, seq, kind, rate):
     """what the batch has decoded since the last call, to stdout; rate: of the input samples (--times)"""
     from gnuais_amd import messages_from_frames, nmea_tagged_from_frames
-    if a.times:
+    if a.unique:
+        frames, times, copies = b.drain_frames_unique()
+        a.unique_records = getattr(a, "unique_records", 0) + len(frames)
+        a.unique_copies = getattr(a, "unique_copies", 0) + int(copies.sum())
+        if a.verbose:
+            for f, t, c in zip(frames, times, copies):
+                sys.stderr.write(f"  copies {int(c)}: receiver {int(f['channel'])}, row {int(t)}, {int(f['nbits'])} bits\n")
+    elif a.times:
         frames, times = b.drain_frames_timed()
+    if a.times:
         num, den, off = b.time_map_ratio(kind)         # index = (t * num + off) // den: floor(index / rate) in one division
         out = nmea_tagged_from_frames(frames, times, seq, num, off, rate * den, a.start)
     else:
@@ -144,7 +168,10 @@ def afc_flush(x, rows, fmt=None):
 
 
 def repair_report(a, b):
-    """--repair: how many of the CRC errors came back, and which sentences they are"""
+    """--unique: transmissions against copies; --repair: how many of the CRC errors came back, and which sentences"""
+    if a.unique:
+        sys.stderr.write(f"{getattr(a, 'unique_records', 0)} transmissions printed once from {getattr(a, 'unique_copies', 0)} "
+                         f"copies, {b.unique_late()} more copies came after their transmission was printed\n")
     if a.repair:
         sys.stderr.write(f"{int(b.repaired().sum())} of the CRC errors repaired (one symbol error each; they are among the "
                          "sentences above)\n")
@@ -192,6 +219,8 @@ def decode_wideband(a, rate, x, fmt=None):
         b.frame_times(True)
     if a.repair:
         b.repair(True)
+    if a.unique:
+        b.unique(a.unique)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
