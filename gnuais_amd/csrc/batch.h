@@ -270,6 +270,7 @@ struct gnuais_batch {
     // AFC stage, afc_audio by K1.  The AFC stage's delay line, block sums and estimates are carries of the first kind.
     struct { hipStream_t s = nullptr; bool used = false; } last[N_STAGES];
     int last_len = 0;
+    int pll_form = 0;               // what pll_form_of() gave for the last run call's PLL launch: 7 / 8; 0 before any call
     // K3 on the deframer's stream: at ring lag 1 the two never overlap (deframer(i) -> K3(i) -> deframer(i+1)), so the two
     // cross-stream event waits per call in the loop that sets the period become stream order: 20-step 0.550 -> 0.544,
     // steady 0.527 -> 0.522 (three A/B pairs, profiles/r04_k3_on_the_deframers_stream.txt).  0 = a stream of its own.

@@ -353,6 +353,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     if (int rc = afc_zero_state(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
+    b->pll_form = 0;
     return GNUAIS_OK;
 }
 
@@ -624,7 +625,10 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
         fill_pll(b, p, k, len);
         if (pl) HIP_TRY(hipStreamWaitEvent(sA, b->e_done[0][k], 0));
         if (tm) HIP_TRY(hipEventRecord(ev[2], sA));
-        if (b->stage_mask & 2) HIP_TRY(launch_pll(p, sA));
+        if (b->stage_mask & 2) {
+            b->pll_form = pll_form_of(p);       // info "pll_form": the form launch_pll() takes for these arguments
+            HIP_TRY(launch_pll(p, sA));
+        }
         if (tm) HIP_TRY(hipEventRecord(ev[6], sA));
         if (pl) HIP_TRY(hipEventRecord(b->e_done[1][k], sA));
         if (int rc = run_tail(b, k, len, tm, ev, s0, pl ? b->e_done[1][k] : nullptr)) return rc;
@@ -1009,6 +1013,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "segments")) *value = b->n_seg;
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
+    else if (!strcmp(name, "pll_form")) *value = b->pll_form;
     else if (!strcmp(name, "repair")) *value = b->repair;
     else if (!strcmp(name, "unique")) *value = b->uq_window;
     else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;

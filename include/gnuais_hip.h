@@ -356,7 +356,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
  * "repair" (gnuais_batch_repair(); 0 = off), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
- * (gnuais_batch_unique_late()) */
+ * (gnuais_batch_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
+ * one, 8 the lane-per-channel one; 0 before any call and after a reset) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
 /* ---- results ------------------------------------------------------------------

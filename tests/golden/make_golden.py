@@ -161,6 +161,9 @@ def main():
     if sys.argv[1:] == ["nmea"]:
         make_nmea()
         return
+    if sys.argv[1:] == ["ref_pins"]:
+        import ref_pins
+        return ref_pins.store()
     ref = reference()
     # 1. full chain, 48 kHz, 2 channels (config C1 shape)
     np.savez_compressed(os.path.join(HERE, "chain_48k.npz"), **run_chain(cases.chain_48k()))

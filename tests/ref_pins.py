@@ -1,6 +1,6 @@
 """What the REAL reference (oracle/_ref/libgnuais_ref.so) answers on the seeded inputs of the pin tests
-(test_oracle_vs_ref.py and the *_vs_reference / *_against_reference tests of test_nmea.py, test_range.py,
-test_vessels.py).  Where oracle/_ref is built the answers come from it, live; elsewhere from the copy that
+(test_oracle_vs_ref.py, test_pll_cpu.py and the *_vs_reference / *_against_reference tests of test_nmea.py,
+test_range.py, test_vessels.py).  Where oracle/_ref is built the answers come from it, live; elsewhere from the copy that
 tests/golden/make_golden.py stored in tests/golden/ref_pins.npz by calling these same functions.  The inputs are
 made here as well, so the stored answers and the tests' inputs cannot drift apart."""
 import os
@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 import cases
+import pll_ref
 from gnuais_amd import params, synth
 from oracle_lib import have_reference, reference
 
@@ -75,6 +76,15 @@ def range_locations(seed):
     return out
 
 
+PLL_PIN_COLUMNS = ("fast", "slow", "coin")
+
+
+def pll_columns(pllinc):
+    """[12000][3]: the two drift columns and the coin of pll_ref.columns(), for the pass-through table pll_ref.TAPS"""
+    x = pll_ref.columns(12000, pllinc)
+    return np.ascontiguousarray(x[:, [pll_ref.COLUMN_NAMES.index(n) for n in PLL_PIN_COLUMNS]])
+
+
 # ---------------------------------------------------------------- the reference's answers
 
 def _chain(x, taps=None, pllinc=0, chunk=1020, bits_of=0):
@@ -85,6 +95,16 @@ def _chain(x, taps=None, pllinc=0, chunk=1020, bits_of=0):
     return {"taps": ref.taps(0), "bits": ref.bits(), "frames": _bytes(ref.frames().tobytes()),
             "counters": ref.counters(), "pll": np.array([ref.pll(c) for c in range(n_ch)], dtype=np.int64),
             "fsm": np.array([[ref.fsm(c)[k] for k in FSM] for c in range(n_ch)], dtype=np.int64)}
+
+
+def _pll(pllinc):
+    x = pll_columns(pllinc)
+    out = {}
+    for j in range(x.shape[1]):                 # one receiver at a time: the reference records one channel's bits
+        r = _chain(x[:, j:j + 1], taps=pll_ref.TAPS, pllinc=pllinc)
+        for k in ("bits", "frames", "counters", "pll", "fsm"):
+            out["%s_%d" % (k, j)] = r[k]
+    return out
 
 
 def _taps():
@@ -145,6 +165,8 @@ PINS["noise_and_full_scale"] = lambda: _chain(noise_and_full_scale(), chunk=4096
 PINS["filter_floats"] = _filter_floats
 PINS["192k"] = lambda: _chain(stream_192k(), taps=params.taps_192k(), pllinc=params.PLLINC_192K, chunk=4096)
 PINS["deframer"] = _deframer
+for _s in pll_ref.PLLINCS:
+    PINS["pll_%d" % _s] = (lambda s: lambda: _pll(s))(_s)
 for _s in (71, 72):
     PINS["stdout_text_%d" % _s] = (lambda s: lambda: _stdout_text(s))(_s)
 for _s in (61, 62, 63):

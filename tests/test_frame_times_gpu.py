@@ -85,6 +85,33 @@ def test_times_192k_table():
     assert b.time_map("audio") == ftr.time_map("audio", n_taps=144)
 
 
+@pytest.mark.parametrize("variant", [7, 8])
+def test_times_at_sixteen_samples_per_bit(variant):
+    """pllinc 4096: the phase is a multiple of the nudge at every sample and meets the loop's equalities (pll == 0x8000 at
+    a transition, == 0x10000 at a slice; tests/test_pll_cpu.py counts them), the segments hold 128 bits instead of 410.
+    The stream of tests/test_pll_gpu.py's message test, ragged calls, both PLL forms: frames and times == restatement."""
+    from gnuais_amd import ReceiverBatch
+    n_ch, sps = 6, 16
+    total = 30 * 256 * sps
+    x = np.stack([synth.make_stream(total, seed=31, channel=c, sps=sps, sigma=1000)[0] for c in range(n_ch)], axis=1)
+    calls = [1, 777, 2047, 2048, 2049, 48000]
+    calls.append(total - sum(calls))
+    b = ReceiverBatch(n_ch, pllinc=0x10000 // sps, max_len=max(calls))
+    b.set_option("pll_variant", variant)
+    b.frame_times(True)
+    ref = ftr.FrameTimeRef(n_ch, None, 0x10000 // sps)
+    cuts = np.cumsum([0] + calls)
+    n_frames = 0
+    for a, e in zip(cuts[:-1], cuts[1:]):
+        b.run(dev(x[a:e]))
+        ref.run(x[a:e])
+        assert b.info("pll_form") == (variant if e - a >= 256 else 8)
+        fr, t = check_drain(b, ref)
+        n_frames += len(fr)
+        assert len(t) == 0 or (t.min() >= 0 and t.max() < e)
+    assert n_frames >= 85
+
+
 @pytest.mark.parametrize("W", [0, 1024])
 def test_times_run_iq(W):
     from gnuais_amd import ReceiverBatch

@@ -7,13 +7,13 @@ import os
 import numpy as np
 import pytest
 
+from chain_parity import batch, dev, fsm_rows, oracle_fsm_rows, run_both
 from gnuais_amd import params, synth
 from oracle_lib import FRAME_DTYPE, Oracle
 
 pytestmark = pytest.mark.gpu
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-FSM_KEYS = ("state", "nstartsign", "antallpreamble", "antallenner", "bitstuff", "last", "bufferpos")
 
 
 def load(name):
@@ -22,32 +22,6 @@ def load(name):
 
 def frames_of(raw):
     return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=FRAME_DTYPE)
-
-
-def batch(*a, **k):
-    from gnuais_amd import ReceiverBatch
-    return ReceiverBatch(*a, **k)
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def fsm_rows(b):
-    f = b.fsm_state()
-    return [[int(r[k]) for k in FSM_KEYS] for r in f]
-
-
-def oracle_fsm_rows(o, n, saturate=True):
-    rows = []
-    for c in range(n):
-        h = o.hdlc(c)
-        r = [h[k] for k in FSM_KEYS]
-        if saturate:
-            r[2] = min(r[2], 15)
-        rows.append(r)
-    return rows
 
 
 # ---------------------------------------------------------------- FIR (K1)
@@ -144,40 +118,6 @@ def test_full_chain_golden(name):
     assert np.array_equal(b.maxval(), g["maxval"])
 
 
-def run_both(x, chunks, n_ch, taps=None, pllinc=0, fir_T=None, pll_variant=0, options=None):
-    o = Oracle(n_ch, taps=taps, pllinc=pllinc)
-    b = batch(n_ch, taps=taps, pllinc=pllinc, max_len=max(chunks))
-    if fir_T:
-        b.set_option("fir_T", fir_T)
-    for k, v in (options or {}).items():
-        b.set_option(k, v)
-    b.set_option("pll_variant", pll_variant)      # 0: by channel count (the time-parallel form up to 1536 channels)
-    pos = 0
-    gbits = [[] for _ in range(n_ch)]
-    obits = [[] for _ in range(n_ch)]
-    for n in chunks:
-        seg = x[pos:pos + n]
-        pos += n
-        r = o.run(seg, want_bits=True)
-        b.run(dev(seg))
-        lb = b.last_bits()
-        for c in range(n_ch):
-            gbits[c].append(lb[c])
-            obits[c].append(r["bits"][c])
-    assert pos == x.shape[0]
-    for c in range(n_ch):
-        assert np.array_equal(np.concatenate(gbits[c]), np.concatenate(obits[c])), c
-    assert b.drain_frames().tobytes() == o.frames().tobytes()
-    cnt = b.counters()
-    assert np.array_equal(np.stack([cnt["receivedframes"], cnt["lostframes"], cnt["lostframes2"]],
-                                   axis=1), o.counters())
-    p = b.pll_state()
-    assert [(int(a), int(bb), int(cc)) for a, bb, cc in zip(p["pll"], p["prev"], p["lastbit"])] == \
-        [o.pll(c) for c in range(n_ch)]
-    assert fsm_rows(b) == oracle_fsm_rows(o, n_ch)
-    return o, b
-
-
 @pytest.mark.parametrize("pll_variant", [7, 8])      # 7: the time-parallel form (pll_tp.hip); 8: one recurrence wave + three helpers (pll_h3.hip)
 def test_chain_vs_oracle_ragged_chunks(pll_variant):
     n_ch, total = 70, 30 * 1280
@@ -239,10 +179,14 @@ def test_time_parallel_pll_walks_out_of_its_window():
 @pytest.mark.parametrize("pll_variant", [7, 8])
 def test_pll_with_a_sign_change_at_every_sample(pll_variant):
     """A table that passes the input through (one tap) and inputs that change sign at every sample, at every second,
-    third ... sample, in bursts between silences, and at random: up to 256 transitions and as many nudges per 256-sample
-    block.  The time-parallel form's value then leaves its +-64 window inside ONE block, chunk after chunk (each chunk
-    still advances by a block: the worst case of its walk); the lane-per-channel form's 128-sample blocks hold their
-    maximum of transitions.  Several pllinc (slices every 4.7 to 20 samples).  == oracle, bit for bit."""
+    third ... sample, in bursts between silences, and at random: up to 256 transitions per 256-sample block, the
+    lane-per-channel form's 128-sample blocks at their maximum of transitions.  The nudges of such inputs ALTERNATE in
+    sign: the net count moves by at most 40 inside a block, from its start to its end included (measured on the
+    reference loop at the three increments below), so the time-parallel form stays inside its +-64 window within a
+    block here (it leaves it by diffusion in
+    test_time_parallel_pll_walks_out_of_its_window and by a steady drift of a window per block in
+    tests/test_pll_gpu.py, whose inputs tests/test_pll_cpu.py measures).  Several pllinc (slices every 4.7 to 20
+    samples).  == oracle, bit for bit."""
     rng = np.random.default_rng(123)
     total = 12000
     taps = np.zeros(9, dtype=np.float32)
