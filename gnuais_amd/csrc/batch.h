@@ -201,6 +201,18 @@ struct gnuais_batch {
     bool frame_times = false;
     unsigned long long rows = 0;
     Buf<int64_t> times;                         // [frame_cap], allocated when the feature is first switched on
+    // The signal power and carrier error of every frame (gnuais_batch_frame_signal, frame_signal.hip; off by default;
+    // needs frame_times).  While it is on, every I/Q-type call launches the ingest kernel in front of its discriminator
+    // (block sums of P, r, i into fs_ring) and every K3 gets one more launch behind its frame_time launch, which
+    // writes signal[slot].  fs_v0: first row of the current run of I/Q-type calls; fs_end: the row behind the last
+    // I/Q-type call (rows != fs_end at the next one: an audio-type call came between, a new run starts); fs_iq_call:
+    // the run call under way came through run_form, so its rows are I/Q rows (else its frames get (0, 0, 0)).
+    bool frame_signal = false, fs_iq_call = false;
+    int fs_RB = 0, fs_nbuf = 0;                 // slots of the ring; the nbuf it was sized for
+    unsigned long long fs_v0 = 0, fs_end = 0;
+    Buf<int64_t> fs_ring;                       // [fs_RB][N][3] (P, R, I), block j of n in slot j % fs_RB
+    Buf<uint32_t> fs_carry;                     // [N] the stage's own previous pair
+    Buf<gnuais_frame_signal> signal;            // [frame_cap], parallel to times
     // The repair of CRC-failed candidates (gnuais_batch_repair, hdlc_repair.hip; off by default): while it is on, one
     // more launch behind each K3 -- in front of the frame_time launch -- appends the repaired frames to ring 0 (a batch
     // with the feature on does not stream) and counts them per channel.

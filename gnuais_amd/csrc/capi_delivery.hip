@@ -64,10 +64,11 @@ static int upload_seq(gnuais_batch *b, const uint8_t *seqnr)
 }
 
 // drain: records and / or sentences of everything queued, consumed once
-// h_times (with h_frames): the records' receive times, through the sort's own permutation
+// h_times (with h_frames): the records' receive times, through the sort's own permutation; h_signal (with h_times):
+// their power and carrier error, likewise
 static int drain_impl(gnuais_batch *b, gnuais_frame *h_frames, int max_frames, int *n_frames,
                       uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len, int *n_sentences,
-                      int64_t *h_times = nullptr)
+                      int64_t *h_times = nullptr, gnuais_frame_signal *h_signal = nullptr)
 {
     // a streaming batch spreads its frames over NRING rings that gnuais_batch_stream_nmea() consumes: ring 0 alone
     // would be a partial view, and clearing its counters would lose frames and error flags
@@ -100,13 +101,17 @@ static int drain_impl(gnuais_batch *b, gnuais_frame *h_frames, int max_frames, i
             // K3 appends the frames in pieces, in whatever order its blocks finish; the reference's
             // print order (channel, then time) is restored on the device -- radix sort of
             // (channel, end_bit), gather -- and the records cross PCIe once, straight into h_frames
-            // (the text buffer holds 164 bytes per frame: the 64 of a record and the 8 of its time fit side by side)
+            // (the text buffer holds 164 bytes per frame: the 64 of a record, the 8 of its time and the 8 of its signal
+            // record fit side by side)
+            static_assert(sizeof(gnuais_frame_signal) == sizeof(int64_t), "the signal records leave through the times' gather");
             gnuais_frame *sorted = reinterpret_cast<gnuais_frame *>(b->d_text.p);
-            int64_t *sorted_t = reinterpret_cast<int64_t *>(sorted + have);
+            int64_t *sorted_t = reinterpret_cast<int64_t *>(sorted + have), *sorted_s = sorted_t + have;
             HIP_TRY(frames_sort_timed(b->ring[0], h_times ? b->times.p : nullptr, (int) have, sorted, sorted_t,
-                                      b->nmea_scratch, b->nmea_scratch.bytes, nullptr));
+                                      b->nmea_scratch, b->nmea_scratch.bytes, nullptr,
+                                      h_signal ? reinterpret_cast<const int64_t *>(b->signal.p) : nullptr, sorted_s));
             HIP_TRY(hipMemcpy(h_frames, sorted, sizeof(gnuais_frame) * have, hipMemcpyDeviceToHost));
             if (h_times) HIP_TRY(hipMemcpy(h_times, sorted_t, sizeof(int64_t) * have, hipMemcpyDeviceToHost));
+            if (h_signal) HIP_TRY(hipMemcpy(h_signal, sorted_s, sizeof(gnuais_frame_signal) * have, hipMemcpyDeviceToHost));
         }
         if (n_frames) *n_frames = (int) have;
     }
@@ -268,6 +273,20 @@ int gnuais_batch_drain_frames_timed(gnuais_batch *b, gnuais_frame *h_out, int64_
     return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr, h_times ? h_times : &none_t);
 }
 
+// the same with, entry for entry, their power and carrier error (gnuais_batch_frame_signal)
+int gnuais_batch_drain_frames_signal(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, gnuais_frame_signal *h_signal,
+                                     int max, int *n_out)
+{
+    if (!b || !n_out || (max > 0 && (!h_out || !h_times || !h_signal))) return fail(GNUAIS_E_ARG, "drain_frames_signal: argument");
+    *n_out = 0;
+    if (!b->frame_signal) return fail(GNUAIS_E_STATE, "drain_frames_signal: the batch does not measure its frames (gnuais_batch_frame_signal)");
+    static gnuais_frame none;
+    static int64_t none_t;
+    static gnuais_frame_signal none_s;
+    return drain_impl(b, h_out ? h_out : &none, max, n_out, nullptr, nullptr, 0, nullptr, nullptr, h_times ? h_times : &none_t,
+                      h_signal ? h_signal : &none_s);
+}
+
 // One record per transmission (gnuais_batch_unique): the queued frames and the open clusters of earlier drains go
 // through frame_unique.hip; the primaries, their times and the copies cross PCIe once.  The carried state -- the tail,
 // the late count -- moves only when everything has succeeded.
@@ -366,6 +385,8 @@ static int stream_setup(gnuais_batch *b)
                                                     "the streamed delivery carries no times");
     if (b->repair) return fail(GNUAIS_E_STATE, "stream_nmea: the batch repairs frames (gnuais_batch_repair); the streamed "
                                                "delivery's order table describes the CRC stage's records only");
+    if (b->frame_signal) return fail(GNUAIS_E_STATE, "stream_nmea: the batch measures its frames (gnuais_batch_frame_signal); "
+                                                     "the streamed delivery carries no records of them");
     if (b->uq_window) return fail(GNUAIS_E_STATE, "stream_nmea: the batch merges duplicates (gnuais_batch_unique); the "
                                                   "streamed delivery has no such stage");
     if (int rc = gnuais_batch_sync(b)) return rc;

@@ -2,6 +2,7 @@
 // carrier-error stage, channeliser with its host tables -- and the entries that take a form's input from device or
 // host memory and hand the audio to gnuais_batch_run (gnuais_capi.hip).  Host code only.
 #include "batch.h"
+#include "frame_signal.h"
 #include "resample_plan.h"
 #include "wide_format.h"
 
@@ -472,6 +473,83 @@ int gnuais_batch_channelise_fmt(gnuais_batch *b, int fmt, const void *d_wide, in
     return channelise(b, fmt, d_wide, len, d_out, stream, "channelise_fmt");
 }
 
+// ---- the signal power and carrier error of every frame (include/gnuais_hip.h, frame_signal.hip) ----
+
+// In front of the discriminator of an I/Q-type call, on its stream s (the discriminator's entry of the drain table covers
+// it: same calls, same stream): the block sums of the call's rows.  The chain has taken b->rows rows: the call's first is n0.
+static int power_launch(gnuais_batch *b, const int16_t *d_iq, int len, hipStream_t s)
+{
+    if (b->rows != b->fs_end) b->fs_v0 = b->rows;        // an audio-type call came between: a new run starts here
+    HIP_TRY(launch_iq_power(d_iq, b->fs_carry, b->fs_ring, b->fs_RB, b->N, len, b->rows, b->rows == b->fs_v0, s));
+    b->fs_end = b->rows + (unsigned long long) len;      // a run call that fails leaves rows behind it: a new run next time
+    return GNUAIS_OK;
+}
+
+// Synchronises: no call is in flight when the switch turns.  The records of what the ring holds start at (0, 0, 0), the
+// run of I/Q-type calls at the current row.
+int gnuais_batch_frame_signal(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "frame_signal: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "frame_signal: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (on && !b->frame_times)
+        return fail(GNUAIS_E_STATE, "frame_signal: the batch does not time its frames (gnuais_batch_frame_times): a frame's "
+                                    "span is found by its receive time");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    b->frame_signal = false;
+    HIP_TRY(b->fs_ring.release());
+    if (!on) return GNUAIS_OK;
+    // The ring's size.  No slot may be written while a frame launch that can still read it is pending.  The ingest
+    // launch of call i is queued before the host waits for the tail of call i - nbuf (gnuais_batch_run: e_done[4][k]),
+    // so while the frame launch of call c is pending, ingest launches up to call c + nbuf may run: they write rows
+    // below n0_c + (nbuf + 1) * max_len.  That frame launch reads from row q - S on, q = t - d_f - W/2 with t >= n0_c:
+    // at most S_max + d_f + W_max/2 rows below n0_c, S_max the span of the longest frame (448 bits).  nbuf + 2 calls
+    // instead of nbuf + 1 leave one call of slack; one block more at either end for the two open ones.
+    // That wait belongs to the pipelined path.  With the pipeline off (set_option("pipeline", 0)) a call's tail runs on
+    // the caller's stream behind its K1, so on one stream the next call's ingest launch is behind the pending frame
+    // launch in stream order, and a call on another stream drains the chain's recorded stream first (run_form passes
+    // the CHAIN bit to drain()): no ingest launch ever runs beside a pending frame launch there.
+    const long long S_max = fs_span_rows(FS_MAX_NBITS, b->pllinc);
+    const long long rows = (long long) (b->nbuf + 2) * b->max_len + S_max + (b->NT + 1) / 2 + AFC_MAX_WINDOW / 2;
+    const long long RB = fs_ceil_div(rows, FS_BLOCK) + 2;
+    if (S_max / FS_BLOCK + 1 > 0xffff || RB > 0x7fffffff)
+        return fail(GNUAIS_E_STATE, "frame_signal: the batch's pllinc gives frames of more than 65535 blocks");
+    const size_t N = (size_t) b->N;
+    if (int rc = alloc_checked(b, b->fs_ring, sizeof(int64_t) * 3 * N * (size_t) RB, "frame_signal", "the ring of block sums"))
+        return rc;
+    HIP_TRY(b->fs_carry.ensure(sizeof(uint32_t) * N));
+    HIP_TRY(b->signal.ensure(sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
+    HIP_TRY(hipMemset(b->signal, 0, sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
+    b->fs_RB = (int) RB;
+    b->fs_nbuf = b->nbuf;
+    b->fs_v0 = b->fs_end = b->rows;
+    b->frame_signal = true;
+    return GNUAIS_OK;
+}
+
+// a parity tap: the ring's sums of the blocks [j0, j0 + count), h_out [count][N][3] (P, R, I)
+int gnuais_batch_signal_blocks(gnuais_batch *b, long long j0, int count, int64_t *h_out)
+{
+    if (!b || count < 0 || (count > 0 && !h_out)) return fail(GNUAIS_E_ARG, "signal_blocks: argument");
+    if (!b->frame_signal) return fail(GNUAIS_E_STATE, "signal_blocks: the batch does not measure its frames (gnuais_batch_frame_signal)");
+    if (int rc = set_device(b)) return rc;
+    // what the ring holds: the blocks of the current run, the one v0 lies in included, that later ones have not replaced
+    const long long end = (long long) ((b->fs_end + FS_BLOCK - 1) / FS_BLOCK);
+    const long long lo = std::max((long long) (b->fs_v0 / FS_BLOCK), end - b->fs_RB);
+    if (j0 < lo || j0 + count > end) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "signal_blocks: blocks [%lld, %lld) asked for, the ring holds [%lld, %lld)", j0, j0 + count, lo, end);
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    if (b->last[DISC].used) HIP_TRY(hipStreamSynchronize(b->last[DISC].s));
+    const size_t blk = 3 * (size_t) b->N;
+    for (int k = 0; k < count; ++k)
+        HIP_TRY(hipMemcpy(h_out + (size_t) k * blk, b->fs_ring + (size_t) ((j0 + k) % b->fs_RB) * blk, sizeof(int64_t) * blk,
+                          hipMemcpyDeviceToHost));
+    return GNUAIS_OK;
+}
+
 // ---- one run path and one host path for every input form ----
 
 // gnuais_batch_run_iq / _run_wideband: on the caller's stream, the stages in front of the chain, each into the
@@ -500,6 +578,8 @@ static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *s
         x = b->wide_iq;
     }
     len = len / f.rows * f.up;
+    if (b->frame_signal)
+        if (int rc = power_launch(b, x, len, s)) return rc;
     if (disc) {
         if (int rc = disc_launch(b, x, len, b->iq_audio, s, afc)) return rc;
         x = b->iq_audio;
@@ -508,7 +588,10 @@ static int run_form(gnuais_batch *b, FormId id, const void *in, int len, void *s
         if (int rc = afc_launch(b, x, len, b->afc_audio, s)) return rc;
         x = b->afc_audio;
     }
-    return gnuais_batch_run(b, x, len, stream);
+    b->fs_iq_call = b->frame_signal;            // the chain's rows of this call are I/Q rows (fill_frame_signal)
+    const int rc = gnuais_batch_run(b, x, len, stream);
+    b->fs_iq_call = false;
+    return rc;
 }
 
 // gnuais_batch_run_host / _run_iq_host / _run_wideband_host: the host input staged in stage_x, then `run`, the

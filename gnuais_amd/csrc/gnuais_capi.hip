@@ -334,6 +334,7 @@ int gnuais_batch_reset(gnuais_batch *b)
         HIP_TRY(hipMemset(b->segcnt[k], 0, sizeof(uint32_t) * N * (size_t) b->n_seg));
     b->calls = 0;
     b->rows = 0;
+    b->fs_v0 = b->fs_end = 0;                   // gnuais_batch_frame_signal: a new run of I/Q-type calls starts at row 0
     b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
@@ -369,6 +370,9 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         b->fir.fir_T = value;
     } else if (!strcmp(name, "nbuf")) {             // hand-off sets in use: the calls that may be in flight
         if (value < 2 || value > gnuais_batch::NBUF) return fail(GNUAIS_E_ARG, "nbuf must be 2..8");
+        if (b->frame_signal && value > b->fs_nbuf)
+            return fail(GNUAIS_E_STATE, "nbuf: the block ring of gnuais_batch_frame_signal is sized for the depth it was switched on "
+                                        "at; switch it off first");
         if (int rc = gnuais_batch_sync(b)) return rc;
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(alloc_sets(b, value));
@@ -381,6 +385,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
             return fail(GNUAIS_E_STATE, "streaming: the batch times its frames (gnuais_batch_frame_times); the streamed delivery carries no times");
         if (value != 0 && b->repair)
             return fail(GNUAIS_E_STATE, "streaming: the batch repairs frames (gnuais_batch_repair); the streamed delivery's order table describes the CRC stage's records only");
+        if (value != 0 && b->frame_signal)
+            return fail(GNUAIS_E_STATE, "streaming: the batch measures its frames (gnuais_batch_frame_signal); the streamed delivery carries no records of them");
         if (value != 0 && b->uq_window)
             return fail(GNUAIS_E_STATE, "streaming: the batch merges duplicates (gnuais_batch_unique); the streamed delivery has no such stage");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
@@ -484,6 +490,20 @@ static FrameTimeLaunch fill_frame_times(const gnuais_batch *b, const HdlcLaunch 
     return t;
 }
 
+// the launch behind that one: the records of a call that did not come through run_form (fs_iq_call) get (0, 0, 0) --
+// v0 behind its last row
+static FrameSignalLaunch fill_frame_signal(const gnuais_batch *b, const HdlcLaunch &h, int len)
+{
+    FrameSignalLaunch a;
+    a.frames = h.frames; a.frame_count = h.frame_count; a.frame_cap = h.frame_cap;
+    a.times = b->times; a.ring = b->fs_ring; a.signal = b->signal.p;
+    a.RB = b->fs_RB; a.N = h.N;
+    a.len = len; a.n0 = (int64_t) b->rows;
+    a.pllinc = b->pllinc; a.n_taps = b->NT; a.afc_window = b->afc_W;
+    a.v0 = (int64_t) (b->fs_iq_call ? b->fs_v0 : b->rows + (unsigned long long) std::max(len, 0));
+    return a;
+}
+
 // the launch behind the K3 described by h, in front of its frame_time launch
 static RepairLaunch fill_repair(const gnuais_batch *b, const HdlcLaunch &h)
 {
@@ -579,6 +599,8 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     // the frames' receive times: behind K3 and in front of e_done[4][k], which is what the reuse of set k (segcnt) and,
     // where K3 has a stream of its own, the next deframer launch (ctl) wait for
     if (b->frame_times && (b->stage_mask & 16)) HIP_TRY(launch_frame_times(fill_frame_times(b, h, len), sD));
+    // their power and carrier error: behind the times it selects its records by, in front of e_done[4][k] (frame_signal.hip)
+    if (b->frame_signal && (b->stage_mask & 16)) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, len), sD));
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -815,6 +837,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         HIP_TRY(launch_hdlc_crc(h, nullptr));
         if (b->repair) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), nullptr));
         if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1
+        if (b->frame_signal) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, 0), nullptr));   // and (0, 0, 0)
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
@@ -1012,6 +1035,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "afc_window")) *value = b->afc_W;
     else if (!strcmp(name, "segments")) *value = b->n_seg;
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
+    else if (!strcmp(name, "frame_signal")) *value = b->frame_signal;
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
     else if (!strcmp(name, "pll_form")) *value = b->pll_form;
     else if (!strcmp(name, "repair")) *value = b->repair;
@@ -1039,6 +1063,9 @@ int gnuais_batch_frame_times(gnuais_batch *b, int on)
     if (!on && b->uq_window)
         return fail(GNUAIS_E_STATE, "frame_times: the batch merges duplicates by their times (gnuais_batch_unique); "
                                     "gnuais_batch_unique(b, 0) first");
+    if (!on && b->frame_signal)
+        return fail(GNUAIS_E_STATE, "frame_times: the batch finds its frames' spans by their times (gnuais_batch_frame_signal); "
+                                    "gnuais_batch_frame_signal(b, 0) first");
     if (int rc = gnuais_batch_sync(b)) return rc;
     if (on && !b->frame_times) {
         HIP_TRY(b->times.ensure(sizeof(int64_t) * (size_t) b->frame_cap));

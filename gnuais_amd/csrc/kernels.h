@@ -130,6 +130,31 @@ hipError_t launch_frame_times(const FrameTimeLaunch &a, hipStream_t stream);
 // times[order[j]] -> out[j], j < n: the times in the order of a sorted drain (frames_sort_timed)
 hipError_t launch_frame_times_gather(const int64_t *times, const uint32_t *order, int n, int64_t *out, hipStream_t stream);
 
+// ---- the signal power and carrier error of every frame (frame_signal.hip; definition in include/gnuais_hip.h) ----
+// launch_iq_power: in front of the discriminator of an I/Q-type call, on its stream.  iq [len][N][2] int16 is what that
+// discriminator reads; n0 = rows the chain had taken before the call; carry [N] words is the stage's own previous pair;
+// ring [RB][N][3] int64 (P, R, I) holds block j of n in slot j % RB, RB >= len / 64 + 2.  first: the call starts a run of
+// I/Q-type calls (n0 == v0): the previous pair is (0, 0) and the open block is set, not added to.
+hipError_t launch_iq_power(const int16_t *iq, uint32_t *carry, int64_t *ring, int RB, int N, int len,
+                           unsigned long long n0, bool first, hipStream_t stream);
+// launch_frame_signal: behind the frame_time launch of the same call, on its stream.  Writes signal[i] for every record i
+// of the ring with times[i] < 0 -- (0, 0, 0) -- or n0 <= times[i] < n0 + len; other records are left alone.
+struct FrameSignalLaunch {
+    const void *frames;            // gnuais_frame[frame_cap]: the ring K3 appended to
+    const uint32_t *frame_count;   // its counters ([0] = frames appended)
+    uint32_t frame_cap;
+    const int64_t *times;          // [frame_cap], by ring slot (frame_time.hip)
+    const int64_t *ring;           // [RB][N][3]
+    void *signal;                  // gnuais_frame_signal[frame_cap], by ring slot
+    int RB, N;
+    int len;                       // rows of the call (<= 0: bits without samples)
+    int64_t n0;                    // rows the chain had taken before it
+    uint32_t pllinc;
+    int n_taps, afc_window;
+    int64_t v0;                    // first row of the current run of I/Q-type calls
+};
+hipError_t launch_frame_signal(const FrameSignalLaunch &a, hipStream_t stream);
+
 // ---- utilities (util.hip) ---------------------------------------------------
 hipError_t launch_tile_channels(const int16_t *base, int n_base, int len, int16_t *out,
                                 int n_channels, hipStream_t stream);
@@ -198,9 +223,11 @@ size_t nmea_scratch_bytes(int n_frames, int n_chunks = 0);
 // frames[n] (device) -> out[n] (device) in print order: channel, then end_bit
 hipError_t frames_sort(const struct gnuais_frame *frames, int n, struct gnuais_frame *out, void *scratch,
                        size_t scratch_bytes, hipStream_t s);
-// the same, and times[n] (by ring slot, frame_time.hip) -> times_out[n] through the same permutation
+// the same, and times[n] (by ring slot, frame_time.hip) -> times_out[n] through the same permutation; words: a second
+// array of 64-bit words by ring slot (the 8-byte records of frame_signal.hip), -> words_out[n] likewise
 hipError_t frames_sort_timed(const struct gnuais_frame *frames, const int64_t *times, int n, struct gnuais_frame *out,
-                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s);
+                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s,
+                             const int64_t *words = nullptr, int64_t *words_out = nullptr);
 // the device part only, queued without waiting; h_info4 (host, pinned): [0] + [1] bytes written,
 // [2] sentences, [3] != 0 if a frame named a channel >= n_channels -- valid once `s` has got there
 // n > 0: count known to the host, order by radix sort.  n < 0: the ring holds exactly one call; order and

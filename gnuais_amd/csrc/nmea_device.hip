@@ -991,7 +991,8 @@ hipError_t frames_sort(const gnuais_frame *frames, int n, gnuais_frame *out, voi
 // The timed form: the frames' receive times (by ring slot) leave through the same permutation, so that times_out[i]
 // belongs to out[i].  times == nullptr: the records only.
 hipError_t frames_sort_timed(const gnuais_frame *frames, const int64_t *times, int n, gnuais_frame *out,
-                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s)
+                             int64_t *times_out, void *scratch, size_t scratch_bytes, hipStream_t s,
+                             const int64_t *words, int64_t *words_out)
 {
     if (n <= 0) return hipSuccess;
     if (scratch_bytes < nmea_scratch_bytes(n)) return hipErrorInvalidValue;
@@ -1007,7 +1008,8 @@ hipError_t frames_sort_timed(const gnuais_frame *frames, const int64_t *times, i
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(frames_gather_kernel, dim3((4 * n + 255) / 256), dim3(256), 0, s, frames, idx2, n, out);
     if ((e = hipGetLastError()) != hipSuccess || !times) return e;
-    return launch_frame_times_gather(times, idx2, n, times_out, s);
+    if ((e = launch_frame_times_gather(times, idx2, n, times_out, s)) != hipSuccess || !words) return e;
+    return launch_frame_times_gather(words, idx2, n, words_out, s);      // 64-bit words: the times' own gather serves
 }
 
 // The slot's eight info words, kept on the device: the formatter's four (offset and length of the last

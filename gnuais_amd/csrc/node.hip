@@ -525,6 +525,12 @@ int gnuais_node_frame_times(gnuais_node *nd, int on)
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_times(s.b, on); });
 }
 
+int gnuais_node_frame_signal(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_frame_signal: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_signal(s.b, on); });
+}
+
 int gnuais_node_repair(gnuais_node *nd, int on)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_repair: NULL node");
@@ -537,7 +543,8 @@ int gnuais_node_repaired(gnuais_node *nd, int32_t *h_out)
     return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_repaired(s.b, h_out + s.first); });
 }
 
-static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
+static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out,
+                      gnuais_frame_signal *h_signal = nullptr);
 
 int gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int *n_out)
 {
@@ -553,7 +560,16 @@ int gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_t
     return node_drain(nd, h_out, h_times, max, n_out);
 }
 
-static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out)
+// and with every record's power and carrier error (gnuais_batch_drain_frames_signal on every shard)
+int gnuais_node_drain_frames_signal(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, gnuais_frame_signal *h_signal,
+                                    int max, int *n_out)
+{
+    if (!nd || !h_out || !h_times || !h_signal || !n_out || max < 0)
+        return node_fail(GNUAIS_E_ARG, "node_drain_frames_signal: argument");
+    return node_drain(nd, h_out, h_times, max, n_out, h_signal);
+}
+
+static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out, gnuais_frame_signal *h_signal)
 {
     *n_out = 0;
     int total = 0;
@@ -575,8 +591,9 @@ static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, in
     }
     const int rc = run_all(nd, [&](Shard &s, size_t i) {
         int got = 0;
-        const int r = h_times ? gnuais_batch_drain_frames_timed(s.b, h_out + off[i], h_times + off[i], cnt[i], &got)
-                              : gnuais_batch_drain_frames(s.b, h_out + off[i], cnt[i], &got);
+        const int r = h_signal ? gnuais_batch_drain_frames_signal(s.b, h_out + off[i], h_times + off[i], h_signal + off[i], cnt[i], &got)
+                      : h_times ? gnuais_batch_drain_frames_timed(s.b, h_out + off[i], h_times + off[i], cnt[i], &got)
+                                : gnuais_batch_drain_frames(s.b, h_out + off[i], cnt[i], &got);
         for (int k = 0; k < got; ++k) h_out[off[i] + k].channel += (uint32_t) s.first;
         cnt[i] = got;
         return r;
@@ -586,6 +603,7 @@ static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, in
     for (size_t i = 0; i < sh.size(); ++i) {
         if (off[i] != w && cnt[i] > 0) memmove(h_out + w, h_out + off[i], sizeof(gnuais_frame) * (size_t) cnt[i]);
         if (off[i] != w && cnt[i] > 0 && h_times) memmove(h_times + w, h_times + off[i], sizeof(int64_t) * (size_t) cnt[i]);
+        if (off[i] != w && cnt[i] > 0 && h_signal) memmove(h_signal + w, h_signal + off[i], sizeof(gnuais_frame_signal) * (size_t) cnt[i]);
         w += cnt[i];
     }
     *n_out = w;

@@ -23,6 +23,9 @@ FSM_DTYPE = np.dtype([("state", "<i4"), ("nstartsign", "<i4"), ("antallpreamble"
                       ("antallenner", "<i4"), ("bitstuff", "<i4"), ("last", "<i4"),
                       ("bufferpos", "<i4")])
 assert FRAME_DTYPE.itemsize == 64
+# struct gnuais_frame_signal: a frame's power (full scale 2^31), carrier error and blocks measured (0: no measurement)
+SIGNAL_DTYPE = np.dtype([("power", "<u4"), ("ferr", "<i2"), ("blocks", "<u2")])
+assert SIGNAL_DTYPE.itemsize == 8
 FRAME_REPAIRED = 0x40         # GNUAIS_FRAME_REPAIRED: frame flags bit 6
 
 # kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
@@ -78,6 +81,10 @@ SYMBOLS = {
     "gnuais_batch_pending_frames": (_I, [_P, C.POINTER(_I)]),
     "gnuais_batch_frame_times": (_I, [_P, _I]),
     "gnuais_batch_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_frame_signal": (_I, [_P, _I]),
+    "gnuais_batch_drain_frames_signal": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_signal_blocks": (_I, [_P, C.c_longlong, _I, _P]),
+    "gnuais_frame_signal_span": (_I, [C.c_longlong, _I, _U, _I, _I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_I)]),
     "gnuais_batch_time_map": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_batch_time_map_ratio": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_nmea_tagged_from_frames": (_I, [_P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
@@ -152,6 +159,8 @@ SYMBOLS = {
     "gnuais_node_drain_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_frame_times": (_I, [_P, _I]),
     "gnuais_node_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_frame_signal": (_I, [_P, _I]),
+    "gnuais_node_drain_frames_signal": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_repair": (_I, [_P, _I]),
     "gnuais_node_repaired": (_I, [_P, _P]),
     "gnuais_node_unique": (_I, [_P, _I]),
@@ -204,6 +213,25 @@ def check(rc: int, allow=()) -> int:
     if rc != OK and rc not in allow:
         raise GnuaisError(rc, load().gnuais_last_error().decode())
     return rc
+
+
+def signal_dbfs(power) -> np.ndarray:
+    """gnuais_frame_signal.power -> dB relative to full scale (2^31 = a pair of -32768s); -inf where it is 0"""
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(np.asarray(power, dtype=np.float64) / 2.0 ** 31)
+
+
+def signal_hz(ferr, rate) -> np.ndarray:
+    """gnuais_frame_signal.ferr -> Hz at `rate` chain rows per second"""
+    return np.asarray(ferr, dtype=np.float64) * float(rate) / 65536.0
+
+
+def frame_signal_span(t: int, nbits: int, pllinc: int, n_taps: int = 36, afc_window: int = 0, v0: int = 0):
+    """gnuais_frame_signal_span(): (j_lo, nb), the whole blocks of 64 rows under a frame; (0, 0): no record"""
+    j_lo, nb = C.c_longlong(0), C.c_int(0)
+    check(load().gnuais_frame_signal_span(int(t), int(nbits), int(pllinc), int(n_taps), int(afc_window), int(v0),
+                                          C.byref(j_lo), C.byref(nb)))
+    return j_lo.value, nb.value
 
 
 def default_taps() -> np.ndarray:

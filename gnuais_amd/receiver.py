@@ -367,6 +367,31 @@ class ReceiverBatch:
                                                         C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy()
 
+    def frame_signal(self, on: bool = True):
+        """gnuais_batch_frame_signal(): from now on every frame of I/Q and wideband input gets its signal power and
+        carrier error (the definition is in include/gnuais_hip.h); one more launch per I/Q-type call and one per call.
+        Needs frame_times().  Synchronises.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_frame_signal(self._h, int(bool(on))))
+
+    def drain_frames_signal(self):
+        """gnuais_batch_drain_frames_signal(): (frames, int64 times, signal), signal a structured array (lib.SIGNAL_DTYPE)
+        with power (full scale 2^31; signal_dbfs()), ferr (signal_hz()) and blocks (0: no measurement) of frames[i]"""
+        n = max(self.pending_frames(), 1)
+        out = np.zeros(n, dtype=FRAME_DTYPE)
+        times = np.zeros(n, dtype=np.int64)
+        sig = np.zeros(n, dtype=_lib.SIGNAL_DTYPE)
+        got = C.c_int()
+        check(self._lib.gnuais_batch_drain_frames_signal(self._h, out.ctypes.data, times.ctypes.data, sig.ctypes.data, n,
+                                                         C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy(), sig[: got.value].copy()
+
+    def signal_blocks(self, j0: int, count: int) -> np.ndarray:
+        """gnuais_batch_signal_blocks(): int64 [count][n_channels][3], the sums (P, R, I) of the blocks [j0, j0 + count)
+        of 64 rows (a parity tap)"""
+        out = np.zeros((max(count, 0), self.n_channels, 3), dtype=np.int64)
+        check(self._lib.gnuais_batch_signal_blocks(self._h, int(j0), int(count), out.ctypes.data))
+        return out
+
     def unique(self, window: int):
         """gnuais_batch_unique(): window > 0 rows: drain_frames_unique() delivers each transmission once (equal frames
         whose receive times chain within the window; the definition is in include/gnuais_hip.h); 0: off.  Needs

@@ -236,6 +236,22 @@ class ReceiverNode:
                                                              self._C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy()
 
+    def frame_signal(self, on: bool = True):
+        """gnuais_batch_frame_signal() on every shard"""
+        self._raise(self._lib.gnuais_node_frame_signal(self._h, int(bool(on))))
+
+    def drain_frames_signal(self):
+        """gnuais_node_drain_frames_signal(): (frames, int64 times, signal), as drain_frames_timed with every record's
+        power, carrier error and blocks (lib.SIGNAL_DTYPE)"""
+        from .lib import FRAME_DTYPE, SIGNAL_DTYPE
+        np_ = self._np
+        n = max(self.pending_frames(), 1)
+        out, times, sig = np_.zeros(n, dtype=FRAME_DTYPE), np_.zeros(n, dtype=np_.int64), np_.zeros(n, dtype=SIGNAL_DTYPE)
+        got = self._C.c_int()
+        self._raise(self._lib.gnuais_node_drain_frames_signal(self._h, out.ctypes.data, times.ctypes.data, sig.ctypes.data,
+                                                              n, self._C.byref(got)))
+        return out[: got.value].copy(), times[: got.value].copy(), sig[: got.value].copy()
+
     def unique(self, window: int):
         """gnuais_node_unique(): each transmission once over the whole node (merged on the host: the shards exchange
         nothing); window in rows, 0 = off.  Needs frame_times()."""

@@ -355,6 +355,7 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
+ * "frame_signal" (gnuais_batch_frame_signal(); 0 = off),
  * "repair" (gnuais_batch_repair(); 0 = off), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
  * (gnuais_batch_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
  * one, 8 the lane-per-channel one; 0 before any call and after a reset) */
@@ -450,6 +451,68 @@ int  gnuais_nmea_tagged_from_frames(const gnuais_frame *frames, const int64_t *t
 				    int n_channels, long long mul, long long off, long long rate_hz,
 				    long long epoch_s, char *out, size_t out_cap, size_t *out_len,
 				    int *n_sentences);
+
+/* ---- how strong a frame was and how far off frequency: signal power and carrier error per frame ------------------------
+ * Not in the reference (it reads discriminator audio, where a level says nothing).  For I/Q and wideband input every
+ * frame gets the mean power of the raw I/Q under it and the power-weighted mean frequency of that I/Q: what an SDR AIS
+ * receiver reports per message, what ranks stations, maps coverage and reads an SDR's ppm.  Off by default: while off, a
+ * call launches exactly what it launches without this section.  While on, every I/Q-type call launches one more kernel
+ * in front of its discriminator, and every call one more behind its frame-time launch.
+ * Rows.
+ *   n is the chain's row counter (gnuais_batch_info "rows").
+ *   x[n] = (I, Q) is the int16 pair an I/Q-type call hands to the discriminator as row n: the caller's pair for
+ *   gnuais_batch_run_iq, the channeliser's output pair for gnuais_batch_run_wideband* (and their host forms).
+ *   v0 is the first row of the current unbroken run of I/Q-type calls.  It is set to the current n when the feature is
+ *   switched on, when gnuais_batch_reset is called, and when the first I/Q-type call follows an audio-type run call.
+ *   (While an audio-type run call runs, v0 counts as the row behind that call: its rows are no x[n].)
+ *   The previous pair of x[v0] is (0, 0).  This is the stage's own carry, not the discriminator's.
+ * Per row, exact integers, (Ip, Qp) = x[n - 1]:
+ *   P = I*I + Q*Q (reaches 2^31),  r = I*Ip + Q*Qp,  i = Q*Ip - I*Qp (the AFC's terms; r reaches 2^31)
+ * Per block.  Block j covers the rows [64j, 64j + 64) of n.  P_j, R_j and I_j are the int64 sums of P, r and i over the
+ *   block.  They are sums of the stream, so they do not depend on where calls are cut.  (Rows of block v0 div 64 that
+ *   lie before v0 count as zero; no record below reads that block unless v0 is its first row.)
+ * Per frame.  A frame has its time t (gnuais_batch_frame_times) and nbits.  With d_f and W as in
+ *   gnuais_batch_time_map(GNUAIS_INPUT_IQ):
+ *     q = t - d_f - W/2
+ *     S = floor((nbits + 24) * 65536 / pllinc)      payload, CRC and closing flag at the nominal bit length; stuffed
+ *                                                   bits only make the burst longer
+ *     j_lo = ceil((q - S) / 64),  j_hi = floor((q + 1) / 64),  nb = j_hi - j_lo      (floor and ceil also for negative values)
+ *   These are the whole blocks inside [q - S, q].  The record is (0, 0, 0) when t < 0, nb <= 0 or 64 * j_lo < v0.
+ *   Otherwise, with the sums over j in [j_lo, j_hi):
+ *     power  = floor(sum P_j / (64 * nb)), uint32.  Full scale is 2^31: dBFS = 10 * log10(power / 2^31).
+ *     ferr   = the AFC's e formula (above gnuais_batch_afc) on re = (float) sum R_j, im = (float) sum I_j: int64 -> fp32
+ *              with round to nearest even, then the discriminator's phase from ax = |re| onward.  int16; Hz = ferr * rate / 65536.
+ *     blocks = nb, uint16.
+ *   ferr is the power-weighted mean frequency of the raw I/Q over the frame.  The AFC does not change it.  It also carries
+ *   the deviation times the imbalance of the frame's own NRZI levels: a property of the estimator (DESIGN.md 4.15 has
+ *   the measured spread); no correction for it is made.
+ *   Repaired frames get a record like any frame.  Frames of gnuais_batch_decode_bits (t = -1), frames closed by an
+ *   audio-type run call and frames appended while the feature was off give (0, 0, 0).
+ * gnuais_batch_frame_signal(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE unless frame times are on,
+ *   and on a streaming batch; while it is on, gnuais_batch_frame_times(b, 0), the three ways into streaming and
+ *   set_option("nbuf") above the depth it was switched on at return GNUAIS_E_STATE.  It allocates a ring of block sums of
+ *   24 bytes per channel and block that covers nbuf + 2 calls of max_len rows (GNUAIS_E_HIP with both figures when the
+ *   device has no room); switching it off frees the ring.
+ * gnuais_batch_drain_frames_signal(): gnuais_batch_drain_frames_timed() with h_signal[i] = the record of h_out[i].
+ *   GNUAIS_E_STATE while the feature is off.  Every other drain keeps working while it is on.
+ * gnuais_batch_signal_blocks(): a parity tap.  h_out[count][n_channels][3] = (P_j, R_j, I_j) of the blocks
+ *   [j0, j0 + count) of the current run.  GNUAIS_E_ARG for blocks the ring does not hold (before block v0 div 64, behind
+ *   the last I/Q-type call's rows, or replaced by later ones).  Waits for the last I/Q-type call's ingest.
+ * gnuais_frame_signal_span(): the span arithmetic alone, host code: *j_lo and *nb of a frame with time t, or 0 and 0
+ *   where the record is (0, 0, 0).  GNUAIS_E_ARG for pllinc = 0 or above 0xffff, nbits outside 0..65535, negative n_taps
+ *   or afc_window.
+ * gnuais_batch_info "frame_signal" (0 / 1). */
+typedef struct gnuais_frame_signal {
+	uint32_t power;        /* floor(mean I^2 + Q^2) over the frame's whole blocks; full scale 2^31 */
+	int16_t  ferr;         /* carrier error, Hz = ferr * rate / 65536 */
+	uint16_t blocks;       /* blocks of 64 rows measured; 0: no measurement, power = ferr = 0 */
+} gnuais_frame_signal;
+int  gnuais_batch_frame_signal(gnuais_batch *b, int on);
+int  gnuais_batch_drain_frames_signal(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, gnuais_frame_signal *h_signal,
+                                      int max, int *n_out);
+int  gnuais_batch_signal_blocks(gnuais_batch *b, long long j0, int count, int64_t *h_out);
+int  gnuais_frame_signal_span(long long t, int nbits, unsigned pllinc, int n_taps, int afc_window, long long v0,
+                              long long *j_lo, int *nb);
 
 /* ---- repair of frames that fail the CRC by one symbol error ---------------------------------------------------------
  * The slicer decides line levels and the NRZI decoder differentiates them, so one wrong level decision is two adjacent
@@ -789,6 +852,10 @@ int  gnuais_node_drain_frames(gnuais_node *nd, gnuais_frame *h_out, int max, int
  * belongs to h_out[i]; global channel numbers and the reference's order as gnuais_node_drain_frames */
 int  gnuais_node_frame_times(gnuais_node *nd, int on);
 int  gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out);
+/* gnuais_batch_frame_signal() on every shard, and the merged drain with every record's power and carrier error */
+int  gnuais_node_frame_signal(gnuais_node *nd, int on);
+int  gnuais_node_drain_frames_signal(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, gnuais_frame_signal *h_signal,
+                                     int max, int *n_out);
 /* gnuais_batch_repair() on every shard, and the repairs per global channel */
 int  gnuais_node_repair(gnuais_node *nd, int on);
 int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);

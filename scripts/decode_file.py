@@ -34,11 +34,19 @@
                                                       # merged on the device (gnuais_batch_unique) and the earliest intact copy
                                                       # is printed.  Implies --times.  --verbose: "copies N" per transmission on
                                                       # stderr; the summary counts copies and late copies
+  ... --signal
+                                                      # --iq / --wideband: how strong every frame was and how far off frequency
+                                                      # it arrived, measured on the device over the raw I/Q under the frame
+                                                      # (gnuais_batch_frame_signal): one line per frame on stderr with its
+                                                      # power in dBFS and its carrier error in Hz.  Implies --times.
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+
+
+CHAIN_RATE = 48000      # rows per second of the chain this script builds (the default table: ReceiverBatch without taps / pllinc)
 
 
 def wideband_arg(v):
@@ -77,12 +85,19 @@ def main():
     ap.add_argument("--unique", type=int, default=0, metavar="ROWS",
                     help="print each transmission once: merge equal frames whose receive times chain within ROWS rows of the "
                          "chain's clock (gnuais_batch_unique; 128 suits receivers of one site); implies --times")
+    ap.add_argument("--signal", action="store_true",
+                    help="--iq / --wideband: every frame's power (dBFS) and carrier error (Hz) on stderr "
+                         "(gnuais_batch_frame_signal); implies --times")
     ap.add_argument("--verbose", action="store_true", help="--unique: the copies of every printed transmission, on stderr")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
     if a.unique < 0:
         sys.exit("--unique takes a window in rows, > 0")
-    a.times = a.times or a.unique > 0
+    if a.signal and not (a.iq or a.wideband):
+        sys.exit("--signal needs --iq or --wideband: it measures the I/Q under a frame, audio input has none")
+    if a.signal and a.unique:
+        sys.exit("--signal is not for --unique: the merged drain carries no signal records")
+    a.times = a.times or a.unique > 0 or a.signal
     if a.times and a.text:
         sys.exit("--times tags NMEA sentences: not with --text")
     import torch
@@ -117,6 +132,8 @@ def main():
         b.frame_times(True)
     if a.repair:
         b.repair(True)
+    if a.signal:
+        b.frame_signal(True)
     if a.unique:
         b.unique(a.unique)
     for part in io.chunks(x, a.call):
@@ -143,6 +160,15 @@ def write_sentences(a, b, seq, kind, rate):
         if a.verbose:
             for f, t, c in zip(frames, times, copies):
                 sys.stderr.write(f"  copies {int(c)}: receiver {int(f['channel'])}, row {int(t)}, {int(f['nbits'])} bits\n")
+    elif a.signal:
+        from gnuais_amd.lib import signal_dbfs, signal_hz
+        frames, times, sig = b.drain_frames_signal()
+        for f, t, s in zip(frames, times, sig):
+            if s["blocks"]:                                # ferr is counted in the chain's rows
+                sys.stderr.write(f"  signal: receiver {int(f['channel'])}, row {int(t)}, {signal_dbfs(s['power']):.1f} dBFS, "
+                                 f"{signal_hz(s['ferr'], CHAIN_RATE):+.0f} Hz\n")
+            else:
+                sys.stderr.write(f"  signal: receiver {int(f['channel'])}, row {int(t)}, not measured\n")
     elif a.times:
         frames, times = b.drain_frames_timed()
     if a.times:
@@ -219,6 +245,8 @@ def decode_wideband(a, rate, x, fmt=None):
         b.frame_times(True)
     if a.repair:
         b.repair(True)
+    if a.signal:
+        b.frame_signal(True)
     if a.unique:
         b.unique(a.unique)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
