@@ -222,11 +222,12 @@ struct gnuais_batch {
     // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
     // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the
     // stage's scratch, which grows on first use like nmea_scratch.  Nothing runs per call; only
-    // gnuais_batch_drain_frames_unique touches any of it.
+    // gnuais_batch_drain_frames_unique and _heard (the same drain with the clusters' member lists) touch any of it.
     int uq_window = 0, uq_hash_bits = 64, uq_cur = 0, uq_n_tail = 0;
     long long uq_late = 0;
     Buf<uint32_t> uq_tail[2];
     Buf<void> uq_scratch;
+    Buf<void> uq_heard;                         // gnuais_batch_drain_frames_heard's own scratch, on its first use
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)

@@ -290,11 +290,11 @@ int gnuais_batch_drain_frames_signal(gnuais_batch *b, gnuais_frame *h_out, int64
 // One record per transmission (gnuais_batch_unique): the queued frames and the open clusters of earlier drains go
 // through frame_unique.hip; the primaries, their times and the copies cross PCIe once.  The carried state -- the tail,
 // the late count -- moves only when everything has succeeded.
-int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
-                                     int *n_out)
+// h_first (with h_members and n_members): the clusters' member lists as well (gnuais_batch_drain_frames_heard); the
+// launches of a drain without them are what they were.
+static int drain_unique_impl(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max, int *n_out,
+                             int32_t *h_first, gnuais_hearer *h_members, int *n_members)
 {
-    if (!b || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
-        return fail(GNUAIS_E_ARG, "drain_frames_unique: argument");
     *n_out = 0;
     if (!b->uq_window) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch does not merge duplicates (gnuais_batch_unique)");
     if (b->streaming) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch is streaming (gnuais_batch_stream_nmea)");
@@ -329,6 +329,18 @@ int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64
         a.out_frames = reinterpret_cast<gnuais_frame *>(b->d_text.p);
         a.out_times = reinterpret_cast<int64_t *>(a.out_frames + have);
         a.out_copies = reinterpret_cast<int32_t *>(a.out_times + have);
+        if (h_first) {
+            // ... and behind them the lists: 4 bytes per cluster and one more, 24 per member, 104 * have + 16 in all
+            static_assert(sizeof(gnuais_hearer) == 24 && sizeof(gnuais_frame_signal) == 8, "a member is three 64-bit words");
+            const size_t need_h = unique_heard_scratch_bytes((int) have);
+            HIP_TRY(b->uq_heard.grow(need_h, need_h / 4));
+            a.signal = b->frame_signal ? b->signal.p : nullptr;
+            a.heard_scratch = b->uq_heard;
+            a.heard_scratch_bytes = b->uq_heard.bytes;
+            a.out_first = a.out_copies + have;
+            const uintptr_t at = reinterpret_cast<uintptr_t>(a.out_first + have + 1);
+            a.out_members = reinterpret_cast<gnuais_hearer *>((at + 15) & ~(uintptr_t) 15);
+        }
         uint32_t info[UNIQUE_INFO_WORDS] = {0};
         for (int exact = 0; exact < 2; ++exact) {
             HIP_TRY(unique_cluster_enqueue(a, exact != 0, nullptr));
@@ -342,6 +354,13 @@ int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64
             HIP_TRY(hipMemcpy(h_out, a.out_frames, sizeof(gnuais_frame) * np, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(h_times, a.out_times, sizeof(int64_t) * np, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+            if (h_first) {
+                HIP_TRY(hipMemcpy(h_first, a.out_first, sizeof(int32_t) * ((size_t) np + 1), hipMemcpyDeviceToHost));
+                const int32_t nm = h_first[np];
+                if (nm < 0 || (uint32_t) nm > have) return fail(GNUAIS_E_HIP, "drain_frames_heard: the stage's counts are out of range");
+                HIP_TRY(hipMemcpy(h_members, a.out_members, sizeof(gnuais_hearer) * (size_t) nm, hipMemcpyDeviceToHost));
+                *n_members = (int) nm;
+            }
         }
         unsigned long long late = 0;
         memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
@@ -350,7 +369,26 @@ int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64
         b->uq_late += (long long) late;
         *n_out = (int) np;
     }
-    return finish_drain(b, pend, "drain_frames_unique", "; results are incomplete");
+    return finish_drain(b, pend, h_first ? "drain_frames_heard" : "drain_frames_unique", "; results are incomplete");
+}
+
+int gnuais_batch_drain_frames_unique(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                     int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
+        return fail(GNUAIS_E_ARG, "drain_frames_unique: argument");
+    return drain_unique_impl(b, h_out, h_times, h_copies, max, n_out, nullptr, nullptr, nullptr);
+}
+
+// the same drain with, for every cluster, the list of its members: who heard the transmission, when and how strongly
+int gnuais_batch_drain_frames_heard(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                    int *n_out, int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    if (!b || !n_out || !n_members || !h_first || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies || !h_members)))
+        return fail(GNUAIS_E_ARG, "drain_frames_heard: argument");
+    *n_members = 0;
+    h_first[0] = 0;
+    return drain_unique_impl(b, h_out, h_times, h_copies, max, n_out, h_first, h_members, n_members);
 }
 
 int gnuais_batch_drain_nmea(gnuais_batch *b, uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len,

@@ -37,6 +37,7 @@ struct Member {
 struct Primary {
     uint64_t order;             // output_word()
     int src, copies;
+    size_t start;               // its members: mem[start .. start + copies) of the sort, unused for an untimed frame
 };
 
 Key key_of(const gnuais_frame &f)
@@ -81,8 +82,24 @@ int gnuais_uniq_reset(gnuais_uniq *u)
 
 long long gnuais_uniq_late(const gnuais_uniq *u) { return u ? u->late : 0; }
 
-int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, int n, long long rows,
-                     gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out)
+} // extern "C"
+
+namespace {
+
+gnuais_hearer hearer_of(const gnuais_frame &f, long long t, const gnuais_frame_signal *signal)
+{
+    gnuais_hearer h;
+    h.channel = f.channel;
+    h.flags = f.flags;
+    h.t = t < 0 ? -1 : t;
+    h.signal = signal ? *signal : gnuais_frame_signal{0, 0, 0};
+    return h;
+}
+
+// one drain of the definition; with out_first the member lists of gnuais_batch_drain_frames_heard as well
+int push_impl(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, const gnuais_frame_signal *signal, int n,
+              long long rows, gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out,
+              int32_t *out_first, gnuais_hearer *out_members, int *n_members)
 {
     if (!u || !n_out || n < 0 || cap < 0 || rows < 0 || (n > 0 && (!frames || !times)) ||
         (cap > 0 && (!out || !out_times || !out_copies)))
@@ -97,7 +114,7 @@ int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *
         if (times[i] < 0) {             // untimed: a cluster by itself
             uint32_t rec[16];
             memcpy(rec, &frames[i], sizeof rec);
-            prim.push_back(Primary{output_word(-1, frames[i].channel, stamp37(rec)), i, 1});
+            prim.push_back(Primary{output_word(-1, frames[i].channel, stamp37(rec)), i, 1, 0});
         } else {
             mem.push_back(Member{key_of(frames[i]), times[i], frames[i].channel, i});
         }
@@ -126,7 +143,7 @@ int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *
                 memcpy(rec, &frames[mem[j].src], sizeof rec);
                 if (!repaired_bit(rec)) { p = j; break; }
             }
-            prim.push_back(Primary{output_word(mem[p].t, mem[p].channel, 0), mem[p].src, size});
+            prim.push_back(Primary{output_word(mem[p].t, mem[p].channel, 0), mem[p].src, size, s});
         }
         if (mem[e - 1].t + W >= rows) tail.push_back(Tail{mem[s].key, mem[e - 1].t});
         s = e;
@@ -140,10 +157,47 @@ int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *
         out_times[j] = times[prim[j].src];
         out_copies[j] = prim[j].copies;
     }
+    if (out_first) {
+        // the members of a cluster lie together in the sort, in member order (t, channel); late ones are listed nowhere
+        int32_t at = 0;
+        out_first[0] = 0;
+        for (size_t j = 0; j < prim.size(); ++j) {
+            const Primary &p = prim[j];
+            if (times[p.src] < 0) {
+                out_members[at++] = hearer_of(frames[p.src], -1, signal ? signal + p.src : nullptr);
+            } else {
+                for (size_t k = p.start; k < p.start + (size_t) p.copies; ++k)
+                    out_members[at++] = hearer_of(frames[mem[k].src], mem[k].t, signal ? signal + mem[k].src : nullptr);
+            }
+            out_first[j + 1] = at;
+        }
+        *n_members = (int) at;
+    }
     u->tail.swap(tail);
     u->late += late;
     *n_out = (int) prim.size();
     return GNUAIS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, int n, long long rows,
+                     gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out)
+{
+    return push_impl(u, frames, times, nullptr, n, rows, out, out_times, out_copies, cap, n_out, nullptr, nullptr, nullptr);
+}
+
+int gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, const gnuais_frame_signal *signal,
+                           int n, long long rows, gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap,
+                           int *n_out, int32_t *out_first, gnuais_hearer *out_members, int *n_members)
+{
+    if (!out_first || !n_members || (n > 0 && !out_members)) return GNUAIS_E_ARG;
+    *n_members = 0;
+    out_first[0] = 0;
+    return push_impl(u, frames, times, signal, n, rows, out, out_times, out_copies, cap, n_out, out_first, out_members,
+                     n_members);
 }
 
 } // extern "C"

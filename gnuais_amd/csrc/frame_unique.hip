@@ -18,6 +18,9 @@
 //             order word, the cluster into the next tail if its last member is within the window of `rows`
 //   deliver   sort of the primaries by the output word (unique per record, so the slot order of the compaction does
 //             not show), gather of records, times and copies: 76 bytes per delivered frame cross PCIe
+//   heard     only where the member lists are wanted (gnuais_batch_drain_frames_heard): scan of the copies in output
+//             order = the lists' offsets, a map from a primary's ring slot to its output position, and per sorted
+//             position the member's 24 bytes into its cluster's list (a cluster's members lie together in the sort)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -257,9 +260,54 @@ __global__ __launch_bounds__(UQ_BLOCK) void uniq_gather_kernel(
     }
 }
 
+// ---- the member lists (gnuais_batch_drain_frames_heard) ----
+// ring slot of a primary -> its position in the output; lane 0 also writes first[0] (the scan fills first[1 ..])
+__global__ __launch_bounds__(UQ_BLOCK) void uniq_slot2q_kernel(
+    int np, const uint32_t *__restrict__ order, const uint32_t *__restrict__ pent, uint32_t *__restrict__ slot2q,
+    uint32_t *__restrict__ first)
+{
+    const int q = blockIdx.x * UQ_BLOCK + threadIdx.x;
+    if (q >= np) return;
+    slot2q[pent[order[q]]] = (uint32_t) q;
+    if (q == 0) first[0] = 0u;
+}
+
+// lane = sorted position j: member j - start of its cluster, into the cluster's list.  A cluster behind a tail entry is
+// late and listed nowhere.  24 bytes per member at 24 * pos: the 16-byte store takes whichever half is 16-aligned.
+__global__ __launch_bounds__(UQ_BLOCK) void uniq_heard_kernel(
+    int n_tail, const uint32_t *__restrict__ frames, const long long *__restrict__ times,
+    const u64 *__restrict__ signal, int m, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ cid,
+    const uint32_t *__restrict__ start, const u64 *__restrict__ prim, const uint32_t *__restrict__ slot2q,
+    const uint32_t *__restrict__ first, u64 *__restrict__ members)
+{
+    const int j = blockIdx.x * UQ_BLOCK + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t c = cid[j] - 1u, s = start[c];
+    if (idx[s] < (uint32_t) n_tail || idx[j] < (uint32_t) n_tail) return;
+    const uint32_t e = idx[j] - (uint32_t) n_tail;                          // this member's ring slot
+    const uint32_t pe = idx[(uint32_t) prim[c]] - (uint32_t) n_tail;        // the primary's
+    const size_t pos = (size_t) first[slot2q[pe]] + ((uint32_t) j - s);
+    const uint32_t *rec = frames + (size_t) e * 16;
+    const uint32_t channel = rec[0], flags = (rec[15] >> 8) & 0xffu;
+    long long t = times[e];
+    if (t < 0) t = -1;
+    const u64 sig = signal ? signal[e] : 0ull;
+    const uint32_t t_lo = (uint32_t) ((u64) t & 0xffffffffull), t_hi = (uint32_t) ((u64) t >> 32);
+    u64 *out = members + 3 * pos;
+    if ((pos & 1) == 0) {
+        *reinterpret_cast<uint4 *>(out) = make_uint4(channel, flags, t_lo, t_hi);
+        out[2] = sig;
+    } else {
+        out[0] = (u64) channel | ((u64) flags << 32);
+        *reinterpret_cast<uint4 *>(out + 1) = make_uint4(t_lo, t_hi, (uint32_t) (sig & 0xffffffffull), (uint32_t) (sig >> 32));
+    }
+}
+
 inline dim3 grid_for(size_t n) { return dim3((unsigned) ((n + UQ_BLOCK - 1) / UQ_BLOCK)); }
 
 } // namespace
+
+size_t unique_heard_scratch_bytes(int have) { return slot(4 * (size_t) (have > 0 ? have : 1)); }
 
 size_t unique_scratch_bytes(int n_entries)
 {
@@ -325,6 +373,24 @@ hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStr
                        static_cast<const uint32_t *>(a.frames), reinterpret_cast<const long long *>(a.times), n_primaries,
                        l.pidx2, l.pent, l.pcopies, reinterpret_cast<uint32_t *>(a.out_frames),
                        reinterpret_cast<long long *>(a.out_times), a.out_copies);
+    if (!a.out_first) return hipGetLastError();
+    // the member lists: first = the running sum of the copies in output order; then every member of a delivered
+    // cluster finds its cluster's list through the primary's ring slot
+    if (!a.out_members || (reinterpret_cast<uintptr_t>(a.out_members) & 15u) || !a.heard_scratch ||
+        a.heard_scratch_bytes < unique_heard_scratch_bytes(a.have))
+        return hipErrorInvalidValue;
+    uint32_t *slot2q = static_cast<uint32_t *>(a.heard_scratch), *first = reinterpret_cast<uint32_t *>(a.out_first);
+    t = l.tmp_bytes;
+    e = rocprim::inclusive_scan(l.tmp, t, reinterpret_cast<const uint32_t *>(a.out_copies), first + 1, (size_t) n_primaries,
+                                rocprim::plus<uint32_t>(), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(uniq_slot2q_kernel, grid_for((size_t) n_primaries), dim3(UQ_BLOCK), 0, s, n_primaries, l.pidx2, l.pent,
+                       slot2q, first);
+    // the sorted index array is idxA in both attempts: one sort into idxB, then one (hashed) or seven (exact) more
+    hipLaunchKernelGGL(uniq_heard_kernel, grid_for((size_t) m), dim3(UQ_BLOCK), 0, s, a.n_tail,
+                       static_cast<const uint32_t *>(a.frames), reinterpret_cast<const long long *>(a.times),
+                       static_cast<const u64 *>(a.signal), m, l.idxA, l.cid, l.start, l.prim, slot2q, first,
+                       reinterpret_cast<u64 *>(a.out_members));
     return hipGetLastError();
 }
 

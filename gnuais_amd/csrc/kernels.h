@@ -307,8 +307,17 @@ struct UniqueLaunch {
     struct gnuais_frame *out_frames;
     int64_t *out_times;
     int32_t *out_copies;
+    // the member lists (gnuais_batch_drain_frames_heard); out_first null: no lists wanted, and the rest is not read.
+    // unique_deliver_enqueue() then also fills out_first[n_primaries + 1] (the running sum of out_copies, from 0) and
+    // out_members[sum of the copies <= have] (16-byte aligned), from the records, times and `signal` by ring slot.
+    const void *signal = nullptr;               // gnuais_frame_signal[have], or null: zeros
+    void *heard_scratch = nullptr;
+    size_t heard_scratch_bytes = 0;             // >= unique_heard_scratch_bytes(have)
+    int32_t *out_first = nullptr;
+    struct gnuais_hearer *out_members = nullptr;
 };
 size_t unique_scratch_bytes(int n_entries);
+size_t unique_heard_scratch_bytes(int have);
 uint32_t *unique_info(void *scratch);
 hipError_t unique_cluster_enqueue(const UniqueLaunch &a, bool exact, hipStream_t s);
 hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStream_t s);

@@ -188,6 +188,7 @@ struct gnuais_node {
     gnuais_uniq *uq = nullptr;
     std::vector<gnuais_frame> uq_frames;
     std::vector<int64_t> uq_times;
+    std::vector<gnuais_frame_signal> uq_signal;     // gnuais_node_drain_frames_heard: the members' records
 };
 
 extern "C" {
@@ -635,11 +636,10 @@ int gnuais_node_unique_late(gnuais_node *nd, long long *late)
     return GNUAIS_OK;
 }
 
-int gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
-                                    int *n_out)
+// h_first: with the clusters' member lists (gnuais_node_drain_frames_heard)
+static int node_drain_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max, int *n_out,
+                             int32_t *h_first, gnuais_hearer *h_members, int *n_members)
 {
-    if (!nd || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
-        return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: argument");
     *n_out = 0;
     if (!nd->uq) return node_fail(GNUAIS_E_STATE, "node_drain_frames_unique: the node does not merge duplicates (gnuais_node_unique)");
     int total = 0;
@@ -648,14 +648,42 @@ int gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_
     nd->uq_frames.resize((size_t) total + 1);
     nd->uq_times.resize((size_t) total + 1);
     int got = 0;
-    const int rc = node_drain(nd, nd->uq_frames.data(), nd->uq_times.data(), total, &got);
+    // the lists carry every copy's signal record: the shards' signal drain where they measure their frames, else zeros
+    bool measured = h_first != nullptr;
+    for (Shard *s : nd->shards) {
+        double on = 0;
+        if (measured && (gnuais_batch_info(s->b, "frame_signal", &on) != GNUAIS_OK || on == 0)) measured = false;
+    }
+    if (measured) nd->uq_signal.resize((size_t) total + 1);
+    const int rc = node_drain(nd, nd->uq_frames.data(), nd->uq_times.data(), total, &got, measured ? nd->uq_signal.data() : nullptr);
     if (rc != GNUAIS_OK && rc != GNUAIS_E_OVERFLOW) return rc;
     double rows = 0;                    // a node's run calls give every shard the same rows
     if (gnuais_batch_info(nd->shards[0]->b, "rows", &rows) != GNUAIS_OK) return node_fail(GNUAIS_E_STATE, "node_drain_frames_unique: rows");
-    if (gnuais_uniq_push(nd->uq, nd->uq_frames.data(), nd->uq_times.data(), got, (long long) rows, h_out, h_times,
-                         h_copies, max, n_out) != GNUAIS_OK)
-        return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: the merge refused its input");
+    const int pushed = h_first ? gnuais_uniq_push_heard(nd->uq, nd->uq_frames.data(), nd->uq_times.data(),
+                                                        measured ? nd->uq_signal.data() : nullptr, got, (long long) rows, h_out,
+                                                        h_times, h_copies, max, n_out, h_first, h_members, n_members)
+                               : gnuais_uniq_push(nd->uq, nd->uq_frames.data(), nd->uq_times.data(), got, (long long) rows, h_out,
+                                                  h_times, h_copies, max, n_out);
+    if (pushed != GNUAIS_OK) return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: the merge refused its input");
     return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
+}
+
+int gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                    int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_frames_unique: argument");
+    return node_drain_unique(nd, h_out, h_times, h_copies, max, n_out, nullptr, nullptr, nullptr);
+}
+
+int gnuais_node_drain_frames_heard(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                   int *n_out, int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    if (!nd || !n_out || !n_members || !h_first || max < 0 || (max > 0 && (!h_out || !h_times || !h_copies || !h_members)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_frames_heard: argument");
+    *n_members = 0;
+    h_first[0] = 0;
+    return node_drain_unique(nd, h_out, h_times, h_copies, max, n_out, h_first, h_members, n_members);
 }
 
 // Streamed sentences of the whole node: gnuais_batch_stream_nmea() on every shard, each from its own thread.  Shard g's

@@ -26,6 +26,9 @@ assert FRAME_DTYPE.itemsize == 64
 # struct gnuais_frame_signal: a frame's power (full scale 2^31), carrier error and blocks measured (0: no measurement)
 SIGNAL_DTYPE = np.dtype([("power", "<u4"), ("ferr", "<i2"), ("blocks", "<u2")])
 assert SIGNAL_DTYPE.itemsize == 8
+# gnuais_hearer: one member of a cluster of gnuais_batch_drain_frames_heard()
+HEARER_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("t", "<i8"), ("signal", SIGNAL_DTYPE)])
+assert HEARER_DTYPE.itemsize == 24
 FRAME_REPAIRED = 0x40         # GNUAIS_FRAME_REPAIRED: frame flags bit 6
 
 # kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
@@ -100,6 +103,8 @@ SYMBOLS = {
     "gnuais_uniq_reset": (_I, [_P]),
     "gnuais_uniq_push": (_I, [_P, _P, _P, _I, C.c_longlong, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_uniq_late": (C.c_longlong, [_P]),
+    "gnuais_batch_drain_frames_heard": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_uniq_push_heard": (_I, [_P, _P, _P, _P, _I, C.c_longlong, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
     "gnuais_batch_counters": (_I, [_P, _P]),
     "gnuais_batch_total_received": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -166,6 +171,7 @@ SYMBOLS = {
     "gnuais_node_unique": (_I, [_P, _I]),
     "gnuais_node_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "gnuais_node_drain_frames_heard": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
     "gnuais_node_stream_nmea": (_I, [_P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_node_discard_frames": (_I, [_P]),
     "gnuais_node_counters": (_I, [_P, _P]),

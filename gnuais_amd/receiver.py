@@ -410,6 +410,23 @@ class ReceiverBatch:
                                                          n, C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy()
 
+    def drain_frames_heard(self):
+        """gnuais_batch_drain_frames_heard(): (frames, int64 times, int32 copies, int32 first, members) -- what
+        drain_frames_unique() delivers, and who heard each transmission: cluster i's members are
+        members[first[i]:first[i + 1]] (lib.HEARER_DTYPE: channel, flags, t, signal) in the order (t, channel)"""
+        n = max(self.pending_frames(), 1)
+        out = np.zeros(n, dtype=FRAME_DTYPE)
+        times = np.zeros(n, dtype=np.int64)
+        copies = np.zeros(n, dtype=np.int32)
+        first = np.zeros(n + 1, dtype=np.int32)
+        members = np.zeros(n, dtype=_lib.HEARER_DTYPE)
+        got, nm = C.c_int(), C.c_int()
+        check(self._lib.gnuais_batch_drain_frames_heard(self._h, out.ctypes.data, times.ctypes.data, copies.ctypes.data,
+                                                        n, C.byref(got), first.ctypes.data, members.ctypes.data,
+                                                        C.byref(nm)))
+        return (out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy(),
+                first[: got.value + 1].copy(), members[: nm.value].copy())
+
     def unique_late(self) -> int:
         """gnuais_batch_unique_late(): copies that arrived after a drain had delivered their transmission"""
         v = C.c_longlong()
@@ -740,3 +757,30 @@ class Uniq:
         if rc != _lib.OK:
             raise _lib.GnuaisError(rc, "gnuais_uniq_push: argument, or more records than cap")
         return out[: got.value].copy(), out_t[: got.value].copy(), out_c[: got.value].copy()
+
+    def push_heard(self, frames: np.ndarray, times: np.ndarray, rows: int, signal: Optional[np.ndarray] = None,
+                   cap: Optional[int] = None):
+        """-> (frames, times, copies, first, members): push() with the clusters' member lists
+        (gnuais_uniq_push_heard); signal: the frames' records (lib.SIGNAL_DTYPE), None for zeros"""
+        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        times = np.ascontiguousarray(times, dtype=np.int64)
+        assert frames.ndim == 1 and times.shape == frames.shape
+        if signal is not None:
+            signal = np.ascontiguousarray(signal, dtype=_lib.SIGNAL_DTYPE)
+            assert signal.shape == frames.shape
+        n = int(frames.size)
+        cap = n if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=FRAME_DTYPE)
+        out_t = np.zeros(max(cap, 1), dtype=np.int64)
+        out_c = np.zeros(max(cap, 1), dtype=np.int32)
+        first = np.zeros(cap + 1, dtype=np.int32)
+        members = np.zeros(max(n, 1), dtype=_lib.HEARER_DTYPE)
+        got, nm = C.c_int(), C.c_int()
+        rc = self._lib.gnuais_uniq_push_heard(self._h, frames.ctypes.data, times.ctypes.data,
+                                              signal.ctypes.data if signal is not None else None, n, int(rows),
+                                              out.ctypes.data, out_t.ctypes.data, out_c.ctypes.data, cap, C.byref(got),
+                                              first.ctypes.data, members.ctypes.data, C.byref(nm))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_uniq_push_heard: argument, or more records than cap")
+        return (out[: got.value].copy(), out_t[: got.value].copy(), out_c[: got.value].copy(),
+                first[: got.value + 1].copy(), members[: nm.value].copy())

@@ -268,6 +268,21 @@ class ReceiverNode:
                                                               copies.ctypes.data, n, self._C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy()
 
+    def drain_frames_heard(self):
+        """gnuais_node_drain_frames_heard(): (frames, int64 times, int32 copies, int32 first, members): the unique drain
+        and, per transmission, the receivers that heard it (lib.HEARER_DTYPE, global channel numbers)"""
+        from .lib import FRAME_DTYPE, HEARER_DTYPE
+        np_ = self._np
+        n = max(self.pending_frames(), 1)
+        out, times, copies = np_.zeros(n, dtype=FRAME_DTYPE), np_.zeros(n, dtype=np_.int64), np_.zeros(n, dtype=np_.int32)
+        first, members = np_.zeros(n + 1, dtype=np_.int32), np_.zeros(n, dtype=HEARER_DTYPE)
+        got, nm = self._C.c_int(), self._C.c_int()
+        self._raise(self._lib.gnuais_node_drain_frames_heard(self._h, out.ctypes.data, times.ctypes.data, copies.ctypes.data,
+                                                             n, self._C.byref(got), first.ctypes.data, members.ctypes.data,
+                                                             self._C.byref(nm)))
+        return (out[: got.value].copy(), times[: got.value].copy(), copies[: got.value].copy(),
+                first[: got.value + 1].copy(), members[: nm.value].copy())
+
     def unique_late(self) -> int:
         t = self._C.c_longlong()
         self._raise(self._lib.gnuais_node_unique_late(self._h, self._C.byref(t)))

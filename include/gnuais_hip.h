@@ -616,6 +616,45 @@ int  gnuais_uniq_push(gnuais_uniq *u, const gnuais_frame *frames, const int64_t 
                       gnuais_frame *out, int64_t *out_times, int32_t *out_copies, int cap, int *n_out);
 long long gnuais_uniq_late(const gnuais_uniq *u);
 
+/* ---- who heard each transmission: the unique drain with its clusters' member lists ----------------------------------
+ * gnuais_batch_drain_frames_heard() is gnuais_batch_drain_frames_unique() with, for every delivered cluster, the list
+ * of its members in CSR form.  Same feature switch (gnuais_batch_unique), same states, same errors, same max rule.
+ *   h_out, h_times, h_copies, *n_out: those of gnuais_batch_drain_frames_unique() for the same state, byte for byte.
+ *   h_first[max + 1]: h_first[0] = 0 and h_first[i + 1] - h_first[i] = h_copies[i].
+ *   h_members[max]: cluster i's members are h_members[h_first[i] .. h_first[i + 1]), in the member order (t, channel)
+ *     of the definition above.  sum(copies) <= pending <= max, so max members always suffice.
+ *   *n_members = h_first[*n_out].
+ *   A member is the copy's receiver (channel), the copy's own gnuais_frame.flags (bit 6: this copy was repaired), its
+ *     receive time and its signal record -- (0, 0, 0) while gnuais_batch_frame_signal is off, and wherever that
+ *     section gives (0, 0, 0).
+ *   An untimed frame is a cluster of one member with t = -1.
+ *   The primary is one of the members: the one whose channel and t are those of h_out[i] and h_times[i].  The primary
+ *     rule does not change; a caller that wants the strongest copy picks it from the list.
+ *   Late copies chain onto a tail entry of an earlier drain; they stay what they are: counted in `late`, listed
+ *     nowhere.  A cluster is listed by the drain that delivers it, with the members that drain saw.
+ *   State: the carried state (tail, `late`) is the one state of the feature; the two drains may be mixed freely from
+ *     drain to drain.  Over any placement of drains of either kind, the listed members plus `late` are the frames
+ *     gnuais_batch_drain_frames_timed() would have delivered.
+ *   No result depends on the order in which frames entered the ring, nor on the hash.
+ *   76 + 4 bytes per delivered record and 24 per member cross PCIe.
+ * gnuais_uniq_push_heard(): gnuais_uniq_push() with the lists; its first three outputs and *n_out equal _push()'s.
+ *   signal[n] are the frames' records, NULL for zeros.  out_first has cap + 1 entries, out_members n (one per pushed
+ *   frame always suffices).  On GNUAIS_E_ARG the object is unchanged.  The device drain equals it bit for bit. */
+typedef struct gnuais_hearer {      /* 24 bytes */
+	uint32_t channel;               /* the copy's receiver */
+	uint32_t flags;                 /* the copy's gnuais_frame.flags (bit 6: this copy was repaired) */
+	int64_t  t;                     /* the copy's receive time, -1 for an untimed frame */
+	gnuais_frame_signal signal;     /* the copy's record; (0,0,0) while gnuais_batch_frame_signal is off */
+} gnuais_hearer;
+int  gnuais_batch_drain_frames_heard(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies,
+                                     int max, int *n_out,
+                                     int32_t *h_first /* [max + 1] */, gnuais_hearer *h_members /* [max] */,
+                                     int *n_members);
+int  gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times,
+                            const gnuais_frame_signal *signal /* NULL: zeros */, int n, long long rows, gnuais_frame *out,
+                            int64_t *out_times, int32_t *out_copies, int cap, int *n_out, int32_t *out_first,
+                            gnuais_hearer *out_members, int *n_members);
+
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
 
@@ -868,6 +907,12 @@ int  gnuais_node_unique(gnuais_node *nd, int window_rows);
 int  gnuais_node_drain_frames_unique(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
                                      int *n_out);
 int  gnuais_node_unique_late(gnuais_node *nd, long long *late);
+/* gnuais_batch_drain_frames_heard()'s definition over the whole node, through the same gnuais_uniq and the same carried
+ * state as gnuais_node_drain_frames_unique(); the two may be mixed.  The host merge is fed by the shards' signal drain,
+ * or by their timed drain with zero records while their gnuais_batch_frame_signal is off.  Channel numbers are global. */
+int  gnuais_node_drain_frames_heard(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
+                                    int *n_out, int32_t *h_first /* [max + 1] */, gnuais_hearer *h_members /* [max] */,
+                                    int *n_members);
 /* gnuais_batch_stream_nmea() on every shard (each from its own thread): texts[g] / lens[g] = shard g's sentences of
  * the call `stream_depth` calls ago (n_devices entries; valid until the next call).  Written out in shard order they
  * are the node's sentences in the reference's order for that call: shard g's channels all lie before shard g+1's and

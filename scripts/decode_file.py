@@ -34,6 +34,13 @@
                                                       # merged on the device (gnuais_batch_unique) and the earliest intact copy
                                                       # is printed.  Implies --times.  --verbose: "copies N" per transmission on
                                                       # stderr; the summary counts copies and late copies
+  ... --unique ROWS --heard
+                                                      # who heard each transmission (gnuais_batch_drain_frames_heard): under
+                                                      # the sentence(s) of every transmission one line "  heard:" on stdout
+                                                      # with, per receiver that decoded a copy, its number, the copy's receive
+                                                      # time in rows after the printed copy's (r = repaired), and -- for --iq /
+                                                      # --wideband input, measured as for --signal -- its power in dBFS and its
+                                                      # carrier error in Hz
   ... --signal
                                                       # --iq / --wideband: how strong every frame was and how far off frequency
                                                       # it arrived, measured on the device over the raw I/Q under the frame
@@ -88,6 +95,9 @@ def main():
     ap.add_argument("--signal", action="store_true",
                     help="--iq / --wideband: every frame's power (dBFS) and carrier error (Hz) on stderr "
                          "(gnuais_batch_frame_signal); implies --times")
+    ap.add_argument("--heard", action="store_true",
+                    help="--unique: under each transmission's sentences one line with the receivers that heard it: number, "
+                         "rows after the printed copy, dBFS and Hz (--iq / --wideband)")
     ap.add_argument("--verbose", action="store_true", help="--unique: the copies of every printed transmission, on stderr")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
@@ -95,8 +105,11 @@ def main():
         sys.exit("--unique takes a window in rows, > 0")
     if a.signal and not (a.iq or a.wideband):
         sys.exit("--signal needs --iq or --wideband: it measures the I/Q under a frame, audio input has none")
+    if a.heard and not a.unique:
+        sys.exit("--heard lists the receivers of a merged transmission: it needs --unique ROWS")
     if a.signal and a.unique:
-        sys.exit("--signal is not for --unique: the merged drain carries no signal records")
+        sys.exit("--signal is not for --unique: --unique ROWS --heard lists every copy's power and carrier error")
+    a.measure = a.signal or (a.heard and bool(a.iq or a.wideband))
     a.times = a.times or a.unique > 0 or a.signal
     if a.times and a.text:
         sys.exit("--times tags NMEA sentences: not with --text")
@@ -132,7 +145,7 @@ def main():
         b.frame_times(True)
     if a.repair:
         b.repair(True)
-    if a.signal:
+    if a.measure:
         b.frame_signal(True)
     if a.unique:
         b.unique(a.unique)
@@ -153,6 +166,8 @@ def main():
 def write_sentences(a, b, seq, kind, rate):
     """what the batch has decoded since the last call, to stdout; rate: of the input samples (--times)"""
     from gnuais_amd import messages_from_frames, nmea_tagged_from_frames
+    if a.unique and a.heard:
+        return write_heard(a, b, seq, kind, rate)
     if a.unique:
         frames, times, copies = b.drain_frames_unique()
         a.unique_records = getattr(a, "unique_records", 0) + len(frames)
@@ -184,6 +199,30 @@ def write_sentences(a, b, seq, kind, rate):
             (int(f["channel"]), int(f["end_bit"]) | ((int(f["flags"]) >> 1 & 31) << 32), int(f["nbits"]))
             for f in frames[(frames["flags"] & FRAME_REPAIRED) != 0]]
     sys.stdout.write(out.decode("ascii", "replace"))
+
+
+def write_heard(a, b, seq, kind, rate):
+    """--unique --heard: every transmission's sentences, and under them the receivers that heard it"""
+    from gnuais_amd import nmea_tagged_from_frames
+    from gnuais_amd.lib import FRAME_REPAIRED, signal_dbfs, signal_hz
+    frames, times, copies, first, members = b.drain_frames_heard()
+    a.unique_records = getattr(a, "unique_records", 0) + len(frames)
+    a.unique_copies = getattr(a, "unique_copies", 0) + int(copies.sum())
+    num, den, off = b.time_map_ratio(kind)
+    for i in range(len(frames)):
+        out = nmea_tagged_from_frames(frames[i:i + 1], times[i:i + 1], seq, num, off, rate * den, a.start)
+        sys.stdout.write(out.decode("ascii", "replace"))
+        who = []
+        for m in members[first[i]:first[i + 1]]:
+            txt = f"{int(m['channel'])} {int(m['t']) - int(times[i]):+d}" + ("r" if int(m["flags"]) & FRAME_REPAIRED else "")
+            if m["signal"]["blocks"]:                       # ferr is counted in the chain's rows
+                txt += f" {signal_dbfs(m['signal']['power']):.1f}dBFS {signal_hz(m['signal']['ferr'], CHAIN_RATE):+.0f}Hz"
+            who.append(txt)
+        sys.stdout.write("  heard: " + ", ".join(who) + "\n")
+    if a.repair:
+        a.repaired_frames = getattr(a, "repaired_frames", []) + [
+            (int(f["channel"]), int(f["end_bit"]) | ((int(f["flags"]) >> 1 & 31) << 32), int(f["nbits"]))
+            for f in frames[(frames["flags"] & FRAME_REPAIRED) != 0]]
 
 
 def afc_flush(x, rows, fmt=None):
@@ -245,7 +284,7 @@ def decode_wideband(a, rate, x, fmt=None):
         b.frame_times(True)
     if a.repair:
         b.repair(True)
-    if a.signal:
+    if a.measure:
         b.frame_signal(True)
     if a.unique:
         b.unique(a.unique)
