@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ("ReceiverBatch", "crc16_batch", "tile_channels", "nmea_from_frames", "nmea_tagged_from_frames", "messages_from_frames", "range_from_frames", "vessels_from_frames", "VESSEL_DTYPE", "Uniq"):
         from . import receiver
         return getattr(receiver, name)
-    if name in ("signal_dbfs", "signal_hz", "frame_signal_span", "SIGNAL_DTYPE", "HEARER_DTYPE"):
+    if name in ("signal_dbfs", "signal_hz", "frame_signal_span", "SIGNAL_DTYPE", "HEARER_DTYPE",
+                "OCCUPANCY_DTYPE", "occupancy_code", "occupancy_power", "occupancy_cover_span", "floor_dbfs", "snr_db"):
         from . import lib
         return getattr(lib, name)
     if name == "ReceiverNode":

@@ -213,6 +213,20 @@ struct gnuais_batch {
     Buf<int64_t> fs_ring;                       // [fs_RB][N][3] (P, R, I), block j of n in slot j % fs_RB
     Buf<uint32_t> fs_carry;                     // [N] the stage's own previous pair
     Buf<gnuais_frame_signal> signal;            // [frame_cap], parallel to times
+    // The channel load per receiver (gnuais_batch_occupancy, occupancy.hip; occ_E = 0: off; needs frame_signal).  While it
+    // is on, every I/Q-type call launches the code kernel behind its ingest kernel and the cover kernel behind its
+    // frame_signal launch, and the call that makes an epoch final launches the finaliser behind that.  occ_v0: the first
+    // row of the run the epochs are counted in (fs_v0, or the row the feature was switched on at when that is later);
+    // occ_next: the run's epochs that are final; occ_seq: final epochs since switch-on / reset, epoch s in slot s % 64 of
+    // occ_out with its first block in occ_first; occ_drained: the next one a drain delivers.
+    int occ_E = 0, occ_margin = 0, occ_CB = 0, occ_nbuf = 0, occ_W = 0;     // occ_nbuf, occ_W: the depth and the AFC window the rings are sized for
+    bool occ_cover_clean = false;               // the cover ring is all zero: the start of a run has nothing to clear
+    unsigned long long occ_v0 = 0, occ_seq = 0, occ_drained = 0;
+    long long occ_next = 0, occ_lost = 0;
+    long long occ_first[64] = {};
+    Buf<uint16_t> occ_codes;                    // [occ_CB][N], block j of n in slot j % occ_CB
+    Buf<uint8_t> occ_cover, occ_carry;          // [occ_CB][N]; [N] the busy bit of the last final epoch's last block
+    Buf<gnuais_occupancy> occ_out;              // [64][N]
     // The repair of CRC-failed candidates (gnuais_batch_repair, hdlc_repair.hip; off by default): while it is on, one
     // more launch behind each K3 -- in front of the frame_time launch -- appends the repaired frames to ring 0 (a batch
     // with the feature on does not stream) and counts them per channel.
@@ -326,4 +340,9 @@ double now_ms();
 // capi_ingest.hip: the carries of the stages in front of the chain, for gnuais_batch_reset
 int chan_zero_state(gnuais_batch *b);
 int afc_zero_state(gnuais_batch *b);
+// capi_ingest.hip: gnuais_batch_occupancy's part of a reset (the device is idle), and of the tail of an I/Q-type call of
+// len rows from row b->rows on, behind its frame_signal launch on stream s: the cover launch and the finalisers of the
+// epochs that call makes final
+int occ_zero_state(gnuais_batch *b);
+int occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s);
 }

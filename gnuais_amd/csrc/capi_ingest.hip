@@ -3,6 +3,7 @@
 // host memory and hand the audio to gnuais_batch_run (gnuais_capi.hip).  Host code only.
 #include "batch.h"
 #include "frame_signal.h"
+#include "occupancy.h"
 #include "resample_plan.h"
 #include "wide_format.h"
 
@@ -70,6 +71,61 @@ int gnuais::afc_zero_state(gnuais_batch *b)
     return GNUAIS_OK;
 }
 
+// gnuais_batch_occupancy: the run starts anew at the current row, no epoch is final, the queue is empty (size kept)
+int gnuais::occ_zero_state(gnuais_batch *b)
+{
+    if (b->occ_E && !b->occ_cover_clean)
+        HIP_TRY(hipMemset(b->occ_cover, 0, (size_t) b->occ_CB * (size_t) b->N));
+    b->occ_cover_clean = true;
+    b->occ_v0 = b->rows;
+    b->occ_next = 0;
+    b->occ_seq = b->occ_drained = 0;
+    b->occ_lost = 0;
+    return GNUAIS_OK;
+}
+
+// the first whole block of the run the epochs are counted in
+static long long occ_b0(const gnuais_batch *b) { return (long long) ((b->occ_v0 + FS_BLOCK - 1) / FS_BLOCK); }
+
+int gnuais::occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s)
+{
+    const size_t N = (size_t) b->N;
+    const long long n0 = (long long) b->rows, b0 = occ_b0(b);
+    // The first call of a run: whatever the run before it left in the cover ring goes, behind that run's last tail in
+    // this stream's order.  (The code ring needs nothing: every block of an epoch is coded before the epoch is final.)
+    if (b->rows == b->occ_v0 && !b->occ_cover_clean)
+        HIP_TRY(hipMemsetAsync(b->occ_cover, 0, (size_t) b->occ_CB * N, s));
+    b->occ_cover_clean = false;
+    OccCoverLaunch c;
+    c.frames = h.frames; c.frame_count = h.frame_count; c.frame_cap = h.frame_cap;
+    c.times = b->times; c.cover = b->occ_cover;
+    c.CB = b->occ_CB; c.N = b->N;
+    c.len = len; c.n0 = n0;
+    c.pllinc = b->pllinc; c.n_taps = b->NT; c.afc_window = b->afc_W;
+    c.v0 = (int64_t) b->occ_v0; c.b0 = b0;
+    HIP_TRY(launch_occ_cover(c, s));
+    // The epochs this call makes final: the host knows them from n0, len and v0 alone
+    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W), E = b->occ_E;
+    while (n0 + len > FS_BLOCK * (b0 + (b->occ_next + 1) * E) - 1 + lag) {
+        const int slot = (int) (b->occ_seq % OCC_RING_EPOCHS);
+        OccEpochLaunch e;
+        e.codes = b->occ_codes; e.cover = b->occ_cover; e.carry = b->occ_carry;
+        e.out = b->occ_out.p + (size_t) slot * N;
+        e.CB = b->occ_CB; e.N = b->N; e.E = b->occ_E; e.margin = b->occ_margin;
+        e.first = b0 + b->occ_next * E;
+        e.first_epoch = b->occ_next == 0;
+        HIP_TRY(launch_occ_epoch(e, s));
+        if (b->occ_seq - b->occ_drained == OCC_RING_EPOCHS) {       // the slot's epoch was never drained
+            b->occ_drained++;
+            b->occ_lost++;
+        }
+        b->occ_first[slot] = e.first;
+        b->occ_seq++;
+        b->occ_next++;
+    }
+    return GNUAIS_OK;
+}
+
 extern "C" {
 
 // ---- complex baseband in (include/gnuais_hip.h): the discriminator (iq_disc.hip) in front of the unchanged chain ----
@@ -101,6 +157,9 @@ int gnuais_batch_afc(gnuais_batch *b, int window)
     if (!b) return fail(GNUAIS_E_ARG, "afc: NULL batch");
     if (window && (window < AFC_MIN_WINDOW || window > AFC_MAX_WINDOW || window % (2 * AFC_BLOCK)))
         return fail(GNUAIS_E_ARG, "afc: the window must be 0 (off) or a multiple of 128 from 128 to 16384");
+    if (b->occ_E && window > b->occ_W)
+        return fail(GNUAIS_E_STATE, "afc: the rings of gnuais_batch_occupancy are sized for the window it was switched on at; "
+                                    "switch it off first");
     if (int rc = set_device(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(b->afc_blk.release());
@@ -482,6 +541,16 @@ static int power_launch(gnuais_batch *b, const int16_t *d_iq, int len, hipStream
     if (b->rows != b->fs_end) b->fs_v0 = b->rows;        // an audio-type call came between: a new run starts here
     HIP_TRY(launch_iq_power(d_iq, b->fs_carry, b->fs_ring, b->fs_RB, b->N, len, b->rows, b->rows == b->fs_v0, s));
     b->fs_end = b->rows + (unsigned long long) len;      // a run call that fails leaves rows behind it: a new run next time
+    if (b->occ_E) {
+        // gnuais_batch_occupancy: a new run drops the epochs of the last one that are not final and counts from its own
+        // first whole block; then the codes of the blocks this call completed, on the same stream behind their sums
+        if (b->rows == b->fs_v0) {
+            b->occ_v0 = b->rows;
+            b->occ_next = 0;
+        }
+        const long long j0 = std::max(occ_b0(b), (long long) (b->rows / FS_BLOCK)), j1 = (long long) (b->fs_end / FS_BLOCK);
+        if (j1 > j0) HIP_TRY(launch_occ_code(b->fs_ring, b->fs_RB, b->occ_codes, b->occ_CB, b->N, j0, (int) (j1 - j0), s));
+    }
     return GNUAIS_OK;
 }
 
@@ -495,6 +564,9 @@ int gnuais_batch_frame_signal(gnuais_batch *b, int on)
     if (on && !b->frame_times)
         return fail(GNUAIS_E_STATE, "frame_signal: the batch does not time its frames (gnuais_batch_frame_times): a frame's "
                                     "span is found by its receive time");
+    if (!on && b->occ_E)
+        return fail(GNUAIS_E_STATE, "frame_signal: the batch codes the block sums of this ring (gnuais_batch_occupancy); "
+                                    "gnuais_batch_occupancy(b, 0, 0) first");
     if (int rc = gnuais_batch_sync(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->frame_signal = false;
@@ -546,6 +618,105 @@ int gnuais_batch_signal_blocks(gnuais_batch *b, long long j0, int count, int64_t
     const size_t blk = 3 * (size_t) b->N;
     for (int k = 0; k < count; ++k)
         HIP_TRY(hipMemcpy(h_out + (size_t) k * blk, b->fs_ring + (size_t) ((j0 + k) % b->fs_RB) * blk, sizeof(int64_t) * blk,
+                          hipMemcpyDeviceToHost));
+    return GNUAIS_OK;
+}
+
+// ---- the channel load per receiver (include/gnuais_hip.h, occupancy.hip) ----
+
+// Synchronises: no call is in flight when the switch turns.  The run the epochs are counted in starts at the current row.
+int gnuais_batch_occupancy(gnuais_batch *b, int epoch_blocks, int margin)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "occupancy: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "occupancy: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (epoch_blocks && !b->frame_signal)
+        return fail(GNUAIS_E_STATE, "occupancy: the batch keeps no block sums (gnuais_batch_frame_signal): a block's code is "
+                                    "the code of its sum");
+    if (epoch_blocks && (epoch_blocks < OCC_MIN_EPOCH || epoch_blocks > OCC_MAX_EPOCH || margin < 1 || margin > 255))
+        return fail(GNUAIS_E_ARG, "occupancy: epoch_blocks must be 0 (off) or 64..4096, margin 1..255");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    b->occ_E = 0;
+    HIP_TRY(b->occ_codes.release());
+    HIP_TRY(b->occ_cover.release());
+    if (!epoch_blocks) return GNUAIS_OK;
+    // The rings' size.  No slot may be written while a finaliser that can still read it is pending.  The finaliser of
+    // the epoch of the blocks [f, f + E) is queued in the tail of the first call c whose rows end behind row
+    // 64 (f + E) - 1 + LAG, so that call begins at or before that row: n0_c <= 64 (f + E) - 1 + LAG.  As for the signal
+    // ring (gnuais_batch_frame_signal above), while the tail of call c is pending the ingest side of up to call c + nbuf
+    // may run, and its code launches write blocks whose rows lie below n0_c + (nbuf + 1) * max_len; the cover launch of
+    // call c itself stores up to row n0_c + len + S_post.  All of them are blocks below
+    // f + E + ceil(LAG / 64) + (nbuf + 1) * ceil(max_len / 64) + 1, and the finaliser reads and writes from block f on.
+    // nbuf + 2 calls instead of nbuf + 1 leave one call of slack, one block more for the open one.  LAG is that of the
+    // AFC window in use; gnuais_batch_afc refuses a wider one while the feature is on.  With the pipeline off every
+    // launch is in one stream's order, as there.
+    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W);
+    const long long CB = epoch_blocks + fs_ceil_div(lag, FS_BLOCK) + (long long) (b->nbuf + 2) * fs_ceil_div(b->max_len, FS_BLOCK) + 2;
+    if (CB > 0x7fffffff) return fail(GNUAIS_E_STATE, "occupancy: the batch's pllinc gives frames of more than 2^31 blocks");
+    const size_t N = (size_t) b->N;
+    if (int rc = alloc_checked(b, b->occ_codes, sizeof(uint16_t) * N * (size_t) CB, "occupancy", "the ring of block codes"))
+        return rc;
+    if (int rc = alloc_checked(b, b->occ_cover, N * (size_t) CB, "occupancy", "the ring of cover bytes")) return rc;
+    HIP_TRY(hipMemset(b->occ_cover, 0, N * (size_t) CB));
+    HIP_TRY(b->occ_carry.ensure(N));
+    HIP_TRY(hipMemset(b->occ_carry, 0, N));
+    HIP_TRY(b->occ_out.ensure(sizeof(gnuais_occupancy) * N * OCC_RING_EPOCHS));
+    b->occ_CB = (int) CB;
+    b->occ_nbuf = b->nbuf;
+    b->occ_W = b->afc_W;
+    b->occ_margin = margin;
+    b->occ_cover_clean = true;
+    b->occ_E = epoch_blocks;
+    return occ_zero_state(b);
+}
+
+// the final epochs in order: h_out [max][N], h_first_block [max]
+int gnuais_batch_drain_occupancy(gnuais_batch *b, gnuais_occupancy *h_out, int64_t *h_first_block, int max, int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max > 0 && (!h_out || !h_first_block))) return fail(GNUAIS_E_ARG, "drain_occupancy: argument");
+    *n_out = 0;
+    if (!b->occ_E) return fail(GNUAIS_E_STATE, "drain_occupancy: the batch does not measure its channels' load (gnuais_batch_occupancy)");
+    if (int rc = set_device(b)) return rc;
+    if (b->occ_drained == b->occ_seq || max == 0) return GNUAIS_OK;
+    if (int rc = gnuais_batch_sync(b)) return rc;              // the tails that produced them
+    const size_t N = (size_t) b->N;
+    int n = 0;
+    for (; n < max && b->occ_drained < b->occ_seq; ++n, ++b->occ_drained) {
+        const int slot = (int) (b->occ_drained % OCC_RING_EPOCHS);
+        HIP_TRY(hipMemcpy(h_out + (size_t) n * N, b->occ_out.p + (size_t) slot * N, sizeof(gnuais_occupancy) * N, hipMemcpyDeviceToHost));
+        h_first_block[n] = b->occ_first[slot];
+    }
+    *n_out = n;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_occupancy_lost(gnuais_batch *b, long long *lost)
+{
+    if (!b || !lost) return fail(GNUAIS_E_ARG, "occupancy_lost: argument");
+    *lost = b->occ_lost;
+    return GNUAIS_OK;
+}
+
+// the tap: the words code | busy << 14 | cover << 15 of the blocks [j0, j0 + count), h_out [count][N]
+int gnuais_batch_occupancy_blocks(gnuais_batch *b, long long j0, int count, uint16_t *h_out)
+{
+    if (!b || count < 0 || (count > 0 && !h_out)) return fail(GNUAIS_E_ARG, "occupancy_blocks: argument");
+    if (!b->occ_E) return fail(GNUAIS_E_STATE, "occupancy_blocks: the batch does not measure its channels' load (gnuais_batch_occupancy)");
+    if (int rc = set_device(b)) return rc;
+    // what the ring holds of final epochs: those of the current run that the codes of later blocks have not replaced
+    const long long end = occ_b0(b) + b->occ_next * b->occ_E;
+    const long long lo = std::max(occ_b0(b), (long long) (b->fs_end / FS_BLOCK) - b->occ_CB);
+    if (j0 < lo || j0 + count > end) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "occupancy_blocks: blocks [%lld, %lld) asked for, the ring holds the final blocks [%lld, %lld)",
+                 j0, j0 + count, lo, std::max(lo, end));
+        return fail(GNUAIS_E_ARG, msg);
+    }
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    const size_t N = (size_t) b->N;
+    for (int k = 0; k < count; ++k)
+        HIP_TRY(hipMemcpy(h_out + (size_t) k * N, b->occ_codes + (size_t) ((j0 + k) % b->occ_CB) * N, sizeof(uint16_t) * N,
                           hipMemcpyDeviceToHost));
     return GNUAIS_OK;
 }

@@ -335,6 +335,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->calls = 0;
     b->rows = 0;
     b->fs_v0 = b->fs_end = 0;                   // gnuais_batch_frame_signal: a new run of I/Q-type calls starts at row 0
+    if (int rc = occ_zero_state(b)) return rc;  // gnuais_batch_occupancy: and its epochs count from there, the queue is empty
     b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
@@ -373,6 +374,9 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         if (b->frame_signal && value > b->fs_nbuf)
             return fail(GNUAIS_E_STATE, "nbuf: the block ring of gnuais_batch_frame_signal is sized for the depth it was switched on "
                                         "at; switch it off first");
+        if (b->occ_E && value > b->occ_nbuf)
+            return fail(GNUAIS_E_STATE, "nbuf: the rings of gnuais_batch_occupancy are sized for the depth it was switched on at; "
+                                        "switch it off first");
         if (int rc = gnuais_batch_sync(b)) return rc;
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(alloc_sets(b, value));
@@ -601,6 +605,10 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     if (b->frame_times && (b->stage_mask & 16)) HIP_TRY(launch_frame_times(fill_frame_times(b, h, len), sD));
     // their power and carrier error: behind the times it selects its records by, in front of e_done[4][k] (frame_signal.hip)
     if (b->frame_signal && (b->stage_mask & 16)) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, len), sD));
+    // the channels' load: the cover of this call's frames behind their times, then the epochs the call makes final, in
+    // front of e_done[4][k] (occupancy.hip; only a call that came through run_form has I/Q rows)
+    if (b->occ_E && b->fs_iq_call && (b->stage_mask & 16))
+        if (int rc = occ_tail(b, h, len, sD)) return rc;
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -1036,6 +1044,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "segments")) *value = b->n_seg;
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
     else if (!strcmp(name, "frame_signal")) *value = b->frame_signal;
+    else if (!strcmp(name, "occupancy")) *value = b->occ_E;
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
     else if (!strcmp(name, "pll_form")) *value = b->pll_form;
     else if (!strcmp(name, "repair")) *value = b->repair;

@@ -155,6 +155,42 @@ struct FrameSignalLaunch {
 };
 hipError_t launch_frame_signal(const FrameSignalLaunch &a, hipStream_t stream);
 
+// ---- the channel load per receiver (occupancy.hip; definition in include/gnuais_hip.h) ----
+// launch_occ_code: behind launch_iq_power of the same call, on its stream.  codes[(j % CB) * N + c] = code(P_j) for the
+// blocks j in [j0, j0 + count), which that call completed; sums is launch_iq_power's ring.  count <= RB and <= CB.
+hipError_t launch_occ_code(const int64_t *sums, int RB, uint16_t *codes, int CB, int N, long long j0, int count,
+                           hipStream_t stream);
+// launch_occ_cover: behind the frame_signal launch of the same call, on its stream.  cover[(j % CB) * N + c] = 1 for the
+// blocks j >= b0 of the cover span of every record with n0 <= times[i] < n0 + len.
+struct OccCoverLaunch {
+    const void *frames;            // gnuais_frame[frame_cap]: the ring K3 appended to
+    const uint32_t *frame_count;
+    uint32_t frame_cap;
+    const int64_t *times;          // [frame_cap], by ring slot
+    uint8_t *cover;                // [CB][N]
+    int CB, N;
+    int len;
+    int64_t n0;
+    uint32_t pllinc;
+    int n_taps, afc_window;
+    int64_t v0, b0;                // the run's first row and its first whole block
+};
+hipError_t launch_occ_cover(const OccCoverLaunch &a, hipStream_t stream);
+// launch_occ_epoch: the finaliser of the epoch of E blocks from block `first` on, behind the cover launch of the call that
+// made it final.  Writes the record of every channel to out[N], the tap word (code | busy << 14 | cover << 15) back into
+// codes, the busy bit of the epoch's last block to carry[N] (read as the bit in front of the epoch unless first_epoch),
+// and clears the epoch's cover bytes.  64 <= E <= 4096 < CB, 1 <= margin <= 255.
+struct OccEpochLaunch {
+    uint16_t *codes;               // [CB][N]
+    uint8_t *cover;                // [CB][N]
+    uint8_t *carry;                // [N]
+    void *out;                     // gnuais_occupancy[N]
+    int CB, N, E, margin;
+    int64_t first;
+    bool first_epoch;
+};
+hipError_t launch_occ_epoch(const OccEpochLaunch &a, hipStream_t stream);
+
 // ---- utilities (util.hip) ---------------------------------------------------
 hipError_t launch_tile_channels(const int16_t *base, int n_base, int len, int16_t *out,
                                 int n_channels, hipStream_t stream);

@@ -532,6 +532,42 @@ int gnuais_node_frame_signal(gnuais_node *nd, int on)
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_frame_signal(s.b, on); });
 }
 
+int gnuais_node_occupancy(gnuais_node *nd, int epoch_blocks, int margin)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_occupancy: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_occupancy(s.b, epoch_blocks, margin); });
+}
+
+// every shard's final epochs into a buffer of its own, then laid side by side by global channel: the shards took the same
+// rows, so they made the same epochs final
+int gnuais_node_drain_occupancy(gnuais_node *nd, gnuais_occupancy *h_out, int64_t *h_first_block, int max, int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max > 0 && (!h_out || !h_first_block)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_occupancy: argument");
+    *n_out = 0;
+    std::vector<Shard *> &sh = nd->shards;
+    std::vector<std::vector<gnuais_occupancy>> rec(sh.size());
+    std::vector<std::vector<int64_t>> first(sh.size());
+    std::vector<int> cnt(sh.size(), 0);
+    const int rc = run_all(nd, [&](Shard &s, size_t i) {
+        rec[i].resize((size_t) std::max(max, 1) * (size_t) s.n);
+        first[i].resize((size_t) std::max(max, 1));
+        return gnuais_batch_drain_occupancy(s.b, rec[i].data(), first[i].data(), max, &cnt[i]);
+    });
+    if (rc) return rc;
+    for (size_t i = 1; i < sh.size(); ++i)
+        if (cnt[i] != cnt[0] || !std::equal(first[i].begin(), first[i].begin() + cnt[i], first[0].begin()))
+            return node_fail(GNUAIS_E_STATE, "node_drain_occupancy: the shards' epochs do not align");
+    for (int k = 0; k < cnt[0]; ++k) {
+        h_first_block[k] = first[0][(size_t) k];
+        for (size_t i = 0; i < sh.size(); ++i)
+            memcpy(h_out + (size_t) k * (size_t) nd->N + (size_t) sh[i]->first, rec[i].data() + (size_t) k * (size_t) sh[i]->n,
+                   sizeof(gnuais_occupancy) * (size_t) sh[i]->n);
+    }
+    *n_out = cnt[0];
+    return GNUAIS_OK;
+}
+
 int gnuais_node_repair(gnuais_node *nd, int on)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_repair: NULL node");

@@ -29,7 +29,11 @@ assert SIGNAL_DTYPE.itemsize == 8
 # gnuais_hearer: one member of a cluster of gnuais_batch_drain_frames_heard()
 HEARER_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("t", "<i8"), ("signal", SIGNAL_DTYPE)])
 assert HEARER_DTYPE.itemsize == 24
-FRAME_REPAIRED = 0x40         # GNUAIS_FRAME_REPAIRED: frame flags bit 6
+# struct gnuais_occupancy: a channel's epoch: the floor's code, busy and covered blocks, bursts
+OCCUPANCY_DTYPE = np.dtype([("floor", "<u2"), ("busy", "<u2"), ("covered", "<u2"), ("bursts", "<u2")])
+assert OCCUPANCY_DTYPE.itemsize == 8
+OCCUPANCY_EPOCHS_HELD = 64    # final epochs the library keeps for gnuais_batch_drain_occupancy
+FRAME_REPAIRED = 0x40        # GNUAIS_FRAME_REPAIRED: frame flags bit 6
 
 # kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
 INPUT_KINDS = {"audio": 0, "iq": 1, "wideband": 2}
@@ -88,6 +92,13 @@ SYMBOLS = {
     "gnuais_batch_drain_frames_signal": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_signal_blocks": (_I, [_P, C.c_longlong, _I, _P]),
     "gnuais_frame_signal_span": (_I, [C.c_longlong, _I, _U, _I, _I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_I)]),
+    "gnuais_batch_occupancy": (_I, [_P, _I, _I]),
+    "gnuais_batch_drain_occupancy": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_occupancy_lost": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "gnuais_batch_occupancy_blocks": (_I, [_P, C.c_longlong, _I, _P]),
+    "gnuais_occupancy_code": (_I, [C.c_longlong, C.POINTER(_I)]),
+    "gnuais_occupancy_power": (_I, [_I, C.POINTER(C.c_longlong)]),
+    "gnuais_occupancy_cover_span": (_I, [C.c_longlong, _I, _U, _I, _I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_I)]),
     "gnuais_batch_time_map": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_batch_time_map_ratio": (_I, [_P, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "gnuais_nmea_tagged_from_frames": (_I, [_P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
@@ -166,6 +177,8 @@ SYMBOLS = {
     "gnuais_node_drain_frames_timed": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_frame_signal": (_I, [_P, _I]),
     "gnuais_node_drain_frames_signal": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_occupancy": (_I, [_P, _I, _I]),
+    "gnuais_node_drain_occupancy": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_repair": (_I, [_P, _I]),
     "gnuais_node_repaired": (_I, [_P, _P]),
     "gnuais_node_unique": (_I, [_P, _I]),
@@ -238,6 +251,45 @@ def frame_signal_span(t: int, nbits: int, pllinc: int, n_taps: int = 36, afc_win
     check(load().gnuais_frame_signal_span(int(t), int(nbits), int(pllinc), int(n_taps), int(afc_window), int(v0),
                                           C.byref(j_lo), C.byref(nb)))
     return j_lo.value, nb.value
+
+
+def occupancy_code(P: int) -> int:
+    """gnuais_occupancy_code(): the code of a block's sum P (eight steps per octave), 0 <= P < 2^38"""
+    code = C.c_int(0)
+    check(load().gnuais_occupancy_code(int(P), C.byref(code)))
+    return code.value
+
+
+def occupancy_power(code: int) -> int:
+    """gnuais_occupancy_power(): the lower edge of a code's bin, a block's sum"""
+    P = C.c_longlong(0)
+    check(load().gnuais_occupancy_power(int(code), C.byref(P)))
+    return P.value
+
+
+def occupancy_cover_span(t: int, nbits: int, pllinc: int, n_taps: int = 36, afc_window: int = 0, v0: int = 0):
+    """gnuais_occupancy_cover_span(): (j_lo, nb), the blocks of 64 rows a frame's cover span intersects; (0, 0): none"""
+    j_lo, nb = C.c_longlong(0), C.c_int(0)
+    check(load().gnuais_occupancy_cover_span(int(t), int(nbits), int(pllinc), int(n_taps), int(afc_window), int(v0),
+                                             C.byref(j_lo), C.byref(nb)))
+    return j_lo.value, nb.value
+
+
+def _bin_edge(code) -> np.ndarray:
+    """power(code) of the definition on an array of codes, as float64"""
+    c = np.asarray(code, dtype=np.int64)
+    return np.where(c < 8, c, (8 + (c & 7)) * 2.0 ** (np.maximum(c, 8) // 8 - 1)).astype(np.float64)
+
+
+def floor_dbfs(code) -> np.ndarray:
+    """gnuais_occupancy.floor -> dB relative to full scale: 10 log10(power(code) / 64 / 2^31); -inf for code 0"""
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(_bin_edge(code) / 64.0 / 2.0 ** 31)
+
+
+def snr_db(power, floor_code) -> np.ndarray:
+    """a frame record's power (gnuais_frame_signal.power) against its epoch's floor (gnuais_occupancy.floor), in dB"""
+    return signal_dbfs(power) - floor_dbfs(floor_code)
 
 
 def default_taps() -> np.ndarray:

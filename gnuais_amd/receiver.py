@@ -392,6 +392,36 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_signal_blocks(self._h, int(j0), int(count), out.ctypes.data))
         return out
 
+    def occupancy(self, epoch_blocks: int = 1024, margin: int = 16):
+        """gnuais_batch_occupancy(): from now on every channel gets, per epoch of epoch_blocks blocks of 64 rows of I/Q
+        input, its noise floor, busy and covered blocks and bursts (the definition is in include/gnuais_hip.h); margin in
+        code steps of 0.376 dB above the floor (16: 6.02 dB).  epoch_blocks = 0: off.  Needs frame_signal().
+        Synchronises.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_occupancy(self._h, int(epoch_blocks), int(margin)))
+
+    def drain_occupancy(self):
+        """gnuais_batch_drain_occupancy(): (int64 first_block[n], records[n][n_channels]) of the final epochs not
+        delivered yet, oldest first; records a structured array (lib.OCCUPANCY_DTYPE)"""
+        n = _lib.OCCUPANCY_EPOCHS_HELD
+        rec = np.zeros((n, self.n_channels), dtype=_lib.OCCUPANCY_DTYPE)
+        first = np.zeros(n, dtype=np.int64)
+        got = C.c_int()
+        check(self._lib.gnuais_batch_drain_occupancy(self._h, rec.ctypes.data, first.ctypes.data, n, C.byref(got)))
+        return first[: got.value].copy(), rec[: got.value].copy()
+
+    def occupancy_lost(self) -> int:
+        """gnuais_batch_occupancy_lost(): final epochs overwritten before a drain took them"""
+        lost = C.c_longlong()
+        check(self._lib.gnuais_batch_occupancy_lost(self._h, C.byref(lost)))
+        return lost.value
+
+    def occupancy_blocks(self, j0: int, count: int) -> np.ndarray:
+        """gnuais_batch_occupancy_blocks(): uint16 [count][n_channels], code | busy << 14 | cover << 15 of the blocks
+        [j0, j0 + count) of final epochs (a tap, and the occupancy map)"""
+        out = np.zeros((max(count, 0), self.n_channels), dtype=np.uint16)
+        check(self._lib.gnuais_batch_occupancy_blocks(self._h, int(j0), int(count), out.ctypes.data))
+        return out
+
     def unique(self, window: int):
         """gnuais_batch_unique(): window > 0 rows: drain_frames_unique() delivers each transmission once (equal frames
         whose receive times chain within the window; the definition is in include/gnuais_hip.h); 0: off.  Needs

@@ -252,6 +252,20 @@ class ReceiverNode:
                                                               n, self._C.byref(got)))
         return out[: got.value].copy(), times[: got.value].copy(), sig[: got.value].copy()
 
+    def occupancy(self, epoch_blocks: int = 1024, margin: int = 16):
+        """gnuais_batch_occupancy() on every shard"""
+        self._raise(self._lib.gnuais_node_occupancy(self._h, int(epoch_blocks), int(margin)))
+
+    def drain_occupancy(self):
+        """gnuais_node_drain_occupancy(): (int64 first_block[n], records[n][n_channels]) of the final epochs, the shards'
+        records side by side by global channel (lib.OCCUPANCY_DTYPE)"""
+        from .lib import OCCUPANCY_DTYPE, OCCUPANCY_EPOCHS_HELD
+        np_, n = self._np, OCCUPANCY_EPOCHS_HELD
+        rec, first = np_.zeros((n, self.n_channels), dtype=OCCUPANCY_DTYPE), np_.zeros(n, dtype=np_.int64)
+        got = self._C.c_int()
+        self._raise(self._lib.gnuais_node_drain_occupancy(self._h, rec.ctypes.data, first.ctypes.data, n, self._C.byref(got)))
+        return first[: got.value].copy(), rec[: got.value].copy()
+
     def unique(self, window: int):
         """gnuais_node_unique(): each transmission once over the whole node (merged on the host: the shards exchange
         nothing); window in rows, 0 = off.  Needs frame_times()."""

@@ -355,7 +355,7 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
- * "frame_signal" (gnuais_batch_frame_signal(); 0 = off),
+ * "frame_signal" (gnuais_batch_frame_signal(); 0 = off), "occupancy" (gnuais_batch_occupancy(); epoch_blocks, 0 = off),
  * "repair" (gnuais_batch_repair(); 0 = off), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
  * (gnuais_batch_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
  * one, 8 the lane-per-channel one; 0 before any call and after a reset) */
@@ -513,6 +513,78 @@ int  gnuais_batch_drain_frames_signal(gnuais_batch *b, gnuais_frame *h_out, int6
 int  gnuais_batch_signal_blocks(gnuais_batch *b, long long j0, int count, int64_t *h_out);
 int  gnuais_frame_signal_span(long long t, int nbits, unsigned pllinc, int n_taps, int afc_window, long long v0,
                               long long *j_lo, int *nb);
+
+/* ---- how loaded a channel is: noise floor, busy and decoded air time per receiver -----------------------------------------
+ * The section above describes what was decoded.  This one describes what was on the air: per channel and epoch of E
+ * blocks, the noise floor, the blocks with a signal above it, how many bursts they form and how many of them lie under a
+ * decoded frame -- the load figure of a base station, the reference every `power` is ranked against, and the share of the
+ * busy air time that ended in a frame (the rest: collisions, garbled slots, signals too weak to decode).  Off by default:
+ * while off, a call launches exactly what it launches without this section.  While on, every I/Q-type call launches one
+ * more kernel behind the ingest kernel of the section above and one more behind its frame-signal launch, and the call
+ * that makes an epoch final one more per such epoch.
+ * n, x[n], P_j, q, S, d_f and W are those of the section above.  v0 is that section's v0, or the row at which
+ * gnuais_batch_occupancy switched the feature on where that is later.
+ * Code of a block.  code(P) for 0 <= P < 2^38:
+ *     code(P) = P                                           for P < 8
+ *     code(P) = 8 (e - 2) + ((P >> (e - 3)) & 7)            otherwise, e = floor(log2 P)
+ *   monotone, eight steps per octave (0.376 dB), at most 287 (nine bits).
+ *     power(code) = code for code < 8, else (8 + (code & 7)) << (code / 8 - 1)         the lower edge of the code's bin
+ *   c_j = code(P_j) for every complete block j with 64 j >= v0.
+ * Epochs.  b0 = ceil(v0 / 64).  Epoch k of a run covers the blocks [b0 + k E, b0 + (k + 1) E); E is the caller's,
+ *   64 <= E <= 4096.
+ * Per epoch and channel:
+ *     floor   = the element of rank floor(E / 8) (0-based, ascending) among the epoch's c_j.  The lowest octile stays on
+ *               noise up to about 85 % load.  Against the mean noise power it is biased low (the octile of a chi-square of
+ *               128 degrees, and the bin's lower edge): a property of the estimator (DESIGN.md 4.17 has the measured
+ *               value); no correction is made.
+ *     busy_j  = c_j >= floor + m, m the caller's margin in code steps, 1 <= m <= 255.
+ *     busy    = the number of busy blocks.
+ *     bursts  = the number of j in the epoch with busy_j and not busy_(j-1); for the epoch's first block busy_(j-1) is the
+ *               value carried from the epoch before (judged with that epoch's floor), 0 for epoch 0 of a run.
+ *     cover_j = block j intersects the cover span of a frame with t >= 0 on that channel: the rows
+ *               [q - S - S_pre, q + S_post], S_pre = floor(64 * 65536 / pllinc) (ramp, training, start flag, stuffing),
+ *               S_post = floor(8 * 65536 / pllinc).  A frame covers only if q - S - S_pre >= v0.  Repaired frames cover
+ *               like any frame.
+ *     covered = the number of blocks with busy_j and cover_j.
+ * When an epoch is final.  At the tail of the first I/Q-type call (rows [n0, n0 + len)) with
+ *     n0 + len > 64 (b0 + (k + 1) E) - 1 + LAG,    LAG = floor((448 + 24) * 65536 / pllinc) + S_pre + d_f + W/2 + 64:
+ *   every frame that can cover the epoch has its time by then.  The host knows this from n0, len and v0; nothing is read
+ *   back to decide it.  A call may make several epochs final, or none.  A run that ends (v0 moves) drops its epochs that
+ *   are not final yet; the numbering starts again at the new b0.
+ * gnuais_batch_occupancy(epoch_blocks, margin): switches the feature (epoch_blocks = 0: off, the rings are freed);
+ *   synchronises the batch.  GNUAIS_E_STATE unless gnuais_batch_frame_signal is on, and on a streaming batch; while it is
+ *   on, gnuais_batch_frame_signal(b, 0), set_option("nbuf") above the depth and gnuais_batch_afc() above the window it
+ *   was switched on at return GNUAIS_E_STATE.  GNUAIS_E_ARG for values outside the ranges above.  It allocates a ring of
+ *   codes and one of cover bytes, 3 bytes per channel and block, of
+ *   E + ceil(LAG / 64) + (nbuf + 2) ceil(max_len / 64) + 2 blocks (GNUAIS_E_HIP with the figure when the device has no
+ *   room).
+ * gnuais_batch_drain_occupancy(): the final epochs not delivered yet, oldest first: h_out[i][c] is the record of channel
+ *   c, h_first_block[i] the epoch's first block; *n_out of them, at most max.  Waits for the tails that produced them.
+ *   The library holds 64 final epochs; one more overwrites the oldest, which gnuais_batch_occupancy_lost() counts.
+ *   gnuais_batch_reset() empties the queue and zeroes that count.
+ * gnuais_batch_occupancy_blocks(): a tap, and the occupancy map a caller can plot: h_out[count][n_channels] =
+ *   c_j | busy_j << 14 | cover_j << 15 of the blocks [j0, j0 + count).  GNUAIS_E_ARG for blocks that are not of a final
+ *   epoch of the current run still held (the codes of later blocks replace them, one ring round later).
+ * gnuais_occupancy_code(), gnuais_occupancy_power(), gnuais_occupancy_cover_span(): the arithmetic alone, host code.
+ *   code: GNUAIS_E_ARG for P outside 0 .. 2^38 - 1; power: for a code outside 0 .. 288 (288: the upper edge of the last
+ *   bin).  cover_span: *j_lo and *nb of the blocks [j_lo, j_lo + nb) the cover span of a frame with time t intersects, or
+ *   0 and 0 where it covers nothing; arguments and GNUAIS_E_ARG as for gnuais_frame_signal_span().
+ * gnuais_batch_info "occupancy" (epoch_blocks; 0 = off). */
+typedef struct gnuais_occupancy {
+	uint16_t floor;        /* code of the noise floor; gnuais_occupancy_power(floor) / 64 is a power like gnuais_frame_signal's */
+	uint16_t busy;         /* blocks of the epoch at or above floor + margin */
+	uint16_t covered;      /* busy blocks under the cover span of a decoded frame */
+	uint16_t bursts;       /* runs of busy blocks that begin in the epoch */
+} gnuais_occupancy;
+int  gnuais_batch_occupancy(gnuais_batch *b, int epoch_blocks, int margin);
+int  gnuais_batch_drain_occupancy(gnuais_batch *b, gnuais_occupancy *h_out /* [max][n_channels] */,
+                                  int64_t *h_first_block /* [max] */, int max, int *n_out);
+int  gnuais_batch_occupancy_lost(gnuais_batch *b, long long *lost);
+int  gnuais_batch_occupancy_blocks(gnuais_batch *b, long long j0, int count, uint16_t *h_out /* [count][n_channels] */);
+int  gnuais_occupancy_code(long long P, int *code);
+int  gnuais_occupancy_power(int code, long long *P);
+int  gnuais_occupancy_cover_span(long long t, int nbits, unsigned pllinc, int n_taps, int afc_window, long long v0,
+                                 long long *j_lo, int *nb);
 
 /* ---- repair of frames that fail the CRC by one symbol error ---------------------------------------------------------
  * The slicer decides line levels and the NRZI decoder differentiates them, so one wrong level decision is two adjacent
@@ -895,6 +967,12 @@ int  gnuais_node_drain_frames_timed(gnuais_node *nd, gnuais_frame *h_out, int64_
 int  gnuais_node_frame_signal(gnuais_node *nd, int on);
 int  gnuais_node_drain_frames_signal(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, gnuais_frame_signal *h_signal,
                                      int max, int *n_out);
+/* gnuais_batch_occupancy() on every shard, and the merged drain: the shards see the same rows, so their epochs align;
+ * h_out[i][c] is the record of GLOBAL channel c.  Every shard delivers the same number of epochs (at most max) with the
+ * same first blocks; GNUAIS_E_STATE if they disagree. */
+int  gnuais_node_occupancy(gnuais_node *nd, int epoch_blocks, int margin);
+int  gnuais_node_drain_occupancy(gnuais_node *nd, gnuais_occupancy *h_out /* [max][n_channels] */,
+                                 int64_t *h_first_block /* [max] */, int max, int *n_out);
 /* gnuais_batch_repair() on every shard, and the repairs per global channel */
 int  gnuais_node_repair(gnuais_node *nd, int on);
 int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);

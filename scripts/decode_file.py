@@ -46,6 +46,12 @@
                                                       # it arrived, measured on the device over the raw I/Q under the frame
                                                       # (gnuais_batch_frame_signal): one line per frame on stderr with its
                                                       # power in dBFS and its carrier error in Hz.  Implies --times.
+  ... --occupancy [BLOCKS]
+                                                      # --iq / --wideband: how loaded every channel is (gnuais_batch_occupancy):
+                                                      # per receiver and epoch of BLOCKS blocks of 64 rows (default 1024, 1.4 s
+                                                      # at 48 kHz) one line on stderr with the load (busy blocks / BLOCKS), the
+                                                      # noise floor in dBFS and the share of the busy blocks that lie under a
+                                                      # decoded frame.  The end of the file that no epoch covers is not reported.
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -95,6 +101,10 @@ def main():
     ap.add_argument("--signal", action="store_true",
                     help="--iq / --wideband: every frame's power (dBFS) and carrier error (Hz) on stderr "
                          "(gnuais_batch_frame_signal); implies --times")
+    ap.add_argument("--occupancy", type=int, nargs="?", const=1024, default=0, metavar="BLOCKS",
+                    help="--iq / --wideband: per receiver and epoch of BLOCKS blocks of 64 rows (64..4096, default 1024) the "
+                         "load, the noise floor in dBFS and the decoded share of the busy blocks, on stderr "
+                         "(gnuais_batch_occupancy)")
     ap.add_argument("--heard", action="store_true",
                     help="--unique: under each transmission's sentences one line with the receivers that heard it: number, "
                          "rows after the printed copy, dBFS and Hz (--iq / --wideband)")
@@ -105,6 +115,8 @@ def main():
         sys.exit("--unique takes a window in rows, > 0")
     if a.signal and not (a.iq or a.wideband):
         sys.exit("--signal needs --iq or --wideband: it measures the I/Q under a frame, audio input has none")
+    if a.occupancy and not (a.iq or a.wideband):
+        sys.exit("--occupancy needs --iq or --wideband: it measures the I/Q of a channel, audio input has none")
     if a.heard and not a.unique:
         sys.exit("--heard lists the receivers of a merged transmission: it needs --unique ROWS")
     if a.signal and a.unique:
@@ -141,12 +153,14 @@ def main():
         b.afc(a.afc)
         x = afc_flush(x, a.afc // 2)
     seq = np.zeros(n_ch, dtype=np.uint8)
-    if a.times:
+    if a.times or a.occupancy:
         b.frame_times(True)
     if a.repair:
         b.repair(True)
-    if a.measure:
+    if a.measure or a.occupancy:
         b.frame_signal(True)
+    if a.occupancy:
+        b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
     for part in io.chunks(x, a.call):
@@ -156,6 +170,7 @@ def main():
         else:
             b.run(d)
         write_sentences(a, b, seq, "iq" if a.iq else "audio", rate or 48000)
+        occupancy_report(a, b)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
@@ -244,6 +259,20 @@ def repair_report(a, b):
             sys.stderr.write(f"  repaired: receiver {c}, closing bit {e}, {n} bits\n")
 
 
+def occupancy_report(a, b):
+    """--occupancy: the epochs that became final since the last call, one line per receiver and epoch"""
+    if not a.occupancy:
+        return
+    from gnuais_amd.lib import floor_dbfs
+    first, rec = b.drain_occupancy()
+    for f, row in zip(first, rec):
+        for c, r in enumerate(row):
+            share = f"{100.0 * r['covered'] / r['busy']:.0f} %" if r["busy"] else "-"
+            sys.stderr.write(f"  occupancy: receiver {c}, blocks {int(f)}..{int(f) + a.occupancy - 1}, load "
+                             f"{100.0 * r['busy'] / a.occupancy:.1f} %, floor {floor_dbfs(r['floor']):.1f} dBFS, "
+                             f"{int(r['bursts'])} bursts, decoded {share} of busy\n")
+
+
 def afc_report(a, b, rate):
     if a.afc:
         hz = b.afc_estimate().astype(np.float64) * rate / 65536.0
@@ -280,18 +309,21 @@ def decode_wideband(a, rate, x, fmt=None):
         b.afc(a.afc)
         x = afc_flush(x, -(-(a.afc // 2) // U) * D, fmt)
     seq = np.zeros(n_ch, dtype=np.uint8)
-    if a.times:
+    if a.times or a.occupancy:
         b.frame_times(True)
     if a.repair:
         b.repair(True)
-    if a.measure:
+    if a.measure or a.occupancy:
         b.frame_signal(True)
+    if a.occupancy:
+        b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
         write_sentences(a, b, seq, "wideband", rate)
+        occupancy_report(a, b)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{M} streams x {len(offsets)} offsets, {x.shape[0]} wide samples per stream\n")
