@@ -181,7 +181,12 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
     const size_t N = (size_t) b->N;
     hipError_t e = hipSuccess;
     b->n_seg = (b->sgn_words + SEG_WORDS - 1) / SEG_WORDS;
-    b->cand_K = std::max(64, b->bits_words * 32 / 30 + 2);
+    b->seg_words = (int) (((uint64_t) SEG_WORDS * 32 * step / 65536 + 2 + 31) / 32) + 1;
+    // a frame start per 30 bits at most (see the candidate ring below), over the most bits ONE deframer launch can be
+    // handed: what a run() call slices (bits_words), or the packs filled to their capacity by gnuais_batch_decode_bits()
+    // (seg_words per segment: each pack is rounded up on its own, so n_seg of them hold more than the call's total)
+    const uint64_t launch_bits = std::max((uint64_t) b->bits_words * 32, (uint64_t) b->seg_words * 32 * (uint64_t) b->n_seg);
+    b->cand_K = (int) std::max<uint64_t>(64, launch_bits / 30 + 2);
     if (const char *v = getenv("GNUAIS_NBUF")) b->nbuf = std::min((int) gnuais_batch::NBUF, std::max(2, atoi(v)));
     {   // preflight: what this batch is about to allocate against what the device has free -- a batch that does not fit
         // says so with both figures at once instead of failing somewhere inside a dozen allocations
@@ -202,7 +207,6 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
         if (e == hipSuccess) e = buf.alloc(bytes, true);
     };
     for (int q = 0; q < gnuais_batch::HB; ++q) alloc(b->hist[q], sizeof(int16_t) * N * b->NT);
-    b->seg_words = (int) (((uint64_t) SEG_WORDS * 32 * step / 65536 + 2 + 31) / 32) + 1;
     if (b->seg_words > 16) {       // K2b keeps one segment pack (<= 16 words) in registers
         gnuais_batch_destroy(b);
         return fail(GNUAIS_E_ARG, "create: pllinc too large (more than one slice per ~4.6 samples)");
@@ -1042,6 +1046,7 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "device")) *value = b->device;
     else if (!strcmp(name, "afc_window")) *value = b->afc_W;
     else if (!strcmp(name, "segments")) *value = b->n_seg;
+    else if (!strcmp(name, "pack_bits")) *value = b->seg_words * 32;        // bits a segment's pack holds; decode_bits fills packs to this
     else if (!strcmp(name, "frame_times")) *value = b->frame_times;
     else if (!strcmp(name, "frame_signal")) *value = b->frame_signal;
     else if (!strcmp(name, "occupancy")) *value = b->occ_E;

@@ -352,7 +352,9 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "sign_eps" (its certification threshold), "sign_central_taps", "sign_matrix_pipe" (1 if the batch is ELIGIBLE for
  * the matrix-pipe FIR: table, options and channel count allow it; a call takes it when its length does too),
  * "first_effective_tap",
- * "n_effective_taps", "compute_units", "device", "segments", "stream_depth" (calls between a
+ * "n_effective_taps", "compute_units", "device", "segments", "pack_bits" (the bits one segment's pack can hold, which
+ * follows from pllinc: 64 .. 512; gnuais_batch_decode_bits() feeds "segments" packs of this size per deframer launch),
+ * "stream_depth" (calls between a
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
  * "frame_signal" (gnuais_batch_frame_signal(); 0 = off), "occupancy" (gnuais_batch_occupancy(); epoch_blocks, 0 = off),

@@ -184,10 +184,13 @@ def pipelined_case(seed):
     return f"ok   {tname:5s} n_ch {n_ch:4d} calls {lens} frames {len(got)} {' '.join(opts)}"
 
 
-def deframer_case(seed):
+def deframer_case(seed, pllinc=0, hdlc_variant=None):
     """protodec_decode() alone: adversarial bit streams (flags back to back, endless training, frames
     of every length up to and beyond the 449-bit buffer, bit errors, stuffing at the edges, runs of
-    ones), fed in several calls of random size so that every state crosses a call boundary."""
+    ones), fed in several calls of random size so that every state crosses a call boundary.
+    pllinc: the batches' clock increment, which sets the size of the packs the bits are fed in (64 bits
+    at 1, 512 at 14426); hdlc_variant: 1 the event-driven deframer, 0 the window-by-window one, None the
+    batch's own choice."""
     rng = np.random.default_rng(seed)
     n_ch = int(rng.choice([1, 5, 64, 96, 200]))
     flag = np.array([0, 1, 1, 1, 1, 1, 1, 0], dtype=np.uint8)
@@ -222,8 +225,11 @@ def deframer_case(seed):
                 parts.append(fb)
         streams.append(np.concatenate(parts).astype(np.uint8) if parts else np.zeros(0, dtype=np.uint8))
     o = Oracle(n_ch)
-    b = ReceiverBatch(n_ch, max_len=48000)
-    b2 = ReceiverBatch(n_ch, max_len=48000)                    # the same frames, formatted on the device
+    b = ReceiverBatch(n_ch, pllinc=pllinc, max_len=48000)
+    b2 = ReceiverBatch(n_ch, pllinc=pllinc, max_len=48000)     # the same frames, formatted on the device
+    if hdlc_variant is not None:
+        b.set_option("hdlc_variant", hdlc_variant)
+        b2.set_option("hdlc_variant", hdlc_variant)
     if rng.integers(0, 2):
         b.set_option("hdlc_lpw", int(rng.choice([1, 2, 8, 32, 64])))
     pos = [0] * n_ch

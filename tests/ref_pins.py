@@ -1,5 +1,5 @@
 """What the REAL reference (oracle/_ref/libgnuais_ref.so) answers on the seeded inputs of the pin tests
-(test_oracle_vs_ref.py, test_pll_cpu.py and the *_vs_reference / *_against_reference tests of test_nmea.py,
+(test_oracle_vs_ref.py, test_pll_cpu.py, test_deframer_cases_cpu.py and the *_vs_reference / *_against_reference tests of test_nmea.py,
 test_range.py, test_vessels.py).  Where oracle/_ref is built the answers come from it, live; elsewhere from the copy that
 tests/golden/make_golden.py stored in tests/golden/ref_pins.npz by calling these same functions.  The inputs are
 made here as well, so the stored answers and the tests' inputs cannot drift apart."""
@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 import cases
+import deframer_cases
 import pll_ref
 from gnuais_amd import params, synth
 from oracle_lib import have_reference, reference
@@ -135,6 +136,19 @@ def _deframer():
     return out
 
 
+def _deframer_boundaries():
+    """the streams of tests/deframer_cases.py, each decoded whole by a fresh receiver"""
+    out = {}
+    for name in deframer_cases.NAMES:
+        ref = reference()
+        ref.add_receivers(1)
+        ref.decode_bits(0, deframer_cases.STREAMS[name])
+        out["frames_" + name] = _bytes(ref.frames().tobytes())
+        out["counters_" + name] = ref.counters()
+        out["fsm_" + name] = np.array([ref.fsm(0)[k] for k in FSM], dtype=np.int64)
+    return out
+
+
 def _stdout_text(seed):
     fr, n_ch = cases.nmea_frames(seed=seed, n_channels=4, n_random=1500)
     nm, seq, tx = reference().nmea_of_frames(fr, n_ch, stdout=True)
@@ -165,6 +179,7 @@ PINS["noise_and_full_scale"] = lambda: _chain(noise_and_full_scale(), chunk=4096
 PINS["filter_floats"] = _filter_floats
 PINS["192k"] = lambda: _chain(stream_192k(), taps=params.taps_192k(), pllinc=params.PLLINC_192K, chunk=4096)
 PINS["deframer"] = _deframer
+PINS["deframer_boundaries"] = _deframer_boundaries
 for _s in pll_ref.PLLINCS:
     PINS["pll_%d" % _s] = (lambda s: lambda: _pll(s))(_s)
 for _s in (71, 72):
