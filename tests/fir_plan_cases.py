@@ -1,13 +1,19 @@
 """The tables, the call grid and the text protocol of tests/c/fir_plan_main.cpp (gnuais_amd/csrc/fir_plan.*), shared by
-tests/test_fir_plan_cpu.py and the fixture's recipe in tests/golden/make_golden.py.
+tests/test_fir_plan_cpu.py, tests/slicer_cert_ref.py (the thresholds and plans its model of the slicer kernels works with)
+and the fixture's recipe in tests/golden/make_golden.py.
 
 The driver reads
     table NAME NT d NE <NE taps as hex words>       the trimmed table
     plan N len fir_variant fir_T fir_pk_taps fir_flag2 fir_mfma dump
 and answers one line each, `bounds k=v ...` / `plan k=v ...`, floats as C hex floats."""
 import itertools
+import os
+import subprocess
 
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "tests", "c", "fir_plan.bin")
 
 N_GRID = (1, 64, 66, 16384)
 HEAD_192K = 640                 # the packed kernel's share of a call beside the matrix pipe, 192 kHz table
@@ -100,3 +106,25 @@ def parse(text):
             plans[cur].append(row)
     plans = {name: {k: np.stack([r[k] for r in rows]) for k in rows[0]} for name, rows in plans.items() if rows}
     return bounds, plans
+
+
+def run_driver(text, workdir, sanitize=True):
+    """Builds the driver if it is stale -- tests/c/fir_plan.bin with AddressSanitizer + UndefinedBehaviorSanitizer, or
+    (sanitize=False, for tests that run beside a GPU) tests/c/fir_plan_plain.bin without --, runs it on `text` (the protocol
+    above; the file goes into `workdir`) and returns parse() of its answer"""
+    if sanitize:
+        exe = EXE
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "c"), "fir_plan"])
+    else:
+        exe = os.path.join(ROOT, "tests", "c", "fir_plan_plain.bin")
+        src = [os.path.join(ROOT, "tests", "c", "fir_plan_main.cpp"), os.path.join(ROOT, "gnuais_amd", "csrc", "fir_plan.cpp")]
+        deps = src + [os.path.join(ROOT, "gnuais_amd", "csrc", "fir_plan.h")]
+        if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(f) for f in deps):
+            subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-ffp-contract=off", *src, "-o", exe, "-lm"])
+    path = os.path.join(str(workdir), "in.txt")
+    with open(path, "w") as f:
+        f.write(text)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([exe, path], capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-4000:]
+    return parse(p.stdout)

@@ -7,7 +7,6 @@ before it: tests/golden/make_golden.py), that gnuais_batch_info() and the launch
 bound holds against the oracle's exact filter where a CPU can check it.  The module runs behind tests/c/fir_plan_main.cpp,
 built on demand with AddressSanitizer + UndefinedBehaviorSanitizer (`make -C tests/c fir_plan`)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ from gnuais_amd import params
 from oracle_lib import Oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "c", "fir_plan.bin")
 K_GENERIC, K_SCALAR32, K_SIGN, K_PACKED, K_PACKED_MFMA = range(5)
 
 
@@ -34,13 +32,7 @@ def golden():
 def driver(golden, tmp_path_factory):
     """The driver's answer on the fixture's tables and the plan grid: (bounds, plans) of fir_plan_cases.parse"""
     _, _, tables = golden
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "c"), "fir_plan"])
-    path = tmp_path_factory.mktemp("fir_plan") / "in.txt"
-    path.write_text(fc.driver_input(tables, fc.PLAN_TABLES))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([EXE, str(path)], capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, p.stderr[-4000:]
-    return fc.parse(p.stdout)
+    return fc.run_driver(fc.driver_input(tables, fc.PLAN_TABLES), tmp_path_factory.mktemp("fir_plan"))
 
 
 def f32(bits):

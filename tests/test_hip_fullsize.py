@@ -271,6 +271,54 @@ def test_sign_exact_slicer_on_its_threshold(flag2):
     f = b0.filter(dev(x)).cpu().numpy()
     assert np.array_equal(f.view(np.uint32), r["filtered"].view(np.uint32))
 
+    # The opponent the patterns above lack (they stand alone in silence: y_ref = y_c up to 5e-8, and a kernel that certified
+    # EVERYTHING would pass).  Family B of tests/slicer_cert_ref.py for the direct form: every row under an omitted tap at
+    # full scale against the central sum, the central sum swept from 0.5 to 1.3 of sign_eps in both signs -- and, because
+    # this table's omitted taps carry only 32768 x sum |outer| = 0.0016 (1.5 % of eps), swept across THAT as well: there the
+    # reference's sign is the opponent's, not the central sum's.
+    ne = int(b0.info("n_effective_taps"))
+    outer_k = [k for k in range(k0, k0 + ne) if not j0 <= k < j0 + 12]
+    reach = 32768.0 * sum(abs(taps[k]) for k in outer_k)
+    assert 0.001 < reach < 0.1 * eps
+    order = sorted(range(j0, j0 + 12), key=lambda k: -abs(taps[k]))
+    pats2 = []
+    for target in [s * fr * eps for fr in np.arange(0.5, 1.3001, 0.05) for s in (1.0, -1.0)] + \
+                  [s * fr * reach for fr in (0.2, 0.4, 0.6, 0.8, 1.2, 1.5, 2.0, 5.0) for s in (1.0, -1.0)]:
+        vals, rest = {}, target
+        for k in order:
+            v = int(np.clip(np.round(rest / taps[k]), -32767, 32767))
+            vals[k] = v
+            rest -= v * taps[k]
+        pats2.append((target, vals, target - rest))
+    gap2 = 80
+    x2 = np.zeros((gap2 * (len(pats2) // n_ch + 2), n_ch), dtype=np.int16)
+    for i, (_, vals, _) in enumerate(pats2):
+        c, n = i % n_ch, gap2 * (i // n_ch + 1)
+        for k in outer_k:
+            x2[n - 36 + k, c] = -32768 if taps[k] > 0 else 32767
+        for k, v in vals.items():
+            x2[n - 36 + k, c] = v
+    o2 = Oracle(n_ch)
+    r2 = o2.run(x2, want_filtered=True, want_bits=True)
+    want2 = (r2["filtered"] > 0).T.astype(np.uint8)
+    flipped = 0
+    for i, (target, _, yc) in enumerate(pats2):
+        got = float(r2["filtered"][gap2 * (i // n_ch + 1), i % n_ch])
+        assert abs(yc - target) < 2e-4 and abs(got - (yc - reach)) < 1e-4 + 1e-3 * reach     # the construction does what it says
+        flipped += (got > 0) != (yc > 0)
+    assert flipped >= 4                                                # certifying everything would get these wrong
+    x2d = dev(x2)
+    for chunk in (x2.shape[0], 33, 1):
+        b = batch(n_ch, max_len=x2.shape[0])
+        b.set_option("fir_flag2", flag2)
+        signs = []
+        for lo in range(0, x2.shape[0], chunk):
+            hi = min(x2.shape[0], lo + chunk)
+            b.run(x2d[lo:hi])
+            signs.append(b.last_signs(hi - lo))
+        assert np.array_equal(np.concatenate(signs, axis=1), want2), chunk
+        assert pll_of(b) == [o2.pll(c) for c in range(n_ch)]
+
 
 # ---------------------------------------------------------------- more than one device
 
