@@ -200,6 +200,7 @@ struct gnuais_batch {
     // the drains, discard_frames or the resets would have to clear.
     bool frame_times = false;
     unsigned long long rows = 0;
+    bool clock_fresh = true;                    // no run or decode call since create / reset: gnuais_batch_set_clock may move the clocks
     Buf<int64_t> times;                         // [frame_cap], allocated when the feature is first switched on
     // The signal power and carrier error of every frame (gnuais_batch_frame_signal, frame_signal.hip; off by default;
     // needs frame_times).  While it is on, every I/Q-type call launches the ingest kernel in front of its discriminator

@@ -34,8 +34,11 @@ struct Member {
     int src;
 };
 
+// the output order: the untimed frames (t = -1) first, by (channel, stamp) as the plain drain orders them, then the timed
+// ones by (t, channel).  t is compared as it is, not packed into output_word(): that word holds rows below 2^39 only.
 struct Primary {
-    uint64_t order;             // output_word()
+    long long t;
+    uint64_t order;             // untimed: output_word(); timed: the channel
     int src, copies;
     size_t start;               // its members: mem[start .. start + copies) of the sort, unused for an untimed frame
 };
@@ -114,7 +117,7 @@ int push_impl(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, 
         if (times[i] < 0) {             // untimed: a cluster by itself
             uint32_t rec[16];
             memcpy(rec, &frames[i], sizeof rec);
-            prim.push_back(Primary{output_word(-1, frames[i].channel, stamp37(rec)), i, 1, 0});
+            prim.push_back(Primary{-1, output_word(-1, frames[i].channel, stamp37(rec)), i, 1, 0});
         } else {
             mem.push_back(Member{key_of(frames[i]), times[i], frames[i].channel, i});
         }
@@ -143,13 +146,14 @@ int push_impl(gnuais_uniq *u, const gnuais_frame *frames, const int64_t *times, 
                 memcpy(rec, &frames[mem[j].src], sizeof rec);
                 if (!repaired_bit(rec)) { p = j; break; }
             }
-            prim.push_back(Primary{output_word(mem[p].t, mem[p].channel, 0), mem[p].src, size, s});
+            prim.push_back(Primary{mem[p].t, mem[p].channel, mem[p].src, size, s});
         }
         if (mem[e - 1].t + W >= rows) tail.push_back(Tail{mem[s].key, mem[e - 1].t});
         s = e;
     }
     if (prim.size() > (size_t) cap) return GNUAIS_E_ARG;        // nothing consumed: tail and late are as they were
     std::sort(prim.begin(), prim.end(), [](const Primary &a, const Primary &b) {
+        if (a.t != b.t) return a.t < b.t;
         return a.order != b.order ? a.order < b.order : a.src < b.src;
     });
     for (size_t j = 0; j < prim.size(); ++j) {

@@ -322,6 +322,14 @@ static int rings_reset(gnuais_batch *b)
     return GNUAIS_OK;
 }
 
+// what is latched from the row count when it is set -- to 0 by a reset, to any row by gnuais_batch_set_clock
+static int latch_rows(gnuais_batch *b, unsigned long long rows)
+{
+    b->rows = rows;
+    b->fs_v0 = b->fs_end = rows;                // gnuais_batch_frame_signal: a new run of I/Q-type calls starts at this row
+    return occ_zero_state(b);                   // gnuais_batch_occupancy: and its epochs count from there, the queue is empty
+}
+
 int gnuais_batch_reset(gnuais_batch *b)
 {
     if (!b) return fail(GNUAIS_E_ARG, "reset: NULL batch");
@@ -337,9 +345,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     for (int k = 0; k < b->sets_alloc; ++k)
         HIP_TRY(hipMemset(b->segcnt[k], 0, sizeof(uint32_t) * N * (size_t) b->n_seg));
     b->calls = 0;
-    b->rows = 0;
-    b->fs_v0 = b->fs_end = 0;                   // gnuais_batch_frame_signal: a new run of I/Q-type calls starts at row 0
-    if (int rc = occ_zero_state(b)) return rc;  // gnuais_batch_occupancy: and its epochs count from there, the queue is empty
+    if (int rc = latch_rows(b, 0)) return rc;
     b->last[CHAIN].used = false;
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
@@ -360,7 +366,31 @@ int gnuais_batch_reset(gnuais_batch *b)
     HIP_TRY(hipDeviceSynchronize());
     b->last_len = 0;
     b->pll_form = 0;
+    b->clock_fresh = true;
     return GNUAIS_OK;
+}
+
+// The clocks of a batch that has taken nothing since create / reset, set as if that reset had happened at row `rows`
+// with h_bits[c] bits fed on channel c: the row count and what reset latches from it, and the deframer's bit count
+int gnuais_batch_set_clock(gnuais_batch *b, long long rows, const uint64_t *h_bits)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "set_clock: NULL batch");
+    if (rows < 0) return fail(GNUAIS_E_ARG, "set_clock: rows < 0");
+    if (!b->clock_fresh) return fail(GNUAIS_E_STATE, "set_clock: a run or decode call has been made since create / reset");
+    if (b->wide.K || b->afc_W)
+        return fail(GNUAIS_E_STATE, "set_clock: not with a wide stage or the AFC configured (their sample counts start at 0)");
+    if (int rc = set_device(b)) return rc;
+    const size_t N = (size_t) b->N;
+    std::vector<uint32_t> lo(N), hi(N);
+    for (size_t c = 0; c < N; ++c) {
+        const uint64_t v = h_bits ? h_bits[c] : 0;
+        lo[c] = (uint32_t) v;
+        hi[c] = (uint32_t) (v >> 32);           // every bit, as the deframer stores it
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(b->ctl + 2 * N, lo.data(), sizeof(uint32_t) * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->ctl + 5 * N, hi.data(), sizeof(uint32_t) * N, hipMemcpyHostToDevice));
+    return latch_rows(b, (unsigned long long) rows);        // the same code reset uses
 }
 
 int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
@@ -625,6 +655,7 @@ int gnuais_batch_run(gnuais_batch *b, const int16_t *d_samples, int len, void *s
     if (!b || !d_samples) return fail(GNUAIS_E_ARG, "run: NULL argument");
     if (len <= 0 || len > b->max_len) return fail(GNUAIS_E_ARG, "run: len out of range (max_len)");
     if (int rc = set_device(b)) return rc;
+    b->clock_fresh = false;
     hipStream_t s0 = (hipStream_t) stream;
     const bool pl = b->pipeline;
     const int k = (int) (b->calls % (unsigned) b->nbuf);      // hand-off buffer set of this call
@@ -819,6 +850,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
 {
     if (!b || !h_bits || !h_count || stride <= 0) return fail(GNUAIS_E_ARG, "decode_bits: argument");
     if (int rc = gnuais_batch_sync(b)) return rc;
+    b->clock_fresh = false;
     const int N = b->N, segcap = b->seg_words * 32, chunk = segcap * b->n_seg;
     int maxc = 0;
     for (int c = 0; c < N; ++c) {

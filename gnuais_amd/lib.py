@@ -49,6 +49,7 @@ SYMBOLS = {
     "gnuais_batch_create": (_I, [C.POINTER(_P), _I, _I, _P, _I, _U, _I, _I]),
     "gnuais_batch_destroy": (None, [_P]),
     "gnuais_batch_reset": (_I, [_P]),
+    "gnuais_batch_set_clock": (_I, [_P, C.c_longlong, _P]),
     "gnuais_batch_run": (_I, [_P, _P, _I, _P]),
     "gnuais_batch_run_host": (_I, [_P, _P, _I]),
     "gnuais_batch_run_host_async": (_I, [_P, _P, _I]),

@@ -56,6 +56,16 @@ class ReceiverBatch:
     def reset(self):
         check(self._lib.gnuais_batch_reset(self._h))
 
+    def set_clock(self, rows: int, bits=None):
+        """gnuais_batch_set_clock(): the batch continues as if reset() had happened at chain row `rows` with bits[c] bits
+        already fed to channel c's deframer (a scalar stands for every channel, None for 0).  Only before the first run
+        or decode call since create / reset, and not with a wide stage or the AFC configured."""
+        if bits is None:
+            check(self._lib.gnuais_batch_set_clock(self._h, int(rows), None))
+            return
+        b = np.array(np.broadcast_to(np.asarray(bits, dtype=np.uint64), (self.n_channels,)), dtype=np.uint64)
+        check(self._lib.gnuais_batch_set_clock(self._h, int(rows), b.ctypes.data))
+
     def set_option(self, name: str, value: int):
         check(self._lib.gnuais_batch_set_option(self._h, name.encode(), int(value)))
 

@@ -47,6 +47,20 @@ typedef struct gnuais_frame {
 	uint16_t nbits;        /* bufferpos - 22, src/protodec.c:1096               */
 } gnuais_frame;
 #define GNUAIS_FRAME_REPAIRED 0x40   /* gnuais_frame.flags: repaired by gnuais_batch_repair / gnuais_repair_candidate */
+/* The 37-bit stamp across its wrap.  A channel's bit count goes on past 2^37; the stamp is that count modulo 2^37, and
+ * everything that orders frames compares stamps as plain numbers.  So for the ONE drained span of a channel whose frames
+ * close on both sides of the wrap (once per 165 days of 9600 bit/s and per channel; a span whose frames all close on one
+ * side is like any other):
+ *   holds:  the records themselves, the stamp included -- every frame is delivered once, with the CRC state, the repair
+ *           flag and the counters of any other span; the receive times (gnuais_batch_frame_times takes the distance
+ *           between the count and the stamp modulo 2^37), and with them the signal records, the channel load, and the
+ *           merge and order of the timed frames in gnuais_batch_drain_frames_unique / _heard;
+ *   does not hold:  the order of that channel's frames inside that drain -- in gnuais_batch_drain_frames and its timed /
+ *           signal forms, in the sentences and sequence digits of the drain_nmea / drain_messages / stream_nmea family,
+ *           among the untimed frames of the unique drain: the frames behind the wrap come first -- and the last writer
+ *           of a vessel's field groups in gnuais_batch_fold_vessels and the carried vessel table, for the vessels that
+ *           channel reports on both sides (the report in front of the wrap wins).
+ * The carry of the count at 2^32 (5.2 days) is an ordinary carry into flags[5:1]: nothing changes across it. */
 
 /* One entry of the reference's position cache, struct cache_ent (src/cache.h:27-56), strings
  * inline: what the cache holds for one MMSI after the per-type decoders called cache_position /
@@ -111,6 +125,23 @@ int  gnuais_batch_create(gnuais_batch **out, int device, int n_channels,
 void gnuais_batch_destroy(gnuais_batch *b);
 /* back to the state init_receiver()+protodec_initialize() leave (src/protodec.c:54-76) */
 int  gnuais_batch_reset(gnuais_batch *b);
+/* Start the batch's clocks somewhere other than zero: after the call the batch behaves as if gnuais_batch_reset() had
+ * happened at chain row `rows`, with h_bits[c] bits already fed to channel c's deframer and nothing found in them
+ * (h_bits: HOST uint64 [n_channels]; NULL = 0 everywhere).  This is what a restarted receiver needs to continue a saved
+ * time base (save info("rows") and, per channel, a bit count at least as large as the one it had: receive times, block
+ * and epoch indices and the frames' 37-bit stamps then go on from there), and what lets a test reach the carries of
+ * these clocks at 2^31, 2^32 and 2^37 without days of input.
+ *   Set: the row count (info("rows"), the n0 of every receive time); the deframer's bit count, low and high word, every
+ *   bit of the high word stored as the deframer stores it (a frame's stamp carries the low 37 bits); and what reset
+ *   latches from row 0 -- the start of the run of I/Q-type calls (gnuais_batch_frame_signal) and the origin and epochs
+ *   of gnuais_batch_occupancy -- is latched from `rows` by the same code.  Nothing else changes: not the frame-start
+ *   count, not the int32 counters.
+ *   GNUAIS_E_ARG: rows < 0.  GNUAIS_E_STATE: a run or decode call (any gnuais_batch_run*, gnuais_batch_decode_bits,
+ *   gnuais_batch_stream_nmea's runs) has been made since create / reset; or a wide stage (gnuais_batch_channeliser /
+ *   _resampler) or the AFC (gnuais_batch_afc) is configured: their sample counts start at their configuration and have
+ *   start-up behaviour, and what a shifted origin means for them is not defined.  The multi-device node has no such
+ *   call.  Synchronises. */
+int  gnuais_batch_set_clock(gnuais_batch *b, long long rows, const uint64_t *h_bits);
 
 /* ---- hot path: receiver_run() for every channel, src/receiver.c:87-135 ------
  * d_samples: DEVICE pointer, interleaved int16 [len][n_channels] (the layout

@@ -55,11 +55,12 @@ def record(sums, nb: int):
 
 
 class BlockSums:
-    """The block sums of n_ch channels: [block][n_ch][3] int64 from block 0 on, fed call by call."""
+    """The block sums of n_ch channels: [block][n_ch][3] int64 from block `base` on (0 unless the clocks start at a
+    large row: blk[k] is block base + k), fed call by call."""
 
-    def __init__(self, n_ch: int):
-        self.n_ch = n_ch
-        self.reset(0)
+    def __init__(self, n_ch: int, base: int = 0):
+        self.n_ch, self.base = n_ch, int(base)
+        self.reset(self.base * B)
 
     def reset(self, n: int):
         """a new run of I/Q-type calls starts at row n"""
@@ -74,30 +75,32 @@ class BlockSums:
         if n0 != self.end:
             self.reset(n0)                                  # an audio-type call came between
         if n0 == self.v0:
-            self.blk = self.blk[:n0 // B]                   # the rows of block v0 div 64 before v0 count as zero
+            self.blk = self.blk[:n0 // B - self.base]       # the rows of block v0 div 64 before v0 count as zero
         P, r, i = row_terms(iq, self.carry)
         n1 = n0 + iq.shape[0]
-        need = -(-n1 // B)
+        need = -(-n1 // B) - self.base
         if need > self.blk.shape[0]:
             self.blk = np.concatenate([self.blk, np.zeros((need - self.blk.shape[0], self.n_ch, 3), dtype=np.int64)])
-        np.add.at(self.blk, np.arange(n0, n1) // B, np.stack([P, r, i], axis=-1))
+        np.add.at(self.blk, np.arange(n0, n1) // B - self.base, np.stack([P, r, i], axis=-1))
         self.carry = iq[-1].copy()
         self.end = n1
 
     def blocks(self, j0: int, count: int) -> np.ndarray:
-        return self.blk[j0:j0 + count].copy()
+        assert j0 >= self.base
+        return self.blk[j0 - self.base:j0 - self.base + count].copy()
 
 
 class FrameSignalRef:
     """frames, times and signal records of n_ch channels; run_iq() takes the I/Q of a call and the audio the stages in
     front of the chain made of it (iq_ref / afc_ref), run_audio() an audio-type call"""
 
-    def __init__(self, n_ch: int, taps=None, pllinc: int = 0, afc_window: int = 0):
-        self.ft = ftr.FrameTimeRef(n_ch, taps, pllinc)
+    def __init__(self, n_ch: int, taps=None, pllinc: int = 0, afc_window: int = 0, rows: int = 0, bits=None):
+        """rows, bits: where the clocks start (gnuais_batch_set_clock)"""
+        self.ft = ftr.FrameTimeRef(n_ch, taps, pllinc, rows, bits)
         self.n_ch, self.W = n_ch, afc_window
         self.n_taps = 36 if taps is None else len(taps)
         self.pllinc = pllinc or 0x10000 // 5
-        self.sums = BlockSums(n_ch)
+        self.sums = BlockSums(n_ch, rows // B)
         self.on = False
         self.calls = []                                     # (first row, v0 for the frames this call closes)
 
@@ -106,9 +109,12 @@ class FrameSignalRef:
         self.sums.reset(self.ft.n)
         self.calls = []                                     # frames of earlier calls: (0, 0, 0)
 
-    def reset(self):
-        self.ft.reset()
-        self.sums.reset(0)
+    def reset(self, rows: int = 0, bits=None):
+        """a reset, then set_clock(rows, bits)"""
+        self.ft.reset(rows, bits)
+        if rows // B != self.sums.base:
+            self.sums = BlockSums(self.n_ch, rows // B)
+        self.sums.reset(rows)
         self.calls = []
 
     def run_iq(self, iq, audio):
@@ -139,7 +145,7 @@ class FrameSignalRef:
                 continue                                    # closed before the feature was switched on
             j_lo, nb = span(int(t[k]), int(fr["nbits"][k]), self.pllinc, self.n_taps, self.W, self.calls[c][1])
             if nb:
-                sig[k] = record(self.sums.blk[j_lo:j_lo + nb, int(fr["channel"][k])].sum(axis=0), nb)
+                sig[k] = record(self.sums.blocks(j_lo, nb)[:, int(fr["channel"][k])].sum(axis=0), nb)
         return sig
 
     def drain(self):

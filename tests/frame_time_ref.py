@@ -6,6 +6,11 @@ gnuais_batch_frame_times).
   j-th slice of some segment s of the call that fed it:   t(e) = n0 + 2048 s + floor((2 j + 1) l_s / (2 c_s)).
   Bits fed without samples (decode_bits) give -1.
 
+The clocks may start anywhere (gnuais_batch_set_clock): FrameTimeRef(rows=R, bits=B) counts n from R and the bits fed on
+channel c from B[c], in int64 / Python integers throughout.  The oracle underneath always starts at zero; its records
+get their 37-bit stamp (B[c] + stamp) mod 2^37 from shift_frames() and keep the ORACLE's order, which is the order in
+time -- a sort of the shifted stamps would hide a device sort on a broken key, and is wrong across the 2^37 wrap.
+
 FrameTimeRef gets c_s from the CPU oracle by feeding it one segment at a time (its state carries across calls, so the
 frames are those of the whole call) and applies the formula to the oracle's frames.  pll_rows() is a per-sample
 transcription of the reference's loop (src/receiver.c:109-135) that gives the true slicing row of every bit, for the
@@ -21,22 +26,45 @@ def interp(n0: int, s: int, j: int, l_s: int, c_s: int) -> int:
     return n0 + SEG * s + ((2 * j + 1) * l_s) // (2 * c_s)
 
 
+M37 = (1 << 37) - 1
+
+
 def stamp(frames: np.ndarray) -> np.ndarray:
     """the 37-bit index of the bit that closed each frame: end_bit and flags[5:1]"""
     return frames["end_bit"].astype(np.int64) | (((frames["flags"].astype(np.int64) >> 1) & 31) << 32)
 
 
+def shift_frames(frames: np.ndarray, bits) -> np.ndarray:
+    """the records of a run that started at zero, as a run that started with bits[channel] bits fed delivers them: the
+    37-bit stamp (bits[channel] + stamp) mod 2^37 written back into end_bit and flags bits 5:1; everything else, the
+    order included, untouched.  bits: one value per channel, or a scalar."""
+    out = frames.copy()
+    if len(out) == 0:
+        return out
+    ch = out["channel"].astype(np.int64)
+    b = np.asarray(bits, dtype=np.uint64)
+    b = (np.broadcast_to(b, (int(ch.max()) + 1,)) if b.ndim == 0 else b)[ch] & np.uint64(M37)
+    e = (b.astype(np.int64) + stamp(out)) & M37
+    out["end_bit"] = (e & 0xffffffff).astype(np.uint32)
+    out["flags"] = ((out["flags"].astype(np.int64) & ~0x3e) | ((e >> 32) << 1)).astype(np.uint8)
+    return out
+
+
 class FrameTimeRef:
-    def __init__(self, n_ch: int, taps=None, pllinc: int = 0):
+    def __init__(self, n_ch: int, taps=None, pllinc: int = 0, rows: int = 0, bits=None):
         self.o = Oracle(n_ch, taps, pllinc)
         self.n_ch = n_ch
-        self.reset()
+        self.reset(rows, bits)
 
-    def reset(self):
+    def reset(self, rows: int = 0, bits=None):
+        """back to the state after create / reset, then set_clock(rows, bits)"""
         self.o.reset()
         self.o.clear_frames()
-        self.n = 0                                          # rows taken
-        self.fed = np.zeros(self.n_ch, dtype=np.int64)      # bits fed per channel
+        self.n = int(rows)                                  # rows taken
+        # bits fed per channel: the origin (kept below 2^37, which is all a stamp carries) + what the oracle has seen
+        self.bits0 = np.array(np.broadcast_to(np.asarray(0 if bits is None else bits, dtype=np.uint64) & np.uint64(M37),
+                                              (self.n_ch,)), dtype=np.int64)
+        self.fed = self.bits0.copy()
         # one entry per segment fed: (first row or -1, rows, bits fed before it per channel, bits in it per channel)
         self.segs = []
 
@@ -69,7 +97,7 @@ class FrameTimeRef:
         times = np.full(len(fr), -2, dtype=np.int64)
         if len(fr):
             base = np.stack([s[2] for s in self.segs])      # [segments][n_ch]
-            e = stamp(fr)
+            e = stamp(fr) + self.bits0[fr["channel"].astype(np.int64)]     # not reduced mod 2^37: comparable with `base`
             for i, (c, ei) in enumerate(zip(fr["channel"], e)):
                 # the last segment that starts at or before the bit (one without bits shares its start with the next)
                 k = int(np.searchsorted(base[:, c], ei, side="right")) - 1
@@ -78,7 +106,7 @@ class FrameTimeRef:
                 assert 0 <= j < cnt[c], (i, c, ei, k)
                 times[i] = -1 if row0 < 0 else interp(row0, 0, j, l_s, int(cnt[c]))
         self.segs = []                                      # a frame still open closes in a segment yet to come
-        return fr, times
+        return shift_frames(fr, self.bits0), times
 
 
 def pll_rows(signs: np.ndarray, pllinc: int, state=None):
