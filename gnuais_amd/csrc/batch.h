@@ -233,6 +233,16 @@ struct gnuais_batch {
     // with the feature on does not stream) and counts them per channel.
     bool repair = false;
     Buf<int32_t> repaired;                      // [N], allocated (zeroed) when the feature is first switched on
+    // Messages of three to five slots (gnuais_batch_long_frames, hdlc_long.hip; off by default): while it is on, one more
+    // launch behind each K3 runs the second decoder D' over the call's bit packs and appends its frames to a ring of its
+    // own (a batch with the feature on does not stream).  Everything is allocated when the feature is first switched on:
+    // D''s machine [LONG_CTL_WORDS][N], the open record [LONG_REC_WORDS][N], its two counters [2][N], the ring of
+    // long_cap records and its two words (frames appended, overflow flag).
+    bool long_frames = false;
+    int long_cap = 0;
+    Buf<uint32_t> long_ctl, long_open, long_count;
+    Buf<int32_t> long_counters;
+    Buf<gnuais_long_frame> long_ring;
     // One record per transmission (gnuais_batch_unique, frame_unique.hip; 0 = off): the window in rows, the open
     // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
     // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the

@@ -427,6 +427,8 @@ static int stream_setup(gnuais_batch *b)
                                                      "the streamed delivery carries no records of them");
     if (b->uq_window) return fail(GNUAIS_E_STATE, "stream_nmea: the batch merges duplicates (gnuais_batch_unique); the "
                                                   "streamed delivery has no such stage");
+    if (b->long_frames) return fail(GNUAIS_E_STATE, "stream_nmea: the batch decodes long frames (gnuais_batch_long_frames); "
+                                                    "the streamed delivery carries no records of them");
     if (int rc = gnuais_batch_sync(b)) return rc;
     // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
     // allocation) is repeated by the next call without leaking what the failed one had made

@@ -322,6 +322,16 @@ static int rings_reset(gnuais_batch *b)
     return GNUAIS_OK;
 }
 
+// D' of gnuais_batch_long_frames back to protodec_reset()'s state, a frame in progress dropped (the device is idle or the
+// null stream orders it); everything: also its two counters and its ring
+static int long_zero_state(gnuais_batch *b, bool everything)
+{
+    if (!b->long_ctl) return GNUAIS_OK;         // never switched on: nothing exists
+    HIP_TRY(launch_hdlc_long_reset(b->long_ctl, everything ? b->long_counters.p : nullptr, b->N, nullptr));
+    if (everything) HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
+    return GNUAIS_OK;
+}
+
 // what is latched from the row count when it is set -- to 0 by a reset, to any row by gnuais_batch_set_clock
 static int latch_rows(gnuais_batch *b, unsigned long long rows)
 {
@@ -359,6 +369,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     for (auto &p : b->sd_seq)
         if (p) HIP_TRY(hipMemset(p, 0, N));
     HIP_TRY(launch_hdlc_reset(b->ctl, b->N, nullptr));                // protodec.c:87-100
+    if (int rc = long_zero_state(b, true)) return rc;                 // gnuais_batch_long_frames: D', its counters, its ring
     HIP_TRY(hipMemset(b->iq_prev, 0, sizeof(int16_t) * 2 * N));       // the discriminator's previous pair: (0, 0)
     b->last[DISC].used = false;
     if (int rc = chan_zero_state(b)) return rc;
@@ -427,6 +438,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
             return fail(GNUAIS_E_STATE, "streaming: the batch measures its frames (gnuais_batch_frame_signal); the streamed delivery carries no records of them");
         if (value != 0 && b->uq_window)
             return fail(GNUAIS_E_STATE, "streaming: the batch merges duplicates (gnuais_batch_unique); the streamed delivery has no such stage");
+        if (value != 0 && b->long_frames)
+            return fail(GNUAIS_E_STATE, "streaming: the batch decodes long frames (gnuais_batch_long_frames); the streamed delivery carries no records of them");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
         if (b->streaming) {
             if (int rc = gnuais_batch_sync(b)) return rc;
@@ -553,6 +566,19 @@ static RepairLaunch fill_repair(const gnuais_batch *b, const HdlcLaunch &h)
     return r;
 }
 
+// the launch behind the K3 described by h: D' over the same packs, len rows from row b->rows on (len <= 0: bits without
+// samples)
+static LongLaunch fill_long(const gnuais_batch *b, const HdlcLaunch &h, int len)
+{
+    LongLaunch a;
+    a.segbits = h.segbits; a.segcnt = h.segcnt; a.ctl = h.ctl;
+    a.lctl = b->long_ctl; a.open = b->long_open; a.counters = b->long_counters;
+    a.frames = b->long_ring.p; a.frame_count = b->long_count; a.frame_cap = (uint32_t) b->long_cap;
+    a.N = h.N; a.n_seg = h.n_seg; a.seg_words = h.seg_words;
+    a.len = len; a.n0 = (int64_t) b->rows;
+    return a;
+}
+
 // K1 + carry: the kernel and its thresholds are plan_fir()'s choice (fir_plan.cpp).  The specialised kernels update
 // the history and clear the next peak buffer themselves; the generic fallback needs the two helper launches.
 static int run_fir(gnuais_batch *b, const int16_t *x, int len, float *dump, hipStream_t s, int k)
@@ -643,6 +669,10 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     // front of e_done[4][k] (occupancy.hip; only a call that came through run_form has I/Q rows)
     if (b->occ_E && b->fs_iq_call && (b->stage_mask & 16))
         if (int rc = occ_tail(b, h, len, sD)) return rc;
+    // messages of three to five slots: D' over this call's packs, behind the deframer that moved the bit count it reads
+    // and in front of e_done[4][k], which is what the reuse of set k (segbits, segcnt) and, where K3 has a stream of its
+    // own, the next deframer launch (ctl) wait for (hdlc_long.hip)
+    if (b->long_frames && (b->stage_mask & 8)) HIP_TRY(launch_hdlc_long(fill_long(b, h, len), sD));
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -882,6 +912,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         if (b->repair) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), nullptr));
         if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1
         if (b->frame_signal) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, 0), nullptr));   // and (0, 0, 0)
+        if (b->long_frames) HIP_TRY(launch_hdlc_long(fill_long(b, h, 0), nullptr));                // D' on the same packs: t = -1
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
@@ -991,6 +1022,7 @@ int gnuais_batch_protodec_reset(gnuais_batch *b)
     if (!b) return fail(GNUAIS_E_ARG, "protodec_reset: NULL batch");
     if (int rc = gnuais_batch_sync(b)) return rc;
     HIP_TRY(launch_hdlc_fsm_reset(b->ctl, b->N, nullptr));
+    if (int rc = long_zero_state(b, false)) return rc;      // D' likewise: its machine, not its counters or its ring
     HIP_TRY(hipStreamSynchronize(nullptr));
     return GNUAIS_OK;
 }
@@ -1060,6 +1092,15 @@ int gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride)
     return GNUAIS_OK;
 }
 
+// The long ring holds one launch's worst case: a long burst is 24 training bits, two flags and more than 426 + 16 frame
+// bits, about 470 bits, over the most bits one deframer launch can be handed (as for the candidate ring in create), on
+// every channel at once.  It is drained far more rarely than it could fill only if every channel sent nothing else.
+static int long_ring_capacity(const gnuais_batch *b)
+{
+    const uint64_t launch_bits = std::max((uint64_t) b->bits_words * 32, (uint64_t) b->seg_words * 32 * (uint64_t) b->n_seg);
+    return (int) std::max<uint64_t>(256, (uint64_t) b->N * (launch_bits / 470 + 2));
+}
+
 int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
 {
     if (!b || !name || !value) return fail(GNUAIS_E_ARG, "info: argument");
@@ -1085,6 +1126,8 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "rows")) *value = (double) b->rows;
     else if (!strcmp(name, "pll_form")) *value = b->pll_form;
     else if (!strcmp(name, "repair")) *value = b->repair;
+    else if (!strcmp(name, "long_frames")) *value = b->long_frames;
+    else if (!strcmp(name, "long_frame_cap")) *value = b->long_cap ? b->long_cap : long_ring_capacity(b);
     else if (!strcmp(name, "unique")) *value = b->uq_window;
     else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
@@ -1118,6 +1161,114 @@ int gnuais_batch_frame_times(gnuais_batch *b, int on)
         HIP_TRY(hipMemset(b->times, 0xff, sizeof(int64_t) * (size_t) b->frame_cap));
     }
     b->frame_times = on != 0;
+    return GNUAIS_OK;
+}
+
+// Messages of three to five slots on / off (definition in include/gnuais_hip.h).  Synchronises: no call is in flight when
+// the switch turns, so every K3 either has D''s launch behind it or has not.  Either way D' starts afresh: its machine,
+// its ring and its counters; its bit count is the chain's deframer's and needs nothing.
+int gnuais_batch_long_frames(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "long_frames: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "long_frames: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (on && !b->long_ctl) {
+        const size_t N = (size_t) b->N;
+        b->long_cap = long_ring_capacity(b);
+        HIP_TRY(b->long_open.ensure(sizeof(uint32_t) * N * LONG_REC_WORDS, true));
+        HIP_TRY(b->long_counters.ensure(sizeof(int32_t) * N * 2, true));
+        HIP_TRY(b->long_count.ensure(sizeof(uint32_t) * 2, true));
+        HIP_TRY(b->long_ring.ensure(sizeof(gnuais_long_frame) * (size_t) b->long_cap));
+        HIP_TRY(b->long_ctl.ensure(sizeof(uint32_t) * N * LONG_CTL_WORDS, true));    // last: long_zero_state() goes by it
+    }
+    if (int rc = long_zero_state(b, true)) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    b->long_frames = on != 0;
+    return GNUAIS_OK;
+}
+
+static_assert(sizeof(gnuais_long_frame) == 152 && sizeof(gnuais_long_frame) == 4 * LONG_FRAME_WORDS, "gnuais_long_frame layout");
+
+// the long ring's two words and what they say: records held, and whether some were dropped
+static int long_pending(gnuais_batch *b, const char *who, uint32_t &have, bool &overflow)
+{
+    if (!b->long_ctl) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: the batch has never decoded long frames (gnuais_batch_long_frames)", who);
+        return fail(GNUAIS_E_STATE, msg);
+    }
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    uint32_t cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpy(cnt, b->long_count, sizeof cnt, hipMemcpyDeviceToHost));
+    have = std::min<uint32_t>(cnt[0], (uint32_t) b->long_cap);
+    overflow = cnt[1] || cnt[0] > (uint32_t) b->long_cap;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_pending_long_frames(gnuais_batch *b, int *n_out)
+{
+    if (!b || !n_out) return fail(GNUAIS_E_ARG, "pending_long_frames: argument");
+    uint32_t have = 0;
+    bool overflow = false;
+    if (int rc = long_pending(b, "pending_long_frames", have, overflow)) return rc;
+    *n_out = (int) have;
+    return GNUAIS_OK;
+}
+
+// Everything queued, consumed once, in (channel, 37-bit stamp) order.  Long frames are rare -- the ring holds a handful
+// per drain -- so the records cross PCIe as the kernel appended them and are put in order here.
+int gnuais_batch_drain_long_frames(gnuais_batch *b, gnuais_long_frame *h_out, int max, int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max && !h_out)) return fail(GNUAIS_E_ARG, "drain_long_frames: argument");
+    *n_out = 0;
+    uint32_t have = 0;
+    bool overflow = false;
+    if (int rc = long_pending(b, "drain_long_frames", have, overflow)) return rc;
+    if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_long_frames: frame buffer too small");
+    if (have) {
+        std::vector<gnuais_long_frame> v(have);
+        HIP_TRY(hipMemcpy(v.data(), b->long_ring, sizeof(gnuais_long_frame) * have, hipMemcpyDeviceToHost));
+        const auto stamp = [](const gnuais_long_frame &f) { return (uint64_t) f.end_bit | ((uint64_t) ((f.flags >> 1) & 31) << 32); };
+        std::stable_sort(v.begin(), v.end(), [&](const gnuais_long_frame &x, const gnuais_long_frame &y) {
+            return x.channel != y.channel ? x.channel < y.channel : stamp(x) < stamp(y);
+        });
+        memcpy(h_out, v.data(), sizeof(gnuais_long_frame) * have);
+    }
+    *n_out = (int) have;
+    HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
+    if (overflow) return fail(GNUAIS_E_OVERFLOW, "drain_long_frames: long-frame ring overflowed, frames were dropped");
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_long_counters(gnuais_batch *b, int32_t *h_delivered, int32_t *h_failed)
+{
+    if (!b || !h_delivered || !h_failed) return fail(GNUAIS_E_ARG, "long_counters: argument");
+    if (!b->long_ctl) return fail(GNUAIS_E_STATE, "long_counters: the batch has never decoded long frames (gnuais_batch_long_frames)");
+    std::vector<int32_t> v;
+    if (int rc = read_out(b, b->long_counters, (size_t) b->N * 2, v)) return rc;
+    memcpy(h_delivered, v.data(), sizeof(int32_t) * (size_t) b->N);
+    memcpy(h_failed, v.data() + b->N, sizeof(int32_t) * (size_t) b->N);
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_long_fsm_state(gnuais_batch *b, gnuais_fsm_state *h_out)
+{
+    if (!b || !h_out) return fail(GNUAIS_E_ARG, "long_fsm_state: argument");
+    if (!b->long_ctl) return fail(GNUAIS_E_STATE, "long_fsm_state: the batch has never decoded long frames (gnuais_batch_long_frames)");
+    std::vector<uint32_t> v;
+    if (int rc = read_out(b, b->long_ctl, (size_t) b->N, v)) return rc;
+    for (int c = 0; c < b->N; ++c) {
+        const uint32_t w = v[c];
+        h_out[c].state = w & 7;
+        h_out[c].nstartsign = (w >> 3) & 15;
+        h_out[c].antallpreamble = (w >> 7) & 15;
+        h_out[c].antallenner = (w >> 11) & 7;
+        h_out[c].bitstuff = (w >> 14) & 1;
+        h_out[c].last = (w >> 15) & 1;
+        h_out[c].bufferpos = (w >> 16) & 2047;
+    }
     return GNUAIS_OK;
 }
 

@@ -315,6 +315,34 @@ struct RepairLaunch {
 };
 hipError_t launch_hdlc_repair(const RepairLaunch &a, hipStream_t stream);
 
+// ---- the long-frame deframer D': messages of three to five slots (hdlc_long.hip; definition in include/gnuais_hip.h) ----
+// One launch behind the call's K3, on its stream, in front of the event that frees the call's hand-off set (segbits,
+// segcnt) and before the next deframer launch moves ctl on.  D' walks the call's packs with a machine of its own (lctl),
+// keeps the raw bits of the frame it is in in the channel's open record, and appends every frame of more than
+// LONG_SHORT_BITS bits whose CRC holds to the long ring through frame_count[0] (overflow: frame_count[1]).
+constexpr int LONG_CTL_WORDS = 3;        // [0] the machine's fields, [1] the open record's partial word, [2] its raw bits
+constexpr int LONG_REC_WORDS = 40;       // the open record: 1030 stored bits + at most 206 stuffed zeros = 1236 raw bits
+constexpr int LONG_FRAME_WORDS = 38;     // sizeof(gnuais_long_frame) / 4
+constexpr int LONG_LIMIT_BITS = 1031;    // D' gives a frame up at this many stored bits: 1008 + 22 + 1
+constexpr int LONG_SHORT_BITS = 426;     // a frame of at most this many bits is the chain's decoder's
+struct LongLaunch {
+    const uint32_t *segbits;       // as in HdlcLaunch, of the call's hand-off set
+    const uint32_t *segcnt;
+    const uint32_t *ctl;           // the chain's deframer's control state AFTER the call ([2], [5]: bits fed since reset)
+    uint32_t *lctl;                // [LONG_CTL_WORDS][N]
+    uint32_t *open;                // [LONG_REC_WORDS][N]
+    int32_t *counters;             // [2][N]: long frames delivered, long frames that failed the CRC
+    void *frames;                  // gnuais_long_frame[frame_cap]
+    uint32_t *frame_count;         // [2]: frames appended, overflow flag
+    uint32_t frame_cap;
+    int N, n_seg, seg_words;
+    int len;                       // rows of the call (<= 0: bits without samples, t = -1)
+    int64_t n0;                    // rows the chain had taken before it
+};
+hipError_t launch_hdlc_long(const LongLaunch &a, hipStream_t stream);
+// protodec_reset() for D' (counters: also its two counters, else null)
+hipError_t launch_hdlc_long_reset(uint32_t *lctl, int32_t *counters, int N, hipStream_t stream);
+
 // ---- one record per transmission: the duplicate merge of a drain (frame_unique.hip; definition in include/gnuais_hip.h) ----
 // Entries = [tail | ring]: n_tail open clusters of earlier drains (16 words each: t_last, then the key as a record
 // holds it) and the `have` frames of the ring with their times.  unique_cluster_enqueue() queues everything up to the

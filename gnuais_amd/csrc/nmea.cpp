@@ -686,6 +686,81 @@ extern "C" int gnuais_nmea_from_frames(const gnuais_frame *frames, int n_frames,
                                        n_sentences, nullptr, 0, nullptr, nullptr);
 }
 
+// The sentences of the long frames (gnuais_batch_drain_long_frames): protodec_getdata()'s head -- the type test, the fill
+// bits, the sequence digit (protodec.c:898-926) -- and protodec_generate_nmea() as written (protodec.c:780-893) over a
+// buffer long enough for 1008 bits: two or three sentences of at most 61 characters.  d->rbuffer holds the frame's
+// nbits / 8 whole bytes and zeros behind them, as for any frame (Bits above).  seqnr, sizing and overflow as in
+// gnuais_nmea_from_frames(); a caller may hand the same seqnr array to both.
+extern "C" int gnuais_nmea_from_long_frames(const gnuais_long_frame *frames, int n_frames, uint8_t *seqnr, int n_channels,
+                                            char *out, size_t out_cap, size_t *out_len, int *n_sentences)
+{
+    if (n_frames < 0 || (n_frames > 0 && !frames) || !seqnr || n_channels <= 0 || !out_len) return GNUAIS_E_ARG;
+    Sink sink{out, out_cap, 0, true};
+    int total = 0;
+    for (int k = 0; k < n_frames; ++k) {
+        const gnuais_long_frame &f = frames[k];
+        if (f.channel >= (uint32_t) n_channels || f.nbits > GNUAIS_LONG_MAX_BITS) return GNUAIS_E_ARG;
+        const int whole = f.nbits >> 3;
+        // protodec_henten(pos, 6, d->rbuffer): six bits from pos, most significant first; 0 behind the whole bytes
+        const auto six = [&](int pos) {
+            unsigned v = 0;
+            for (int i = pos; i < pos + 6; ++i)
+                v = (v << 1) | ((i >> 3) < whole ? (f.payload[i >> 3] >> (7 - (i & 7))) & 1u : 0u);
+            return v;
+        };
+        const unsigned type = six(0);
+        if (type < 1 || type > (unsigned) MAX_TYPE) continue;           // protodec.c:898-900
+        int bufferlen = f.nbits, fillbits = 0;
+        if (bufferlen % 6 > 0) {                                        // :909-915
+            fillbits = 6 - bufferlen % 6;
+            bufferlen += fillbits;
+        }
+        const int senlen = CHARS_PER_SENTENCE;
+        int sentences = 1;                                              // :794-801
+        if (bufferlen > senlen * 6) sentences = bufferlen / (senlen * 6) + (bufferlen % (senlen * 6) != 0 ? 1 : 0);
+        uint8_t &seq = seqnr[f.channel];
+        int sentencenum = 0, pos = 0;
+        do {
+            char nmea[96];
+            int kk = 13;                                                // :806-817
+            while (kk < senlen + 13 && bufferlen > pos) {
+                const unsigned letter = six(pos);
+                nmea[kk++] = (char) (letter < 40 ? letter + 48 : letter + 56);
+                pos += 6;
+            }
+            memcpy(nmea + kk, ",0*", 3);                                // :821-826, the checksum follows
+            ++sentencenum;
+            memcpy(nmea, "AIVDM,", 6);                                  // :832-841
+            nmea[6] = (char) (48 + sentences);
+            nmea[7] = ',';
+            nmea[8] = (char) (48 + sentencenum);
+            nmea[9] = ',';
+            if (sentences > 1) {                                        // :844-860
+                nmea[10] = (char) (seq + 48);
+                nmea[11] = ',';
+                nmea[12] = ',';
+                if (sentencenum == sentences) nmea[kk + 1] = (char) (48 + fillbits);
+            } else {
+                nmea[10] = ',';
+                nmea[11] = 'A';
+                nmea[12] = ',';
+            }
+            unsigned char chk = 0;                                      // :864-880
+            for (int m = 0; nmea[m] != '*'; ++m) chk ^= (unsigned char) nmea[m];
+            nmea[kk + 3] = HEX[chk >> 4];
+            nmea[kk + 4] = HEX[chk & 15];
+            sink.put("!", 1);                                           // :883
+            sink.put(nmea, (size_t) kk + 5);
+            sink.put("\r\n", 2);
+            ++total;
+        } while (sentencenum < sentences);
+        seq = (uint8_t) (seq + 1 > 9 ? 0 : seq + 1);                    // :924-926
+    }
+    *out_len = sink.len;
+    if (n_sentences) *n_sentences = total;
+    return sink.fits ? GNUAIS_OK : GNUAIS_E_OVERFLOW;
+}
+
 // The same sentences, each preceded by an NMEA 4.10 TAG block that carries the frame's receive time:
 // "\c:<unix>*hh\" with <unix> = epoch_s + floor((t * mul + off) / rate_hz) and hh the XOR of the characters between the
 // backslashes up to the '*'.  A frame with t = -1 (no receive time on record) gets no tag.  The sentences themselves are

@@ -580,6 +580,48 @@ int gnuais_node_repaired(gnuais_node *nd, int32_t *h_out)
     return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_repaired(s.b, h_out + s.first); });
 }
 
+// messages of three to five slots (gnuais_batch_long_frames on every shard)
+int gnuais_node_long_frames(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_long_frames: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_long_frames(s.b, on); });
+}
+
+int gnuais_node_long_counters(gnuais_node *nd, int32_t *h_delivered, int32_t *h_failed)
+{
+    if (!nd || !h_delivered || !h_failed) return node_fail(GNUAIS_E_ARG, "node_long_counters: argument");
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_long_counters(s.b, h_delivered + s.first, h_failed + s.first); });
+}
+
+// every shard drains its own long ring; a shard's records come in (channel, stamp) order with LOCAL channel numbers and
+// the shards own ascending channel blocks, so the parts are renumbered and laid end to end
+int gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max && !h_out)) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames: argument");
+    *n_out = 0;
+    std::vector<Shard *> &sh = nd->shards;
+    std::vector<int> pend(sh.size(), 0);
+    if (int rc = run_all(nd, [&](Shard &s, size_t i) { return gnuais_batch_pending_long_frames(s.b, &pend[i]); })) return rc;
+    long long total = 0;
+    for (int v : pend) total += v;
+    if (total > max) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames: frame buffer too small");
+    std::vector<std::vector<gnuais_long_frame>> part(sh.size());
+    std::vector<int> cnt(sh.size(), 0);
+    const int rc = run_all(nd, [&](Shard &s, size_t i) {
+        part[i].resize((size_t) std::max(pend[i], 1));
+        const int r = gnuais_batch_drain_long_frames(s.b, part[i].data(), pend[i], &cnt[i]);
+        for (int k = 0; k < cnt[i]; ++k) part[i][(size_t) k].channel += (uint32_t) s.first;
+        return r;
+    });
+    int w = 0;
+    for (size_t i = 0; i < sh.size(); ++i) {
+        if (cnt[i] > 0) memcpy(h_out + w, part[i].data(), sizeof(gnuais_long_frame) * (size_t) cnt[i]);
+        w += cnt[i];
+    }
+    *n_out = w;
+    return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
+}
+
 static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out,
                       gnuais_frame_signal *h_signal = nullptr);
 

@@ -33,6 +33,11 @@ assert HEARER_DTYPE.itemsize == 24
 OCCUPANCY_DTYPE = np.dtype([("floor", "<u2"), ("busy", "<u2"), ("covered", "<u2"), ("bursts", "<u2")])
 assert OCCUPANCY_DTYPE.itemsize == 8
 OCCUPANCY_EPOCHS_HELD = 64    # final epochs the library keeps for gnuais_batch_drain_occupancy
+# struct gnuais_long_frame: a message of three to five slots (gnuais_batch_long_frames)
+LONG_FRAME_DTYPE = np.dtype([("channel", "<u4"), ("end_bit", "<u4"), ("t", "<i8"), ("nbits", "<u2"), ("flags", "u1"),
+                             ("reserved", "u1"), ("payload", "u1", (132,))])
+assert LONG_FRAME_DTYPE.itemsize == 152
+LONG_MAX_BITS = 1008         # GNUAIS_LONG_MAX_BITS
 FRAME_REPAIRED = 0x40        # GNUAIS_FRAME_REPAIRED: frame flags bit 6
 
 # kinds of input for gnuais_batch_time_map (GNUAIS_INPUT_* in include/gnuais_hip.h)
@@ -107,6 +112,12 @@ SYMBOLS = {
     "gnuais_batch_repair": (_I, [_P, _I]),
     "gnuais_batch_repaired": (_I, [_P, _P]),
     "gnuais_repair_candidate": (_I, [_P, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
+    "gnuais_batch_long_frames": (_I, [_P, _I]),
+    "gnuais_batch_pending_long_frames": (_I, [_P, C.POINTER(_I)]),
+    "gnuais_batch_drain_long_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_long_counters": (_I, [_P, _P, _P]),
+    "gnuais_batch_long_fsm_state": (_I, [_P, _P]),
+    "gnuais_nmea_from_long_frames": (_I, [_P, _I, _P, _I, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I)]),
     "gnuais_batch_unique": (_I, [_P, _I]),
     "gnuais_batch_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -182,6 +193,9 @@ SYMBOLS = {
     "gnuais_node_drain_occupancy": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_repair": (_I, [_P, _I]),
     "gnuais_node_repaired": (_I, [_P, _P]),
+    "gnuais_node_long_frames": (_I, [_P, _I]),
+    "gnuais_node_drain_long_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_long_counters": (_I, [_P, _P, _P]),
     "gnuais_node_unique": (_I, [_P, _I]),
     "gnuais_node_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),

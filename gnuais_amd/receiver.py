@@ -14,7 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import lib as _lib
-from .lib import COUNTERS_DTYPE, E_OVERFLOW, FRAME_DTYPE, FSM_DTYPE, OK, PLL_DTYPE, GnuaisError, check
+from .lib import (COUNTERS_DTYPE, E_OVERFLOW, FRAME_DTYPE, FSM_DTYPE, LONG_FRAME_DTYPE, OK, PLL_DTYPE, GnuaisError,
+                  check)
 
 
 def _is_torch(x) -> bool:
@@ -366,6 +367,45 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_repaired(self._h, out.ctypes.data))
         return out
 
+    def long_frames(self, on: bool = True):
+        """gnuais_batch_long_frames(): from now on a second decoder per channel delivers the messages of three to five
+        slots (427 .. 1008 bits), which the chain -- the reference bit for bit -- gives up at 449 stored bits, as records
+        of their own (the definition is in include/gnuais_hip.h); one more launch per call.  Synchronises; switching
+        resets that decoder, its ring and its counters.  Not on a streaming batch."""
+        check(self._lib.gnuais_batch_long_frames(self._h, int(bool(on))))
+
+    def pending_long_frames(self) -> int:
+        n = C.c_int()
+        check(self._lib.gnuais_batch_pending_long_frames(self._h, C.byref(n)))
+        return n.value
+
+    def drain_long_frames(self) -> np.ndarray:
+        """gnuais_batch_drain_long_frames(): LONG_FRAME_DTYPE records in (channel, stamp) order, each with its receive
+        time t in chain rows (-1: closed by decode_bits).  GnuaisError(E_OVERFLOW) carries what was delivered in
+        `.frames`."""
+        n = self.pending_long_frames()
+        out = np.zeros(max(n, 1), dtype=LONG_FRAME_DTYPE)
+        got = C.c_int()
+        rc = self._lib.gnuais_batch_drain_long_frames(self._h, out.ctypes.data, int(out.size), C.byref(got))
+        if rc == E_OVERFLOW:
+            err = GnuaisError(rc, self._lib.gnuais_last_error().decode())
+            err.frames = out[: got.value].copy()
+            raise err
+        check(rc)
+        return out[: got.value].copy()
+
+    def long_counters(self):
+        """gnuais_batch_long_counters(): (delivered, failed), int32 [n_channels] each: the long frames the second decoder
+        delivered and those (more than 426 bits) whose CRC failed"""
+        d = np.zeros(self.n_channels, dtype=np.int32)
+        f = np.zeros(self.n_channels, dtype=np.int32)
+        check(self._lib.gnuais_batch_long_counters(self._h, d.ctypes.data, f.ctypes.data))
+        return d, f
+
+    def long_fsm_state(self) -> np.ndarray:
+        """gnuais_batch_long_fsm_state(): the second decoder's live fields, as fsm_state()"""
+        return self._struct_array(self._lib.gnuais_batch_long_fsm_state, FSM_DTYPE)
+
     def drain_frames_timed(self):
         """gnuais_batch_drain_frames_timed(): (frames, int64 times), times[i] the receive time of frames[i] in chain rows
         since create / reset, -1 where there is none (decode_bits, or appended while the feature was off)."""
@@ -671,6 +711,21 @@ def nmea_from_frames(frames: np.ndarray, seqnr: np.ndarray) -> bytes:
     n_sent = C.c_int(0)
     check(lib.gnuais_nmea_from_frames(frames.ctypes.data, len(frames), seqnr.ctypes.data, len(seqnr),
                                       out.ctypes.data, cap, C.byref(need), C.byref(n_sent)))
+    return out[: need.value].tobytes()
+
+
+def nmea_from_long_frames(frames: np.ndarray, seqnr: np.ndarray) -> bytes:
+    """gnuais_nmea_from_long_frames(): the two or three "!AIVDM" sentences of each long frame record, concatenated;
+    `seqnr` as in nmea_from_frames() (the same array may serve both)."""
+    lib = _lib.load()
+    frames = np.ascontiguousarray(frames, dtype=LONG_FRAME_DTYPE)
+    assert seqnr.dtype == np.uint8 and seqnr.flags.c_contiguous
+    cap = 3 * 82 * max(1, len(frames))
+    out = np.zeros(cap, dtype=np.uint8)
+    need = C.c_size_t(0)
+    n_sent = C.c_int(0)
+    check(lib.gnuais_nmea_from_long_frames(frames.ctypes.data, len(frames), seqnr.ctypes.data, len(seqnr),
+                                           out.ctypes.data, cap, C.byref(need), C.byref(n_sent)))
     return out[: need.value].tobytes()
 
 

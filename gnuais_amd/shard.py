@@ -226,6 +226,32 @@ class ReceiverNode:
         self._raise(self._lib.gnuais_node_repaired(self._h, out.ctypes.data))
         return out
 
+    def long_frames(self, on: bool = True):
+        """gnuais_batch_long_frames() on every shard"""
+        self._raise(self._lib.gnuais_node_long_frames(self._h, int(bool(on))))
+
+    def drain_long_frames(self):
+        """gnuais_node_drain_long_frames(): the long frames of every shard, global channel numbers, (channel, stamp) order.
+        The node has no count of them: the buffer doubles until the call takes it (a refused call consumes nothing)."""
+        from .lib import E_ARG, E_OVERFLOW, LONG_FRAME_DTYPE
+        n = 1024
+        while True:
+            out = self._np.zeros(n, dtype=LONG_FRAME_DTYPE)
+            got = self._C.c_int()
+            rc = self._lib.gnuais_node_drain_long_frames(self._h, out.ctypes.data, n, self._C.byref(got))
+            if rc == E_ARG and n < 1 << 24:
+                n *= 4
+                continue
+            self._raise(rc)
+            return out[: got.value].copy()
+
+    def long_counters(self):
+        """gnuais_node_long_counters(): (delivered, failed), int32 [n_channels] each, per global channel"""
+        d = self._np.zeros(self.n_channels, dtype=self._np.int32)
+        f = self._np.zeros(self.n_channels, dtype=self._np.int32)
+        self._raise(self._lib.gnuais_node_long_counters(self._h, d.ctypes.data, f.ctypes.data))
+        return d, f
+
     def drain_frames_timed(self):
         """gnuais_node_drain_frames_timed(): (frames, int64 times), as drain_frames with every record's receive time"""
         from .lib import FRAME_DTYPE

@@ -662,6 +662,69 @@ int  gnuais_batch_repair(gnuais_batch *b, int on);
 int  gnuais_batch_repaired(gnuais_batch *b, int32_t *h_out /* [n_channels] */);
 int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload[53], int *nbits, int *pos);
 
+/* ---- messages of three to five slots: a second decoder for long frames ------------------------------------------------
+ * protodec_decode() gives a frame up once 449 unstuffed bits are stored (src/protodec.c:1024), so the chain -- which is the
+ * reference bit for bit -- delivers no message of more than 426 bits: two slots.  ITU-R M.1371 allows five slots, 1008
+ * bits: binary messages (types 6, 8), safety text (12, 14), DGNSS corrections (17), type 26.  With this feature on they are
+ * delivered as records of their own.  Off by default: while off, a call launches exactly what it launches without this
+ * section, and whether on or off the chain's frames, counters and state are what they are without it.
+ *   Definition.  Each channel gets a second decoder D', independent of the chain's.  It is protodec_decode() /
+ *     protodec_reset() / protodec_calculate_crc() statement by statement with exactly these changes:
+ *       - the two buffers hold 1200 bits;
+ *       - the give-up test `bufferpos >= 449` is `bufferpos >= 1031`: GNUAIS_LONG_MAX_BITS + 22 + 1;
+ *       - a frame that reaches ST_STOPSIGN's good branch (stop bit 0, n = bufferpos - 22 > 0) is delivered only if
+ *         n > 426 and the CRC holds -- the reference's routine over n/8 + 2 bytes, as it stands.  Frames with n <= 426
+ *         belong to the chain's decoder: D' walks over them and says nothing;
+ *       - D' keeps two per-channel int32 counters: long frames delivered, and long frames (n > 426) that failed the CRC.
+ *   Carried state.  D' sees the bit stream the chain's deframer sees, through every kind of call: audio, I/Q, wideband,
+ *     their host forms, gnuais_batch_decode_bits.  Its bit count IS that deframer's count: a long frame's 37-bit stamp
+ *     (end_bit and flags[5:1]) is what the chain's deframer would stamp a frame closing on the same bit, also when the
+ *     feature is switched on in mid-stream, and gnuais_batch_set_clock moves it.  gnuais_batch_reset() clears everything;
+ *     gnuais_batch_protodec_reset() resets D''s machine and keeps the count and the counters.  Switching the feature on or
+ *     off synchronises and resets D''s machine, ring and counters.
+ *   Record.  payload is packed as in gnuais_frame: nbits/8 bytes used, the rest zero.  flags bit 0 is set, bits 5:1 are
+ *     stamp bits 36:32.  t is the receive time by the formula of the frame-times section, n_0 + 2048 s + floor((2j + 1)
+ *     l_s / (2 c_s)): D''s kernel walks a call's segments in order and knows s, j, l_s and c_s of the closing bit itself,
+ *     so t is filled in whether gnuais_batch_frame_times is on or off.  t = -1 for a frame closed by
+ *     gnuais_batch_decode_bits.
+ *   Not in this section.  For long frames there is no repair (gnuais_batch_repair), no duplicate merge and no member
+ *     lists (gnuais_batch_unique), no signal record and no share in the channel load (gnuais_batch_frame_signal,
+ *     gnuais_batch_occupancy), no stdout text line, no device formatter (gnuais_batch_drain_nmea and its family), no
+ *     entry in the vessel tables and no streamed delivery.  t and the stamp are in the record, so a host can do these
+ *     itself.
+ * gnuais_batch_long_frames(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE on a streaming batch, and
+ *   while it is on the batch cannot start streaming (gnuais_batch_stream_nmea, gnuais_batch_autotune_delivery and
+ *   set_option("streaming", 1) return GNUAIS_E_STATE): the streamed delivery carries no records of long frames.  One more
+ *   launch follows every call's CRC stage while it is on (and every chunk of gnuais_batch_decode_bits).
+ * gnuais_batch_pending_long_frames(): the long frames queued.  Synchronises.
+ * gnuais_batch_drain_long_frames(): everything queued, consumed once, in (channel, stamp) order.  The long frames have a
+ *   ring of their own (info "long_frame_cap": sized from max_len and pllinc so that the worst case of one call fits -- a
+ *   long burst is at least about 470 bits); when it overflowed the call delivers what it holds, the oldest records, and
+ *   returns GNUAIS_E_OVERFLOW, as the frame ring does.  GNUAIS_E_ARG when max is less than what is queued.
+ * gnuais_batch_long_counters(): the two counters of D' per channel since create / reset / the last switch.
+ * gnuais_batch_long_fsm_state(): the live fields of D''s machine, as gnuais_batch_fsm_state() (bufferpos up to 1030):
+ *   the parity tap for the carried state.
+ *   These four return GNUAIS_E_STATE on a batch whose feature was never switched on.
+ * gnuais_nmea_from_long_frames(): host code, no device.  protodec_getdata()'s head (type test, fill bits, sequence digit)
+ *   and protodec_generate_nmea() as written (src/protodec.c:780-926) over the longer buffer: two or three sentences of at
+ *   most 61 characters per frame.  seqnr, sizing and overflow as in gnuais_nmea_from_frames(); a caller may pass the
+ *   same seqnr array to both.  GNUAIS_E_ARG for a record with nbits > GNUAIS_LONG_MAX_BITS. */
+#define GNUAIS_LONG_MAX_BITS 1008
+typedef struct gnuais_long_frame {
+	uint32_t channel, end_bit;
+	int64_t  t;
+	uint16_t nbits;
+	uint8_t  flags, reserved;
+	uint8_t  payload[132];
+} gnuais_long_frame;   /* 152 bytes */
+int  gnuais_batch_long_frames(gnuais_batch *b, int on);
+int  gnuais_batch_pending_long_frames(gnuais_batch *b, int *n_out);
+int  gnuais_batch_drain_long_frames(gnuais_batch *b, gnuais_long_frame *h_out, int max, int *n_out);
+int  gnuais_batch_long_counters(gnuais_batch *b, int32_t *h_delivered /* [n_channels] */, int32_t *h_failed /* [n_channels] */);
+int  gnuais_batch_long_fsm_state(gnuais_batch *b, gnuais_fsm_state *h_out /* [n_channels] */);
+int  gnuais_nmea_from_long_frames(const gnuais_long_frame *frames, int n_frames, uint8_t *seqnr, int n_channels,
+                                  char *out, size_t out_cap, size_t *out_len, int *n_sentences);
+
 /* ---- each transmission once: the copies several receivers hear, merged on the delivery side ----------------------------
  * Not in the reference (one process, one or two receivers).  A batch is thousands of receivers with overlapping cover,
  * and most transmissions are heard by more than one of them; every copy is a frame of its own in the drains above.
@@ -1007,6 +1070,11 @@ int  gnuais_node_occupancy(gnuais_node *nd, int epoch_blocks, int margin);
 int  gnuais_node_drain_occupancy(gnuais_node *nd, gnuais_occupancy *h_out /* [max][n_channels] */,
                                  int64_t *h_first_block /* [max] */, int max, int *n_out);
 /* gnuais_batch_repair() on every shard, and the repairs per global channel */
+/* gnuais_batch_long_frames / _long_counters on every shard; the drain merged over the shards, with global channel numbers,
+ * in (channel, stamp) order */
+int  gnuais_node_long_frames(gnuais_node *nd, int on);
+int  gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out);
+int  gnuais_node_long_counters(gnuais_node *nd, int32_t *h_delivered /* [n_channels] */, int32_t *h_failed /* [n_channels] */);
 int  gnuais_node_repair(gnuais_node *nd, int on);
 int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);
 /* gnuais_batch_unique()'s definition over the whole node.  Copies on different shards must merge, and the shards

@@ -52,6 +52,13 @@
                                                       # at 48 kHz) one line on stderr with the load (busy blocks / BLOCKS), the
                                                       # noise floor in dBFS and the share of the busy blocks that lie under a
                                                       # decoded frame.  The end of the file that no epoch covers is not reported.
+  ... --long
+                                                      # also the messages of three to five slots (427 .. 1008 bits: binary
+                                                      # messages, safety text, DGNSS corrections), which the reference's
+                                                      # decoder and so the chain give up on: a second decoder on the device
+                                                      # (gnuais_batch_long_frames) delivers them, and their two or three
+                                                      # sentences follow each call's other sentences -- behind TAG blocks of
+                                                      # their own when --times is given; the summary counts them
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -109,6 +116,10 @@ def main():
                     help="--unique: under each transmission's sentences one line with the receivers that heard it: number, "
                          "rows after the printed copy, dBFS and Hz (--iq / --wideband)")
     ap.add_argument("--verbose", action="store_true", help="--unique: the copies of every printed transmission, on stderr")
+    ap.add_argument("--long", action="store_true",
+                    help="also decode the messages of three to five slots (427 .. 1008 bits: binary, safety text, DGNSS), "
+                         "which the chain gives up on (gnuais_batch_long_frames); their sentences follow each call's others, "
+                         "with TAG blocks when --times is given")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
     if a.unique < 0:
@@ -163,6 +174,8 @@ def main():
         b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
+    if a.long:
+        b.long_frames(True)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -170,12 +183,15 @@ def main():
         else:
             b.run(d)
         write_sentences(a, b, seq, "iq" if a.iq else "audio", rate or 48000)
+        write_long(a, b, seq, "iq" if a.iq else "audio", rate or 48000)
         occupancy_report(a, b)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
                      f"{n_ch} channels, {x.shape[0]} samples per channel\n")
     repair_report(a, b)
     afc_report(a, b, 48000)
+    if a.long:
+        sys.stderr.write(f"{getattr(a, 'long_frames', 0)} long frames (more than two slots)\n")
 
 
 def write_sentences(a, b, seq, kind, rate):
@@ -214,6 +230,28 @@ def write_sentences(a, b, seq, kind, rate):
             (int(f["channel"]), int(f["end_bit"]) | ((int(f["flags"]) >> 1 & 31) << 32), int(f["nbits"]))
             for f in frames[(frames["flags"] & FRAME_REPAIRED) != 0]]
     sys.stdout.write(out.decode("ascii", "replace"))
+
+
+def write_long(a, b, seq, kind, rate):
+    """--long: the sentences of the long frames closed since the last call, behind that call's other sentences; with
+    --times each carries the TAG block of nmea_tagged_from_frames(): "\\c:<unix>*hh\\", from the record's own t"""
+    if not a.long:
+        return
+    from gnuais_amd.receiver import nmea_from_long_frames
+    frames = b.drain_long_frames()
+    a.long_frames = getattr(a, "long_frames", 0) + len(frames)
+    num, den, off = b.time_map_ratio(kind) if a.times else (1, 1, 0)
+    for i in range(len(frames)):
+        text = nmea_from_long_frames(frames[i:i + 1], seq).decode("ascii", "replace")
+        t = int(frames[i]["t"])
+        if a.times and t >= 0:
+            body = f"c:{a.start + (t * num + off) // (rate * den)}"
+            chk = 0
+            for ch in body.encode():
+                chk ^= ch
+            tag = f"\\{body}*{chk:02X}\\"
+            text = "".join(tag + line + "\r\n" for line in text.split("\r\n")[:-1])
+        sys.stdout.write(text)
 
 
 def write_heard(a, b, seq, kind, rate):
@@ -319,10 +357,13 @@ def decode_wideband(a, rate, x, fmt=None):
         b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
+    if a.long:
+        b.long_frames(True)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
         write_sentences(a, b, seq, "wideband", rate)
+        write_long(a, b, seq, "wideband", rate)
         occupancy_report(a, b)
     c = b.counters()
     sys.stderr.write(f"{int(c['receivedframes'].sum())} frames, {int(c['lostframes'].sum())} CRC errors, "
