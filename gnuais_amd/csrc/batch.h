@@ -236,13 +236,24 @@ struct gnuais_batch {
     // Messages of three to five slots (gnuais_batch_long_frames, hdlc_long.hip; off by default): while it is on, one more
     // launch behind each K3 runs the second decoder D' over the call's bit packs and appends its frames to a ring of its
     // own (a batch with the feature on does not stream).  Everything is allocated when the feature is first switched on:
-    // D''s machine [LONG_CTL_WORDS][N], the open record [LONG_REC_WORDS][N], its two counters [2][N], the ring of
-    // long_cap records and its two words (frames appended, overflow flag).
+    // D''s machine [LONG_CTL_WORDS][N], the open record [LONG_REC_WORDS][N], its counters [3][N] (delivered, failed,
+    // repaired), the ring of long_cap records and its two words (frames appended, overflow flag).
     bool long_frames = false;
     int long_cap = 0;
     Buf<uint32_t> long_ctl, long_open, long_count;
     Buf<int32_t> long_counters;
     Buf<gnuais_long_frame> long_ring;
+    // The repair of the long frames D' counts in `failed` (gnuais_batch_long_repair, hdlc_long_repair.hip; off by default,
+    // only with long_frames): while it is on, D' runs in its form that keeps the raw bits -- it unstuffs a closing frame
+    // into long_clean [LONG_REC_WORDS][N] and appends every failed one to the candidate ring long_cand
+    // [long_cand_cap][LONG_CAND_WORDS] -- and one more launch behind it repairs what the ring holds.  The ring is sized
+    // like the long ring (every close of one call fits) and consumed within the call.  long_cand_count holds two
+    // counters used by call parity: D' of a call counts in [long_parity] and clears the other, which the repair launch
+    // of the call before has read by then -- no memset command between the calls.  Allocated on first use.
+    bool long_repair = false;
+    int long_cand_cap = 0;
+    int long_parity = 0;
+    Buf<uint32_t> long_clean, long_cand, long_cand_count;
     // One record per transmission (gnuais_batch_unique, frame_unique.hip; 0 = off): the window in rows, the open
     // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
     // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the

@@ -329,6 +329,12 @@ static int long_zero_state(gnuais_batch *b, bool everything)
     if (!b->long_ctl) return GNUAIS_OK;         // never switched on: nothing exists
     HIP_TRY(launch_hdlc_long_reset(b->long_ctl, everything ? b->long_counters.p : nullptr, b->N, nullptr));
     if (everything) HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
+    // the candidate ring of gnuais_batch_long_repair is empty between calls (consumed within each); a frame in progress
+    // restarts with its record, so nothing of it needs clearing.  Both counters and the parity start over all the same.
+    if (everything && b->long_cand_count) {
+        HIP_TRY(hipMemset(b->long_cand_count, 0, sizeof(uint32_t) * 2));
+        b->long_parity = 0;
+    }
     return GNUAIS_OK;
 }
 
@@ -438,6 +444,8 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
             return fail(GNUAIS_E_STATE, "streaming: the batch measures its frames (gnuais_batch_frame_signal); the streamed delivery carries no records of them");
         if (value != 0 && b->uq_window)
             return fail(GNUAIS_E_STATE, "streaming: the batch merges duplicates (gnuais_batch_unique); the streamed delivery has no such stage");
+        if (value != 0 && b->long_repair)
+            return fail(GNUAIS_E_STATE, "streaming: the batch repairs long frames (gnuais_batch_long_repair); the streamed delivery carries no records of them");
         if (value != 0 && b->long_frames)
             return fail(GNUAIS_E_STATE, "streaming: the batch decodes long frames (gnuais_batch_long_frames); the streamed delivery carries no records of them");
         if (value != 0) return fail(GNUAIS_E_ARG, "streaming can only be switched off here (stream_nmea switches it on)");
@@ -576,7 +584,29 @@ static LongLaunch fill_long(const gnuais_batch *b, const HdlcLaunch &h, int len)
     a.frames = b->long_ring.p; a.frame_count = b->long_count; a.frame_cap = (uint32_t) b->long_cap;
     a.N = h.N; a.n_seg = h.n_seg; a.seg_words = h.seg_words;
     a.len = len; a.n0 = (int64_t) b->rows;
+    if (b->long_repair) {                       // the form that keeps the raw bits and lists the failed frames
+        a.clean = b->long_clean; a.cand = b->long_cand; a.cand_count = b->long_cand_count;
+        a.cand_cap = (uint32_t) b->long_cand_cap; a.parity = b->long_parity;
+    }
     return a;
+}
+
+// D' behind the K3 described by h and, while gnuais_batch_long_repair is on, the repair of what it counted in `failed`
+// behind it on the same stream; the next call counts its candidates in the other word
+static int run_long(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s)
+{
+    HIP_TRY(launch_hdlc_long(fill_long(b, h, len), s));
+    if (b->long_repair) {
+        LongRepairLaunch r;
+        r.cand = b->long_cand; r.cand_count = b->long_cand_count.p + b->long_parity; r.cand_cap = (uint32_t) b->long_cand_cap;
+        r.repaired = b->long_counters.p + 2 * (size_t) b->N;
+        r.frames = b->long_ring.p; r.frame_count = b->long_count; r.frame_cap = (uint32_t) b->long_cap;
+        r.N = b->N;
+        r.blocks = 16 * std::max(b->n_cu, 1);   // four waves per SIMD: fixed, the count is known on the device only
+        HIP_TRY(launch_hdlc_long_repair(r, s));
+        b->long_parity ^= 1;
+    }
+    return GNUAIS_OK;
 }
 
 // K1 + carry: the kernel and its thresholds are plan_fir()'s choice (fir_plan.cpp).  The specialised kernels update
@@ -672,7 +702,8 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     // messages of three to five slots: D' over this call's packs, behind the deframer that moved the bit count it reads
     // and in front of e_done[4][k], which is what the reuse of set k (segbits, segcnt) and, where K3 has a stream of its
     // own, the next deframer launch (ctl) wait for (hdlc_long.hip)
-    if (b->long_frames && (b->stage_mask & 8)) HIP_TRY(launch_hdlc_long(fill_long(b, h, len), sD));
+    if (b->long_frames && (b->stage_mask & 8))
+        if (int rc = run_long(b, h, len, sD)) return rc;
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -912,7 +943,8 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         if (b->repair) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), nullptr));
         if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1
         if (b->frame_signal) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, 0), nullptr));   // and (0, 0, 0)
-        if (b->long_frames) HIP_TRY(launch_hdlc_long(fill_long(b, h, 0), nullptr));                // D' on the same packs: t = -1
+        if (b->long_frames)                                                                        // D' on the same packs: t = -1
+            if (int rc = run_long(b, h, 0, nullptr)) return rc;
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
@@ -1128,6 +1160,8 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "repair")) *value = b->repair;
     else if (!strcmp(name, "long_frames")) *value = b->long_frames;
     else if (!strcmp(name, "long_frame_cap")) *value = b->long_cap ? b->long_cap : long_ring_capacity(b);
+    else if (!strcmp(name, "long_repair")) *value = b->long_repair;
+    else if (!strcmp(name, "long_cand_cap")) *value = b->long_cand_cap ? b->long_cand_cap : long_ring_capacity(b);
     else if (!strcmp(name, "unique")) *value = b->uq_window;
     else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
@@ -1178,7 +1212,7 @@ int gnuais_batch_long_frames(gnuais_batch *b, int on)
         const size_t N = (size_t) b->N;
         b->long_cap = long_ring_capacity(b);
         HIP_TRY(b->long_open.ensure(sizeof(uint32_t) * N * LONG_REC_WORDS, true));
-        HIP_TRY(b->long_counters.ensure(sizeof(int32_t) * N * 2, true));
+        HIP_TRY(b->long_counters.ensure(sizeof(int32_t) * N * 3, true));
         HIP_TRY(b->long_count.ensure(sizeof(uint32_t) * 2, true));
         HIP_TRY(b->long_ring.ensure(sizeof(gnuais_long_frame) * (size_t) b->long_cap));
         HIP_TRY(b->long_ctl.ensure(sizeof(uint32_t) * N * LONG_CTL_WORDS, true));    // last: long_zero_state() goes by it
@@ -1186,6 +1220,47 @@ int gnuais_batch_long_frames(gnuais_batch *b, int on)
     if (int rc = long_zero_state(b, true)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     b->long_frames = on != 0;
+    if (!on) b->long_repair = false;            // gnuais_batch_long_repair: nothing to repair without D'
+    return GNUAIS_OK;
+}
+
+// The repair of the long frames D' counts in `failed`, on / off (definition in include/gnuais_hip.h).  Synchronises: no
+// call is in flight when the switch turns, so every D' launch is of the form the switch says and either has its repair
+// launch behind it or has not.  D' itself is not reset: a frame in progress keeps its raw bits in `open` in either form.
+// The candidate ring holds what one call's D' can close -- the long ring's own bound (long_ring_capacity) -- and the
+// repair launch of the same call consumes it, so it cannot overflow across calls.
+int gnuais_batch_long_repair(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "long_repair: NULL batch");
+    if (b->streaming) return fail(GNUAIS_E_STATE, "long_repair: the batch is streaming (gnuais_batch_stream_nmea); "
+                                                  "set_option(\"streaming\", 0) leaves that mode");
+    if (!b->long_frames)
+        return fail(GNUAIS_E_STATE, "long_repair: the batch does not decode long frames (gnuais_batch_long_frames): "
+                                    "the repair works on what that decoder counts as failed");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (on && !b->long_cand) {
+        const size_t N = (size_t) b->N;
+        b->long_cand_cap = b->long_cap;
+        HIP_TRY(b->long_clean.ensure(sizeof(uint32_t) * N * LONG_REC_WORDS, true));
+        HIP_TRY(b->long_cand_count.ensure(sizeof(uint32_t) * 2, true));
+        HIP_TRY(b->long_cand.ensure(sizeof(uint32_t) * (size_t) b->long_cand_cap * LONG_CAND_WORDS));
+    }
+    if (on) {
+        HIP_TRY(hipMemset(b->long_cand_count, 0, sizeof(uint32_t) * 2));
+        b->long_parity = 0;
+    }
+    b->long_repair = on != 0;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_long_repaired(gnuais_batch *b, int32_t *h_out)
+{
+    if (!b || !h_out) return fail(GNUAIS_E_ARG, "long_repaired: argument");
+    if (!b->long_ctl) return fail(GNUAIS_E_STATE, "long_repaired: the batch has never decoded long frames (gnuais_batch_long_frames)");
+    std::vector<int32_t> v;
+    if (int rc = read_out(b, b->long_counters, (size_t) b->N * 3, v)) return rc;
+    memcpy(h_out, v.data() + 2 * (size_t) b->N, sizeof(int32_t) * (size_t) b->N);
     return GNUAIS_OK;
 }
 

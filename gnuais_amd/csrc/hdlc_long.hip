@@ -25,6 +25,8 @@
 // over n/8 + 2 bytes of it, and appends the 152-byte record to the long ring through one atomic.  The other lanes of
 // its wave wait for that -- a few microseconds where a long frame exists, nothing where none does -- which was chosen
 // over a compact list and a second launch: one launch less in every call, and no list to size.
+// While the repair of long frames is on (gnuais_batch_long_repair) the kernel runs in a second compile-time form that
+// unstuffs into a record beside the open one and lists the frames whose CRC fails with their raw bits; see the kernel.
 // The receive time needs nothing from outside either: the lane knows the segment s, the slice j, the segment's rows
 // l_s and its bit count c_s of the closing bit.
 #include <hip/hip_runtime.h>
@@ -58,7 +60,7 @@ __device__ __forceinline__ int l_clz32(uint32_t v)      // 32 for v == 0
 
 } // namespace
 
-// everything of D' back to protodec_reset()'s state (protodec.c:87-100); counters: also the two counters
+// everything of D' back to protodec_reset()'s state (protodec.c:87-100); counters: also the three counters
 __global__ void hdlc_long_reset_kernel(uint32_t *__restrict__ lctl, int32_t *__restrict__ counters, int N)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -69,16 +71,28 @@ __global__ void hdlc_long_reset_kernel(uint32_t *__restrict__ lctl, int32_t *__r
     if (counters) {
         counters[c] = 0;
         counters[(size_t) N + c] = 0;
+        counters[(size_t) 2 * N + c] = 0;
     }
 }
 
 extern __shared__ uint32_t long_pack[];                     // [LPACK_MAX + 1][blockDim.x]
 
+// The kernel in its two compile-time forms.  KEEP_RAW = false is D' as gnuais_batch_long_frames defines it and is what
+// runs while the repair of long frames is off: its last five arguments are not read.  KEEP_RAW = true (gnuais_batch_long_repair) keeps what that form destroys:
+// the unstuffed bits go to a second per-channel record, `clean`, so `open` still holds the raw bits when the CRC fails,
+// and the lane then appends one candidate record (kernels.h: LONG_CAND_*) to the candidate ring through one atomic on
+// cand_count[parity].  It also clears cand_count[parity ^ 1], the counter of the NEXT call: the two are used by call
+// parity, and the repair launch that read the other one ran in front of this launch.
+template <bool KEEP_RAW = false>
 __global__ __launch_bounds__(64) void hdlc_long_kernel(
     const uint32_t *__restrict__ segbits, const uint32_t *__restrict__ segcnt, const uint32_t *__restrict__ ctl,
     uint32_t *__restrict__ lctl, uint32_t *open, int32_t *__restrict__ counters, uint32_t *__restrict__ frames,
-    uint32_t *__restrict__ frame_count, uint32_t frame_cap, int N, int n_seg, int seg_words, int len, long long n0)
+    uint32_t *__restrict__ frame_count, uint32_t frame_cap, int N, int n_seg, int seg_words, int len, long long n0,
+    uint32_t *clean = nullptr, uint32_t *__restrict__ cand = nullptr, uint32_t *cand_count = nullptr,
+    uint32_t cand_cap = 0, int parity = 0)
 {
+    uint32_t *const urec = KEEP_RAW ? clean : open;             // where the unstuffed bits of a closing frame go
+    if (KEEP_RAW && blockIdx.x == 0 && threadIdx.x == 0) cand_count[parity ^ 1] = 0;
     const int cg = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = cg < N;
     const size_t c = (size_t) (live ? cg : N - 1), n_ = (size_t) N;
@@ -207,20 +221,20 @@ __global__ __launch_bounds__(64) void hdlc_long_kernel(
                                     acc |= (unsigned long long) rw << fill;
                                     fill += nout;
                                     if (fill >= 32) {           // ow <= q: behind the word just read
-                                        open[(size_t) ow * n_ + c] = (uint32_t) acc;
+                                        urec[(size_t) ow * n_ + c] = (uint32_t) acc;
                                         ++ow;
                                         acc >>= 32;
                                         fill -= 32;
                                     }
                                 }
-                                if (ow < LONG_REC_WORDS) open[(size_t) ow * n_ + c] = (uint32_t) acc;
+                                if (ow < LONG_REC_WORDS) urec[(size_t) ow * n_ + c] = (uint32_t) acc;
                             }
                             // protodec_calculate_crc(nb): protodec_sdlc_crc() over nb/8 + 2 bytes, bits LSB first
                             const int nbytes = nb >> 3, buflen = nbytes + 2;
                             uint32_t crc = 0xffffu;
 #pragma unroll 1
                             for (int q = 0; q * 4 < buflen; ++q) {
-                                const uint32_t w = open[(size_t) q * n_ + c];
+                                const uint32_t w = urec[(size_t) q * n_ + c];
                                 const int nby = buflen - q * 4 < 4 ? buflen - q * 4 : 4;
 #pragma unroll 1
                                 for (int bq = 0; bq < nby; ++bq) {
@@ -229,17 +243,20 @@ __global__ __launch_bounds__(64) void hdlc_long_kernel(
                                     for (int i = 0; i < 8; ++i) crc = (crc >> 1) ^ ((crc & 1u) ? 0x8408u : 0u);
                                 }
                             }
+                            // the stamp: bits fed before the closing bit, as the chain's deframer counts them; the time:
+                            // -1 for bits without samples (gnuais_batch_decode_bits)
+#define LONG_STAMP_AND_TIME()                                                                                           \
+                                    const unsigned long long eb = seenbase + (unsigned long long) pos;                  \
+                                    long long t = -1;                                                                   \
+                                    if (len > 0) {                                                                      \
+                                        const long long ls = len - seg * SEG_LEN < SEG_LEN ? len - seg * SEG_LEN : SEG_LEN; \
+                                        t = n0 + (long long) seg * SEG_LEN + ((2 * (long long) pos + 1) * ls) / (2 * (long long) tile_end); \
+                                    }
                             if (crc == 0xf0b8u) {               // ~crc == 0x0f47, protodec.c:166
                                 ++delivered;
                                 const uint32_t slot = atomicAdd(&frame_count[0], 1u);
                                 if (slot < frame_cap) {
-                                    // the stamp: bits fed before the closing bit, as the chain's deframer counts them
-                                    const unsigned long long eb = seenbase + (unsigned long long) pos;
-                                    long long t = -1;           // bits without samples (gnuais_batch_decode_bits)
-                                    if (len > 0) {
-                                        const long long ls = len - seg * SEG_LEN < SEG_LEN ? len - seg * SEG_LEN : SEG_LEN;
-                                        t = n0 + (long long) seg * SEG_LEN + ((2 * (long long) pos + 1) * ls) / (2 * (long long) tile_end);
-                                    }
+                                    LONG_STAMP_AND_TIME()
                                     uint32_t *dst = frames + (size_t) slot * LONG_FRAME_WORDS;
                                     dst[0] = (uint32_t) c;
                                     dst[1] = (uint32_t) eb;
@@ -250,7 +267,7 @@ __global__ __launch_bounds__(64) void hdlc_long_kernel(
                                     for (int q = 0; q < LONG_FRAME_WORDS - 5; ++q) {
                                         uint32_t v = 0;
                                         if (q * 4 < nbytes) {
-                                            v = open[(size_t) q * n_ + c];
+                                            v = urec[(size_t) q * n_ + c];
                                             const int keep = nbytes - q * 4;
                                             if (keep < 4) v &= (1u << (8 * keep)) - 1u;
                                         }
@@ -261,7 +278,25 @@ __global__ __launch_bounds__(64) void hdlc_long_kernel(
                                 }
                             } else {
                                 ++failed;
+                                if (KEEP_RAW) {                 // a candidate of the repair: the record as it was received
+                                    const uint32_t slot = atomicAdd(&cand_count[parity], 1u);
+                                    if (slot < cand_cap) {      // sized so that every close of one call fits
+                                        LONG_STAMP_AND_TIME()
+                                        uint32_t *dst = cand + (size_t) slot * LONG_CAND_WORDS;
+                                        dst[0] = (uint32_t) c;
+                                        dst[1] = (uint32_t) eb;
+                                        dst[2] = (uint32_t) (unsigned long long) t;
+                                        dst[3] = (uint32_t) ((unsigned long long) t >> 32);
+                                        dst[4] = (uint32_t) nb | (((uint32_t) (eb >> 32) & 31u) << 16);
+                                        dst[5] = (uint32_t) rawpos;
+                                        const int nwords = (rawpos + 31) >> 5 < LONG_REC_WORDS ? (rawpos + 31) >> 5 : LONG_REC_WORDS;
+#pragma unroll 1
+                                        for (int q = 0; q < LONG_REC_WORDS; ++q)
+                                            dst[LONG_CAND_HDR + q] = q < nwords ? open[(size_t) q * n_ + c] : 0u;
+                                    }
+                                }
                             }
+#undef LONG_STAMP_AND_TIME
                         }
                         // nb <= 426, a stop bit of 1, nb <= 0: the chain's decoder's business; D' says nothing
                         LONG_RESET();
@@ -422,9 +457,18 @@ hipError_t launch_hdlc_long(const LongLaunch &a, hipStream_t stream)
     if (!a.segbits || !a.segcnt || !a.ctl || !a.lctl || !a.open || !a.counters || !a.frames || !a.frame_count ||
         a.N <= 0 || a.n_seg <= 0 || a.seg_words <= 0 || a.seg_words > LPACK_MAX || a.len > a.n_seg * SEG_LEN)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hdlc_long_kernel, dim3((a.N + 63) / 64), dim3(64), (LPACK_MAX + 1) * 64 * sizeof(uint32_t), stream,
+    if (a.clean) {                              // the repair of long frames is on: the form that keeps the raw bits
+        if (!a.cand || !a.cand_count || a.cand_cap == 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdlc_long_kernel<true>, dim3((a.N + 63) / 64), dim3(64), (LPACK_MAX + 1) * 64 * sizeof(uint32_t),
+                           stream, a.segbits, a.segcnt, a.ctl, a.lctl, a.open, a.counters, (uint32_t *) a.frames,
+                           a.frame_count, a.frame_cap, a.N, a.n_seg, a.seg_words, a.len, (long long) a.n0, a.clean, a.cand,
+                           a.cand_count, a.cand_cap, a.parity);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(hdlc_long_kernel<false>, dim3((a.N + 63) / 64), dim3(64), (LPACK_MAX + 1) * 64 * sizeof(uint32_t), stream,
                        a.segbits, a.segcnt, a.ctl, a.lctl, a.open, a.counters, (uint32_t *) a.frames, a.frame_count,
-                       a.frame_cap, a.N, a.n_seg, a.seg_words, a.len, (long long) a.n0);
+                       a.frame_cap, a.N, a.n_seg, a.seg_words, a.len, (long long) a.n0, (uint32_t *) nullptr,
+                       (uint32_t *) nullptr, (uint32_t *) nullptr, 0u, 0);
     return hipGetLastError();
 }
 

@@ -12,6 +12,10 @@
 //   * bufferpos = rawlen - (stuffed 0s), and it must stay below 449.
 // trial_shape() decides all that and gives n'; trial_crc() is K3's CRC over n'/8 + 2 bytes of the unstuffed bits, and
 // hands out the payload bytes when asked to.
+//
+// The repair of long frames (gnuais_batch_long_repair: hdlc_long_repair.hip, hdlc_long_repair.cpp) is the same trial over
+// D''s record with D''s numbers, so the four numbers are a parameter of the text, `Limits`: the raw words of a record,
+// the most stored bits, the most CRC bytes and the smallest n'.  The default, ShortLimits, is the chain's.
 #pragma once
 #include <stdint.h>
 
@@ -24,10 +28,22 @@
 namespace gnuais {
 namespace repair {
 
-constexpr int RAW_WORDS = 18;               // CAND_WORDS - CAND_HDR (kernels.h): the raw words of a candidate record
-constexpr int RAW_BITS = RAW_WORDS * 32;    // the record's limit
-constexpr int MAX_STORED = 448;             // bufferpos >= 449 gives the frame up (protodec.c:1024)
-constexpr int MAX_CRC_BYTES = 60;           // K3 reads no further (HDLC_BUF_WORDS words)
+struct ShortLimits {
+    static constexpr int RAW_WORDS = 18;        // CAND_WORDS - CAND_HDR (kernels.h): the raw words of a candidate record
+    static constexpr int RAW_BITS = RAW_WORDS * 32;     // the record's limit
+    static constexpr int MAX_STORED = 448;      // bufferpos >= 449 gives the frame up (protodec.c:1024)
+    static constexpr int MAX_CRC_BYTES = 60;    // K3 reads no further (HDLC_BUF_WORDS words)
+    static constexpr int MIN_BITS = 1;          // n' > 0
+};
+struct LongLimits {
+    static constexpr int RAW_WORDS = 40;        // LONG_REC_WORDS (kernels.h): D''s open record
+    static constexpr int RAW_BITS = RAW_WORDS * 32;
+    static constexpr int MAX_STORED = 1030;     // D' gives the frame up at 1031 stored bits; n' <= 1008 says the same
+    static constexpr int MAX_CRC_BYTES = 128;   // 1008 / 8 + 2
+    static constexpr int MIN_BITS = 427;        // n' > 426: at most 426 bits are the chain's decoder's
+};
+constexpr int RAW_WORDS = ShortLimits::RAW_WORDS, RAW_BITS = ShortLimits::RAW_BITS;
+constexpr int MAX_STORED = ShortLimits::MAX_STORED, MAX_CRC_BYTES = ShortLimits::MAX_CRC_BYTES;
 constexpr uint32_t CRC_GOOD = 0xf0b8u;      // ~crc == 0x0f47 (protodec.c:166)
 constexpr uint32_t POLY = 0x8408u;          // protodec.c:113
 
@@ -64,10 +80,11 @@ REPAIR_HD uint32_t five_below(uint32_t w, uint32_t prevw)
 
 REPAIR_HD uint32_t low_bits(int k) { return k >= 32 ? ~0u : (1u << k) - 1u; }     // k in [0, 32]
 
-// n' of trial p when it is well formed (> 0, a multiple of 8), else -1.  0 < rawlen <= RAW_BITS.
+// n' of trial p when it is well formed (>= MIN_BITS, a multiple of 8), else -1.  0 < rawlen <= RAW_BITS.
+template <class Limits = ShortLimits>
 REPAIR_HD int trial_shape(const uint32_t *raw, int rawlen, int p)
 {
-    if (rawlen < 5 || rawlen > RAW_BITS) return -1;
+    if (rawlen < 5 || rawlen > Limits::RAW_BITS) return -1;
     const int nwords = (rawlen + 31) >> 5;
     uint32_t prevw = 0, w = 0, before = 0;
     int stuffed = 0;
@@ -85,19 +102,20 @@ REPAIR_HD int trial_shape(const uint32_t *raw, int rawlen, int p)
     const unsigned long long cc = ((unsigned long long) w << 32) | before;
     if (((cc >> (27 + e)) & 31ull) != 31ull) return -1;
     const int stored = rawlen - stuffed;            // bufferpos at the stop
-    if (stored > MAX_STORED) return -1;
+    if (stored > Limits::MAX_STORED) return -1;
     const int n = stored - 6 - 16;                  // protodec.c:1096
-    if (n <= 0 || (n & 7)) return -1;
+    if (n < Limits::MIN_BITS || (n & 7)) return -1;
     return n;
 }
 
 // K3's CRC of trial p over `buflen` bytes of the unstuffed bits (packed LSB first, protodec.c:138-143; zeros behind
 // the last bit), before the final complement; the first n_out of those bytes go to out[] (n_out = 0: none).  The
 // caller has made sure that r' holds no run of six 1s (trial_shape, or a record the deframer closed).
+template <class Limits = ShortLimits>
 REPAIR_HD uint32_t trial_crc(const uint32_t *raw, int rawlen, int p, int buflen, const uint16_t *tab, uint8_t *out,
                              int n_out)
 {
-    if (buflen > MAX_CRC_BYTES) buflen = MAX_CRC_BYTES;
+    if (buflen > Limits::MAX_CRC_BYTES) buflen = Limits::MAX_CRC_BYTES;
     const int nwords = (rawlen + 31) >> 5;
     unsigned long long acc = 0;
     uint32_t prevw = 0, crc = 0xffffu;
@@ -136,12 +154,13 @@ REPAIR_HD uint32_t trial_crc(const uint32_t *raw, int rawlen, int p, int buflen,
 }
 
 // trial p passes: well formed and the CRC holds; *n = n'
+template <class Limits = ShortLimits>
 REPAIR_HD bool trial_passes(const uint32_t *raw, int rawlen, int p, const uint16_t *tab, int *n)
 {
-    const int n1 = trial_shape(raw, rawlen, p);
+    const int n1 = trial_shape<Limits>(raw, rawlen, p);
     if (n1 <= 0) return false;
     *n = n1;
-    return trial_crc(raw, rawlen, p, (n1 >> 3) + 2, tab, nullptr, 0) == CRC_GOOD;
+    return trial_crc<Limits>(raw, rawlen, p, (n1 >> 3) + 2, tab, nullptr, 0) == CRC_GOOD;
 }
 
 } // namespace repair

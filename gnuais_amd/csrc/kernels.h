@@ -338,10 +338,38 @@ struct LongLaunch {
     int N, n_seg, seg_words;
     int len;                       // rows of the call (<= 0: bits without samples, t = -1)
     int64_t n0;                    // rows the chain had taken before it
+    // the repair of long frames (below): all null / 0 while it is off, and the launch is then the kernel without it
+    uint32_t *clean = nullptr;     // [LONG_REC_WORDS][N]: where a closing frame is unstuffed, so that `open` stays raw
+    uint32_t *cand = nullptr;      // [cand_cap][LONG_CAND_WORDS]: the call's candidate ring
+    uint32_t *cand_count = nullptr;    // [2]: [parity] this call's count (zero at the launch), the other the next call's, cleared here
+    uint32_t cand_cap = 0;
+    int parity = 0;
 };
 hipError_t launch_hdlc_long(const LongLaunch &a, hipStream_t stream);
-// protodec_reset() for D' (counters: also its two counters, else null)
+// protodec_reset() for D' (counters: also its three counters [3][N] -- delivered, failed, repaired -- else null)
 hipError_t launch_hdlc_long_reset(uint32_t *lctl, int32_t *counters, int N, hipStream_t stream);
+
+// ---- repair of the long frames D' counted in `failed` (hdlc_long_repair.hip; definition in include/gnuais_hip.h) ----
+// One launch behind D''s of the same call, on its stream.  D' (in its form that keeps the raw bits) appended one record
+// per failed frame to the candidate ring; this launch reads the count D' left, tries every pair flip of every record
+// (the trial is hdlc_repair.h's with LongLimits) and appends the frames with exactly one passing trial to the long ring
+// through frame_count[0] (overflow: frame_count[1]), counting them in repaired[channel].
+// A candidate record: [0] channel, [1] stamp bits 31:0, [2] [3] t, [4] n | stamp bits 36:32 << 16, [5] rawlen, then the
+// LONG_REC_WORDS raw words (zero behind rawlen).
+constexpr int LONG_CAND_HDR = 6;
+constexpr int LONG_CAND_WORDS = LONG_CAND_HDR + LONG_REC_WORDS;
+struct LongRepairLaunch {
+    const uint32_t *cand;          // as in LongLaunch, of the D' launch it follows
+    const uint32_t *cand_count;    // the word that launch counted in: its cand_count + parity
+    uint32_t cand_cap;
+    int32_t *repaired;             // [N]
+    void *frames;                  // gnuais_long_frame[frame_cap]
+    uint32_t *frame_count;
+    uint32_t frame_cap;
+    int N;
+    int blocks;                    // the fixed grid: workgroups of one wave, candidate i is taken by workgroup i mod blocks
+};
+hipError_t launch_hdlc_long_repair(const LongRepairLaunch &a, hipStream_t stream);
 
 // ---- one record per transmission: the duplicate merge of a drain (frame_unique.hip; definition in include/gnuais_hip.h) ----
 // Entries = [tail | ring]: n_tail open clusters of earlier drains (16 words each: t_last, then the key as a record

@@ -593,6 +593,19 @@ int gnuais_node_long_counters(gnuais_node *nd, int32_t *h_delivered, int32_t *h_
     return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_long_counters(s.b, h_delivered + s.first, h_failed + s.first); });
 }
 
+// the repair of long frames (gnuais_batch_long_repair on every shard) and the repairs per global channel
+int gnuais_node_long_repair(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_long_repair: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_long_repair(s.b, on); });
+}
+
+int gnuais_node_long_repaired(gnuais_node *nd, int32_t *h_out)
+{
+    if (!nd || !h_out) return node_fail(GNUAIS_E_ARG, "node_long_repaired: argument");
+    return run_all(nd, [&](Shard &s, size_t) { return gnuais_batch_long_repaired(s.b, h_out + s.first); });
+}
+
 // every shard drains its own long ring; a shard's records come in (channel, stamp) order with LOCAL channel numbers and
 // the shards own ascending channel blocks, so the parts are renumbered and laid end to end
 int gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out)

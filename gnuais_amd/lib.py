@@ -118,6 +118,9 @@ SYMBOLS = {
     "gnuais_batch_long_counters": (_I, [_P, _P, _P]),
     "gnuais_batch_long_fsm_state": (_I, [_P, _P]),
     "gnuais_nmea_from_long_frames": (_I, [_P, _I, _P, _I, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I)]),
+    "gnuais_batch_long_repair": (_I, [_P, _I]),
+    "gnuais_batch_long_repaired": (_I, [_P, _P]),
+    "gnuais_long_repair_candidate": (_I, [_P, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_batch_unique": (_I, [_P, _I]),
     "gnuais_batch_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -196,6 +199,8 @@ SYMBOLS = {
     "gnuais_node_long_frames": (_I, [_P, _I]),
     "gnuais_node_drain_long_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_long_counters": (_I, [_P, _P, _P]),
+    "gnuais_node_long_repair": (_I, [_P, _I]),
+    "gnuais_node_long_repaired": (_I, [_P, _P]),
     "gnuais_node_unique": (_I, [_P, _I]),
     "gnuais_node_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),

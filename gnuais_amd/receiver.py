@@ -402,6 +402,18 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_long_counters(self._h, d.ctypes.data, f.ctypes.data))
         return d, f
 
+    def long_repair(self, on: bool = True):
+        """gnuais_batch_long_repair(): from now on a long frame that fails the CRC by one symbol error (two adjacent
+        bits) is repaired on the device and delivered with flags bit 6 set (the definition is in include/gnuais_hip.h).
+        Needs long_frames() on; switching that off switches this off."""
+        check(self._lib.gnuais_batch_long_repair(self._h, int(bool(on))))
+
+    def long_repaired(self) -> np.ndarray:
+        """gnuais_batch_long_repaired(): int32 [n_channels], the long frames repaired per channel"""
+        out = np.zeros(self.n_channels, dtype=np.int32)
+        check(self._lib.gnuais_batch_long_repaired(self._h, out.ctypes.data))
+        return out
+
     def long_fsm_state(self) -> np.ndarray:
         """gnuais_batch_long_fsm_state(): the second decoder's live fields, as fsm_state()"""
         return self._struct_array(self._lib.gnuais_batch_long_fsm_state, FSM_DTYPE)

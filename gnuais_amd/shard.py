@@ -252,6 +252,16 @@ class ReceiverNode:
         self._raise(self._lib.gnuais_node_long_counters(self._h, d.ctypes.data, f.ctypes.data))
         return d, f
 
+    def long_repair(self, on: bool = True):
+        """gnuais_batch_long_repair() on every shard"""
+        self._raise(self._lib.gnuais_node_long_repair(self._h, int(bool(on))))
+
+    def long_repaired(self):
+        """gnuais_node_long_repaired(): int32 [n_channels], the long frames repaired per global channel"""
+        out = self._np.zeros(self.n_channels, dtype=self._np.int32)
+        self._raise(self._lib.gnuais_node_long_repaired(self._h, out.ctypes.data))
+        return out
+
     def drain_frames_timed(self):
         """gnuais_node_drain_frames_timed(): (frames, int64 times), as drain_frames with every record's receive time"""
         from .lib import FRAME_DTYPE

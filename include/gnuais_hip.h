@@ -389,7 +389,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * gnuais_batch_stream_nmea() call and the one that hands its text out), "afc_window" (gnuais_batch_afc(); 0 = off),
  * "frame_times" (gnuais_batch_frame_times(); 0 = off), "rows" (rows the chain has taken since create / reset),
  * "frame_signal" (gnuais_batch_frame_signal(); 0 = off), "occupancy" (gnuais_batch_occupancy(); epoch_blocks, 0 = off),
- * "repair" (gnuais_batch_repair(); 0 = off), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
+ * "repair" (gnuais_batch_repair(); 0 = off), "long_repair" (gnuais_batch_long_repair(); 0 = off), "long_cand_cap" (the
+ * candidate records one call of that repair can list), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
  * (gnuais_batch_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
  * one, 8 the lane-per-channel one; 0 before any call and after a reset) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
@@ -687,7 +688,7 @@ int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload
  *     l_s / (2 c_s)): D''s kernel walks a call's segments in order and knows s, j, l_s and c_s of the closing bit itself,
  *     so t is filled in whether gnuais_batch_frame_times is on or off.  t = -1 for a frame closed by
  *     gnuais_batch_decode_bits.
- *   Not in this section.  For long frames there is no repair (gnuais_batch_repair), no duplicate merge and no member
+ *   Not in this section.  For long frames there is no duplicate merge and no member
  *     lists (gnuais_batch_unique), no signal record and no share in the channel load (gnuais_batch_frame_signal,
  *     gnuais_batch_occupancy), no stdout text line, no device formatter (gnuais_batch_drain_nmea and its family), no
  *     entry in the vessel tables and no streamed delivery.  t and the stamp are in the record, so a host can do these
@@ -724,6 +725,52 @@ int  gnuais_batch_long_counters(gnuais_batch *b, int32_t *h_delivered /* [n_chan
 int  gnuais_batch_long_fsm_state(gnuais_batch *b, gnuais_fsm_state *h_out /* [n_channels] */);
 int  gnuais_nmea_from_long_frames(const gnuais_long_frame *frames, int n_frames, uint8_t *seqnr, int n_channels,
                                   char *out, size_t out_cap, size_t *out_len, int *n_sentences);
+
+/* ---- repair of long frames that fail the CRC by one symbol error -------------------------------------------------------
+ * A 1008-bit frame carries about five times the symbols of a position report, so at the same symbol error rate it fails
+ * its CRC about five times as often; D' counts such a frame in `failed` and drops it.  With this repair on, the frame is
+ * looked for among the pair-flip neighbours of what was received, as gnuais_batch_repair does for the chain's frames (one
+ * wrong level decision is two adjacent wrong bits behind the NRZI decoder).  The section mirrors that one statement by
+ * statement, with D''s numbers.  Off by default: while off, a call launches exactly what it launches without this
+ * section, and no result of the sections above changes.  gnuais_batch_repair keeps its meaning: the chain's frames only.
+ *   Candidate.  A frame that D' counts in `failed`: it reached ST_STOPSIGN's good branch (stop bit 0) with
+ *     n = bufferpos - 22 > 426 and its CRC is wrong; n need not be a multiple of 8.  Its raw bits are r[0 .. rawlen): the
+ *     bits D' saw in ST_DATA, stuffed zeros included, up to and including the fifth 1 of the closing flag; the sixth 1 is
+ *     not among them.  rawlen <= 1236: 1030 stored bits and at most 206 stuffed zeros, 40 words.
+ *   Trial p, 0 <= p <= rawlen - 2: r' = r with bits p and p + 1 inverted; ST_DATA of D' (from antallenner = 0,
+ *     bitstuff = 0, last = 0, bufferpos = 0) runs over r', followed by one more bit of value 1.
+ *   A trial is well formed when that appended bit, and no bit before it, takes the machine to ST_STOPSIGN; bufferpos
+ *     never reaches 1031; and n' = bufferpos - 22 satisfies 426 < n' <= 1008 and n' mod 8 = 0.
+ *   A trial passes when it is well formed and the reference's CRC over n'/8 + 2 bytes of its buffer holds.
+ *   Outcome.  The candidate is repaired iff exactly one trial passes; with none or with several it stays lost.
+ *     Single-bit flips and two or more symbol errors are not tried.
+ *   Record.  The repaired frame is a gnuais_long_frame in the long ring: the candidate's channel, stamp (end_bit and
+ *     flags[5:1]) and t; nbits = n'; the payload of r'; flags bit 0 and bit 6 (GNUAIS_FRAME_REPAIRED) set.  It shares the
+ *     ring's capacity and overflow report, drains in (channel, stamp) order with the others, and
+ *     gnuais_nmea_from_long_frames takes it as it takes any record: a consumer that wants received frames only tests bit 6.
+ *   Counters.  D''s two counters do not move: the frame stays counted in `failed`.  A third per-channel int32 counter,
+ *     long_repaired, counts the repairs, with the reset rules of the other two: gnuais_batch_reset() and a switch of
+ *     gnuais_batch_long_frames zero it, gnuais_batch_protodec_reset() keeps it.  Switching the repair itself leaves it.
+ *   False repairs.  A frame with more than one symbol error is accepted wrongly with probability about trials / 65536,
+ *     at most 1235 / 65536, about 1.9 per cent for the longest frame; no message-type plausibility check is made.
+ *   Against the chain's repair.  n' > 426 keeps the two disjoint.  A 424-bit frame whose error destroyed stuffed zeros can
+ *     be a candidate here with n = 427 or more; its only passing trial gives n' = 424, which is not delivered here: the
+ *     chain's repair owns it.  A 432-bit frame whose error made a stuffed zero has n = 431; the chain gave it up at 449
+ *     stored bits, and it is repaired here.
+ * gnuais_batch_long_repair(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE unless
+ *   gnuais_batch_long_frames is on, and on a streaming batch; switching long frames off switches it off.  While it is on
+ *   D' runs in a form that keeps the raw bits of a closing frame and lists the failed ones, and one more launch follows
+ *   D''s (also behind every chunk of gnuais_batch_decode_bits).  info "long_repair" and "long_cand_cap": the switch, and
+ *   the records the candidate list of one call holds (sized like the long ring; consumed within the call).
+ * gnuais_batch_long_repaired(): h_out[c] = long frames repaired on channel c.  Synchronises.  GNUAIS_E_STATE on a batch
+ *   that never decoded long frames.
+ * gnuais_long_repair_candidate(): the same repair of one candidate on the host, from its raw bits (one per byte, bit 0
+ *   counts; n_raw <= 1280, more gives 0).  Returns the number of passing trials, or GNUAIS_E_ARG; when that number is 1,
+ *   payload[126] (zero behind nbits / 8 bytes), *nbits = n' and *pos = p are written.  It does not ask whether r itself
+ *   passes.  Host code, no device. */
+int  gnuais_batch_long_repair(gnuais_batch *b, int on);
+int  gnuais_batch_long_repaired(gnuais_batch *b, int32_t *h_out /* [n_channels] */);
+int  gnuais_long_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload[126], int *nbits, int *pos);
 
 /* ---- each transmission once: the copies several receivers hear, merged on the delivery side ----------------------------
  * Not in the reference (one process, one or two receivers).  A batch is thousands of receivers with overlapping cover,
@@ -1075,6 +1122,9 @@ int  gnuais_node_drain_occupancy(gnuais_node *nd, gnuais_occupancy *h_out /* [ma
 int  gnuais_node_long_frames(gnuais_node *nd, int on);
 int  gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out);
 int  gnuais_node_long_counters(gnuais_node *nd, int32_t *h_delivered /* [n_channels] */, int32_t *h_failed /* [n_channels] */);
+/* gnuais_batch_long_repair() on every shard, and the long frames repaired per global channel */
+int  gnuais_node_long_repair(gnuais_node *nd, int on);
+int  gnuais_node_long_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);
 int  gnuais_node_repair(gnuais_node *nd, int on);
 int  gnuais_node_repaired(gnuais_node *nd, int32_t *h_out /* [n_channels] */);
 /* gnuais_batch_unique()'s definition over the whole node.  Copies on different shards must merge, and the shards

@@ -59,6 +59,10 @@
                                                       # (gnuais_batch_long_frames) delivers them, and their two or three
                                                       # sentences follow each call's other sentences -- behind TAG blocks of
                                                       # their own when --times is given; the summary counts them
+  ... --long-repair
+                                                      # --long, and a long frame that fails its CRC by one wrong symbol is
+                                                      # repaired on the device (gnuais_batch_long_repair); the summary counts
+                                                      # the repairs
   ... --text   prints the reference's stdout lines instead of the bare NMEA sentences
 """
 import argparse, os, sys
@@ -120,8 +124,11 @@ def main():
                     help="also decode the messages of three to five slots (427 .. 1008 bits: binary, safety text, DGNSS), "
                          "which the chain gives up on (gnuais_batch_long_frames); their sentences follow each call's others, "
                          "with TAG blocks when --times is given")
+    ap.add_argument("--long-repair", action="store_true",
+                    help="--long, and long frames that fail the CRC by one symbol error are repaired (gnuais_batch_long_repair)")
     ap.add_argument("--start", type=int, default=0, metavar="UNIX_SECONDS", help="--times: the second of the file's first sample")
     a = ap.parse_args()
+    a.long = a.long or a.long_repair
     if a.unique < 0:
         sys.exit("--unique takes a window in rows, > 0")
     if a.signal and not (a.iq or a.wideband):
@@ -176,6 +183,8 @@ def main():
         b.unique(a.unique)
     if a.long:
         b.long_frames(True)
+    if a.long_repair:
+        b.long_repair(True)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -191,7 +200,8 @@ def main():
     repair_report(a, b)
     afc_report(a, b, 48000)
     if a.long:
-        sys.stderr.write(f"{getattr(a, 'long_frames', 0)} long frames (more than two slots)\n")
+        sys.stderr.write(f"{getattr(a, 'long_frames', 0)} long frames (more than two slots)"
+                         + (f", {getattr(a, 'long_repaired', 0)} of them repaired" if a.long_repair else "") + "\n")
 
 
 def write_sentences(a, b, seq, kind, rate):
@@ -240,6 +250,7 @@ def write_long(a, b, seq, kind, rate):
     from gnuais_amd.receiver import nmea_from_long_frames
     frames = b.drain_long_frames()
     a.long_frames = getattr(a, "long_frames", 0) + len(frames)
+    a.long_repaired = getattr(a, "long_repaired", 0) + int(((frames["flags"] & 0x40) != 0).sum())
     num, den, off = b.time_map_ratio(kind) if a.times else (1, 1, 0)
     for i in range(len(frames)):
         text = nmea_from_long_frames(frames[i:i + 1], seq).decode("ascii", "replace")
@@ -359,6 +370,8 @@ def decode_wideband(a, rate, x, fmt=None):
         b.unique(a.unique)
     if a.long:
         b.long_frames(True)
+    if a.long_repair:
+        b.long_repair(True)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
