@@ -193,6 +193,17 @@ struct gnuais_batch {
     Buf<uint2> ring_chunks[NRING];              // K3's chunk table per ring (kernels.h: HdlcLaunch::chunks)
     int ring_runs[NRING] = {};                  // K3 launches into the ring since it became current
     int n_chunks = 0;
+    // gnuais_batch_discard_frames leaves no dispatch behind: it sets discard_pending, and the next deframer launch empties
+    // ring 0's words itself (HdlcLaunch::discard), behind the last K3 and in front of its own in stream order.  Whatever
+    // reads or hands out ring 0 or its words before that launch -- the drains, the counts, reset, the switch to
+    // streaming, a call without a deframer -- calls discard_flush() first, which issues the memset the discard used to be.
+    // discard_launches counts the launches that carried the flag (the parity of HdlcLaunch::ovf_mark).
+    bool discard_pending = false;
+    hipStream_t discard_stream = nullptr;       // the stream the last discard named (the chain's, when it is not pipelined)
+    unsigned discard_launches = 0;
+    // Experiments (GNUAIS_CYCLE, bits): 1 = the discard rides on the deframer launch (else: a memset per discard, as
+    // before), 2 = no event record between the deframer and a K3 on the same stream.  Default 3.
+    int cycle_parts = 3;
     // The receive time of every frame (gnuais_batch_frame_times, frame_time.hip; off by default).  `rows` counts the rows
     // the chain has taken since create / reset, over every kind of run call, whether the feature is on or not; while it
     // is on, one more launch behind each K3 writes times[slot] for the records that K3 appended to ring 0 (a batch with
@@ -358,6 +369,8 @@ int drain(gnuais_batch *b, unsigned stages, hipStream_t s);
 // the stream K3 runs on, and the stream behind the last K3 (when the chain runs on the caller's stream: that one)
 hipStream_t k3_stream(const gnuais_batch *b);
 hipStream_t behind_k3(const gnuais_batch *b);
+// capi_delivery.hip: a pending discard (gnuais_batch::discard_pending) takes effect now, as a memset behind the last K3
+int discard_flush(gnuais_batch *b);
 double now_ms();
 // capi_ingest.hip: the carries of the stages in front of the chain, for gnuais_batch_reset
 int chan_zero_state(gnuais_batch *b);

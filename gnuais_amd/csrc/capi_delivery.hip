@@ -3,6 +3,17 @@
 // delivery (gnuais_batch_stream_nmea) and the placement of its copy stream.  Host code only.
 #include "batch.h"
 
+// A pending discard as the memset it used to be: behind the last K3 (not pipelined: on the stream the discard named).  Everything that
+// reads or hands out ring 0 or its words without a deframer launch in between comes through here first.
+int gnuais::discard_flush(gnuais_batch *b)
+{
+    if (!b->discard_pending) return GNUAIS_OK;
+    b->discard_pending = false;
+    hipStream_t s = b->pipeline ? k3_stream(b) : b->discard_stream;     // behind the last K3
+    HIP_TRY(hipMemsetAsync(b->ring_count[0], 0, sizeof(uint32_t) * 3, s));
+    return GNUAIS_OK;
+}
+
 extern "C" {
 
 // device buffers of the post-stage (sorted records / text, rocPRIM scratch): allocated on first use
@@ -23,6 +34,7 @@ struct Pending {
 
 static int read_pending(gnuais_batch *b, Pending &p)
 {
+    if (int rc = discard_flush(b)) return rc;
     if (int rc = gnuais_batch_sync(b)) return rc;
     uint32_t cnt[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpy(cnt, b->ring_count[0], sizeof cnt, hipMemcpyDeviceToHost));
@@ -227,6 +239,7 @@ int gnuais_batch_vessel_table_update(gnuais_batch *b)
 {
     if (!b || !b->vt) return fail(GNUAIS_E_STATE, "vessel_table_update: no table (gnuais_batch_vessel_table_enable)");
     if (b->streaming) return fail(GNUAIS_E_STATE, "vessel_table_update: a streaming batch updates its table by itself");
+    if (int rc = discard_flush(b)) return rc;
     if (int rc = gnuais_batch_sync(b)) return rc;             // a drain-type call: waits for the chain like the drains do
     HIP_TRY(vessel_table_update_enqueue(b->ring[0], b->ring_count[0], b->frame_cap, b->vt, b->vt_slots, b->vt_fslot, behind_k3(b)));
     return GNUAIS_OK;
@@ -429,6 +442,7 @@ static int stream_setup(gnuais_batch *b)
                                                   "streamed delivery has no such stage");
     if (b->long_frames) return fail(GNUAIS_E_STATE, "stream_nmea: the batch decodes long frames (gnuais_batch_long_frames); "
                                                     "the streamed delivery carries no records of them");
+    if (int rc = discard_flush(b)) return rc;   // ring 0 is about to be handed to the streamed delivery
     if (int rc = gnuais_batch_sync(b)) return rc;
     // every object is created only if it does not exist yet: a first use that failed half way (e.g. the pinned
     // allocation) is repeated by the next call without leaking what the failed one had made
@@ -574,8 +588,13 @@ int gnuais_batch_discard_frames(gnuais_batch *b, void *stream)
     if (!b) return fail(GNUAIS_E_ARG, "discard_frames: NULL batch");
     if (b->streaming) return fail(GNUAIS_E_STATE, "discard_frames: the batch is streaming (gnuais_batch_stream_nmea)");
     if (int rc = set_device(b)) return rc;
-    hipStream_t s = b->pipeline ? k3_stream(b) : (hipStream_t) stream;   // behind the last K3
-    HIP_TRY(hipMemsetAsync(b->ring_count[0], 0, sizeof(uint32_t) * 3, s));
+    // Behind the last K3, in stream order.  No dispatch for it: the next deframer launch runs exactly there -- behind the
+    // previous K3, in front of its own -- and empties the ring's words itself (HdlcLaunch::discard); whoever looks at the
+    // ring before that launch turns the mark into the memset first (discard_flush).  Two discards in a row are one.
+    b->discard_stream = (hipStream_t) stream;   // where the chain runs when it is not pipelined
+    b->discard_pending = true;
+    if (!(b->cycle_parts & 1))
+        if (int rc = discard_flush(b)) return rc;
     b->hdlc_calls = 0;
     return GNUAIS_OK;
 }

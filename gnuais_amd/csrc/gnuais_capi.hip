@@ -282,6 +282,7 @@ int gnuais_batch_create(gnuais_batch **out, int device, int n_channels, const fl
             if (e == hipSuccess) e = b->pool[made].ensure(made < 8 ? hi : 0);
     }
     if (const char *v = getenv("GNUAIS_K3_SAME")) b->k3_same = atoi(v) != 0;
+    if (const char *v = getenv("GNUAIS_CYCLE")) b->cycle_parts = atoi(v) & 3;
     if (const char *v = getenv("GNUAIS_PLL_VARIANT")) {      // the values set_option takes, nothing else
         const int pv = atoi(v);
         if (pv == 0 || pv == 7 || pv == 8) b->pll_variant = pv;
@@ -319,6 +320,7 @@ static int rings_reset(gnuais_batch *b)
     }
     b->ring_cur = 0;
     b->stream_calls = 0;
+    b->discard_pending = false;                 // every word of every ring is zero
     return GNUAIS_OK;
 }
 
@@ -351,6 +353,7 @@ int gnuais_batch_reset(gnuais_batch *b)
     if (!b) return fail(GNUAIS_E_ARG, "reset: NULL batch");
     if (int rc = set_device(b)) return rc;
     const size_t N = (size_t) b->N;
+    if (int rc = discard_flush(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     for (int q = 0; q < gnuais_batch::HB; ++q)
         HIP_TRY(hipMemset(b->hist[q], 0, sizeof(int16_t) * N * b->NT));   // filter.c:62
@@ -472,6 +475,7 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
         if (value < 1) return fail(GNUAIS_E_ARG, "timing_stride must be >= 1");
         b->timing_stride = value;
     } else if (!strcmp(name, "pipeline")) {
+        if (int rc = discard_flush(b)) return rc;       // "behind the last K3" names another stream from here on
         b->pipeline = value != 0;
     } else if (!strcmp(name, "pll_variant")) {
         if (value != 0 && value != 7 && value != 8)
@@ -536,6 +540,20 @@ static void fill_hdlc(const gnuais_batch *b, HdlcLaunch &h, int k)
     h.lanes_per_wave = b->hdlc_lpw ? b->hdlc_lpw : (b->hdlc_variant ? ev_lpw : 64);
     // the chunk table describes ONE launch; a second one into the same ring would overwrite it
     h.chunks = (b->streaming && b->ring_runs[b->ring_cur] == 0) ? b->ring_chunks[b->ring_cur] : nullptr;
+    // a pending gnuais_batch_discard_frames rides on this launch's deframer (a batch that streams takes no discard)
+    h.discard = b->discard_pending && !b->streaming && b->ring_cur == 0;
+    h.ovf_mark = 2u << ((b->discard_launches + (h.discard ? 1u : 0u)) & 1u);
+}
+
+// the deframer launch described by h; a discard it carried is no longer pending
+static int run_deframer(gnuais_batch *b, const HdlcLaunch &h, hipStream_t s)
+{
+    HIP_TRY(b->hdlc_variant ? launch_hdlc_events(h, s) : launch_hdlc_deframe(h, s));
+    if (h.discard) {
+        b->discard_pending = false;
+        b->discard_launches++;
+    }
+    return GNUAIS_OK;
 }
 
 // the launch behind the K3 described by h: len rows from row b->rows on (len <= 0: bits without samples)
@@ -679,11 +697,17 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     if (pl && b->calls >= 1 && sD != sC)
         HIP_TRY(hipStreamWaitEvent(sC, b->e_done[4][(k + b->nbuf - 1) % b->nbuf], 0));
     if (tm) HIP_TRY(hipEventRecord(ev[5], sC));
-    if (b->stage_mask & 8) HIP_TRY(b->hdlc_variant ? launch_hdlc_events(h, sC) : launch_hdlc_deframe(h, sC));
+    if (b->stage_mask & 8)
+        if (int rc = run_deframer(b, h, sC)) return rc;
     if (tm) HIP_TRY(hipEventRecord(ev[7], sC));
-    if (pl) HIP_TRY(hipEventRecord(b->e_done[3][k], sC));
+    // e_done[3][k] has one waiter: the K3 of this call, when it runs on a stream of its own.  On the deframer's stream
+    // the order is the stream's, and the record would be one more packet between the two launches of the serial cycle.
+    const bool hand_off = pl && (sD != sC || !(b->cycle_parts & 2));
+    if (hand_off) HIP_TRY(hipEventRecord(b->e_done[3][k], sC));
     // K3
     if (pl && sD != sC) HIP_TRY(hipStreamWaitEvent(sD, b->e_done[3][k], 0));
+    // a discard still pending here found no deframer launch to ride on (stage_mask): the memset, where it always was
+    if (int rc = discard_flush(b)) return rc;
     if (tm) HIP_TRY(hipEventRecord(ev[9], sD));
     if (b->stage_mask & 16) HIP_TRY(launch_hdlc_crc(h, sD));
     // the repair of what K3 counted in lostframes: behind K3, in front of the times (repaired frames get theirs) and of
@@ -938,7 +962,7 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         HIP_TRY(hipMemcpy(b->segcnt[0], cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
         HdlcLaunch h;
         fill_hdlc(b, h, 0);
-        HIP_TRY(b->hdlc_variant ? launch_hdlc_events(h, nullptr) : launch_hdlc_deframe(h, nullptr));
+        if (int rc = run_deframer(b, h, nullptr)) return rc;
         HIP_TRY(launch_hdlc_crc(h, nullptr));
         if (b->repair) HIP_TRY(launch_hdlc_repair(fill_repair(b, h), nullptr));
         if (b->frame_times) HIP_TRY(launch_frame_times(fill_frame_times(b, h, 0), nullptr));   // bits without samples: -1

@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "crc_sliced.h"
 #include "kernels.h"
 
 namespace gnuais {
@@ -91,10 +92,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     const uint32_t *__restrict__ segbits, const uint32_t *__restrict__ segcnt,
     uint32_t *__restrict__ ctl, uint32_t *__restrict__ cand, uint32_t *__restrict__ cand_first,
     uint32_t *__restrict__ cand_count, int32_t *__restrict__ counters,
-    uint32_t *__restrict__ flags, int N, int n_seg, int seg_words, int K)
+    uint32_t *__restrict__ flags, int N, int n_seg, int seg_words, int K, uint32_t ovf_mark)
 {
     __builtin_amdgcn_s_setprio(3);      // latency-bound chain: take every issue slot it can use
     const int cg = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((ovf_mark & 1u) && cg == 0) hdlc_discard_ring(flags, ovf_mark & ~1u);
     const bool live = cg < N;
     const size_t c = (size_t) (live ? cg : N - 1), n_ = (size_t) N;
 
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
                                     bufferpos = 0; cur = 0; rawpos = 0; bitstuff = 0; last = 0;
                                     rec_ok = (nstart - first) < (uint32_t) K;
                                     rec = cand + ((size_t) c * K + nstart % (uint32_t) K) * CAND_WORDS;
-                                    if (rec_ok) rec[0] = 0; else flags[1] = 1;
+                                    if (rec_ok) rec[0] = 0; else flags[1] = ovf_mark & ~1u;
                                     ++nstart;
                                 } else if (L == R - 1) {        // 0 in ST_STARTSIGN (nstartsign 6)
                                     HDLC_RESET(); nstartsign = 1; last = 0;
@@ -387,157 +389,182 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
 // K3: CRC check + delivery of the candidates closed in this call.  One block of 256
 // threads owns K3_CH adjacent channels: their candidate counts are prefix-summed in
 // LDS and the candidates, enumerated channel-major then in time, are taken 256 at
-// a time (one per thread).  CRC-16/X-25 by bytes through a 256-entry table built
-// in LDS from the bitwise definition (protodec.c:106-118).  The good frames of a
+// a time (one per thread).  CRC-16/X-25 four bytes per step through four 256-entry tables built
+// in LDS from the bitwise definition (crc_sliced.h; protodec.c:106-118).  The good frames of a
 // pass are compacted in order (ballot ranks) and the block reserves one contiguous
 // piece of the frame ring for them.  Pieces land in whatever order the blocks finish;
 // the drain restores the reference's print order with a device sort on (channel, end_bit).
+//
+// K3 sits between two deframer launches on one stream, so its duration is part of the chain's period, and it is a chain
+// of waits, not of work: what a pass costs is its dependent trips to memory and to LDS.  Hence
+//   * the channels' first slots come with their counts (one trip for the block, not one per pass);
+//   * a pass's record -- header, end_bit and the raw words, 80 bytes, 16-byte aligned -- is ONE round of five 16-byte
+//     loads, issued before anything is known about it (an abandoned slot's words are simply not used), and the NEXT
+//     pass's round is issued before this pass's work, so only the first pass waits for memory at all;
+//   * the per-thread LDS arrays are word-major (word q of thread t at [q * 256 + t]): a lane's bank is its lane number
+//     whatever word it asks for, in the unstuffing loop's data-dependent indices too;
+//   * the CRC takes a word per dependent LDS round (8 to 14 rounds for a frame, not 23 to 55).
+// The ring reservation (one returning atomic per pass) is the trip that is left.
+struct K3Rec {
+    uint4 v[CAND_WORDS / 4];            // [0].x header, [0].y end_bit, then the raw words
+    int c;                              // the candidate's channel; -1: this thread has none in the pass
+};
+static_assert(CAND_WORDS % 4 == 0 && CAND_HDR == 2, "a candidate record is a whole number of 16-byte loads");
+
+__device__ __forceinline__ void k3_fetch(K3Rec &r, uint32_t i, uint32_t total, const uint32_t *pre, const uint32_t *first,
+                                         const uint32_t *__restrict__ cand, int K, int ch0)
+{
+    r.c = -1;
+    r.v[0].x = 0;
+    if (i >= total) return;
+    // channel of candidate i: largest k with pre[k] <= i
+    int lo = 0, hi = K3_CH - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pre[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    r.c = ch0 + lo;
+    const uint32_t slot = (first[lo] + (i - pre[lo])) % (uint32_t) K;
+    const uint4 *rec = reinterpret_cast<const uint4 *>(cand + ((size_t) r.c * K + slot) * CAND_WORDS);
+#pragma unroll
+    for (int q = 0; q < CAND_WORDS / 4; ++q) r.v[q] = rec[q];
+}
+
 __global__ __launch_bounds__(256) void hdlc_crc_kernel(
     const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cand_first,
     const uint32_t *__restrict__ cand_count, int32_t *__restrict__ counters,
     uint32_t *__restrict__ frames, uint32_t *__restrict__ flags, uint32_t frame_cap, int N, int K,
     uint2 *__restrict__ chunks, int n_pass)
 {
-    __shared__ uint32_t tab[256];
+    __shared__ uint16_t tab[crc::SLICES * 256];
     __shared__ uint32_t pre[K3_CH + 1];
+    __shared__ uint32_t first[K3_CH];
     // The two per-thread buffers are DYNAMIC shared memory (K3_DYN_LDS bytes at launch).  As static arrays (36 KB) they
     // made the compiler derive "at most four waves per SIMD" from the workgroup's LDS and then pad the kernel's register
     // request up to that occupancy: 104 VGPRs per wave in the descriptor for 59 in use -- beside four FIR waves and a
     // PLL wave that is the difference between a wave that fits a SIMD's free registers and one that waits for a FIR
     // wave to retire.
     extern __shared__ uint32_t k3_dyn[];
-    uint32_t (*const stage)[HDLC_BUF_WORDS + 1] = reinterpret_cast<uint32_t (*)[HDLC_BUF_WORDS + 1]>(k3_dyn);   // unstuffed frame bits per thread
-    uint32_t (*const rawlds)[CAND_WORDS - CAND_HDR + 1] =                                                     // raw record per thread
-        reinterpret_cast<uint32_t (*)[CAND_WORDS - CAND_HDR + 1]>(k3_dyn + 256 * (HDLC_BUF_WORDS + 1));
+    constexpr int RAW_WORDS = CAND_WORDS - CAND_HDR;
+    const int tid = threadIdx.x;
+    uint32_t *const stage = k3_dyn + tid;                                   // unstuffed frame bits: word q at stage[q * 256], q <= HDLC_BUF_WORDS
+    uint32_t *const rawlds = k3_dyn + 256 * (HDLC_BUF_WORDS + 1) + tid;     // raw record: word q at rawlds[q * 256]
     __shared__ uint32_t wave_cnt[4];
     __shared__ uint32_t pass_base;
-    const int tid = threadIdx.x;
-    const int c_own = blockIdx.x * K3_CH + tid;
+    const int ch0 = blockIdx.x * K3_CH;
 
-    {   // table entry tid: eight LFSR steps on the byte value
+    {   // entry tid of the four tables: eight LFSR steps on the byte value, eight more for each further table
         uint32_t t = (uint32_t) tid;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) t = (t >> 1) ^ ((t & 1u) ? 0x8408u : 0u);
-        tab[tid] = t;
+        for (int k = 0; k < crc::SLICES; ++k) {
+            t = crc::advance8(t);
+            tab[k * 256 + tid] = (uint16_t) t;
+        }
     }
-    // prefix sums of the per-channel candidate counts (K3_CH is small: serial scan)
-    if (tid < K3_CH) pre[tid + 1] = (c_own < N) ? cand_count[c_own] : 0u;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        pre[0] = 0;
-        for (int q = 1; q <= K3_CH; ++q) { run += pre[q]; pre[q] = run; }
+    // prefix sums of the per-channel candidate counts (K3_CH channels: one wave's scan), and the channels' first slots
+    static_assert(K3_CH <= 64, "the scan is one wave's");
+    if (tid < 64) {
+        const int c_own = ch0 + tid;
+        const bool own = tid < K3_CH && c_own < N;
+        uint32_t v = own ? cand_count[c_own] : 0u;
+        const uint32_t f = own ? cand_first[c_own] : 0u;
+#pragma unroll
+        for (int d = 1; d < K3_CH; d <<= 1) {
+            const uint32_t up = __shfl_up(v, d);
+            if (tid >= d) v += up;
+        }
+        if (tid < K3_CH) { pre[tid + 1] = v; first[tid] = f; }
+        if (tid == 0) pre[0] = 0;
     }
     __syncthreads();
     const uint32_t total = pre[K3_CH];
     const size_t n_ = (size_t) N;
 
+    K3Rec nx;
+    k3_fetch(nx, (uint32_t) tid, total, pre, first, cand, K, ch0);
     int pass = 0;
     for (uint32_t i0 = 0; i0 < total; i0 += 256, ++pass) {
-        const uint32_t i = i0 + (uint32_t) tid;
+        const K3Rec r = nx;
+        if (i0 + 256 < total) k3_fetch(nx, i0 + 256 + (uint32_t) tid, total, pre, first, cand, K, ch0);
         bool good = false;
-        uint32_t out[16];
+        const uint32_t hdr = r.v[0].x;
+        const int n = (int) (hdr & 0xffffu);
+        const int nbytes = n >> 3, buflen = nbytes + 2;     // protodec.c:133-134
+        if (r.c >= 0 && (hdr & CAND_VALID)) {               // else: abandoned before its closing flag
+            const int rawlen = (int) ((hdr >> 17) & 0x3ffu);
+            // protodec.c:1008-1023 on the raw bits: store every bit except the one
+            // that follows five 1s (it is a stuffed 0 inside a frame)
+            {
+                // the record is parked in LDS so that the bit
+                // loop below can stay rolled (small code: this kernel shares the
+                // instruction cache with the FIR and the sequential kernels)
+                rawlds[0] = r.v[0].z;
+                rawlds[256] = r.v[0].w;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) out[q] = 0;
-        if (i < total) {
-            // channel of candidate i: largest k with pre[k] <= i
-            int lo = 0, hi = K3_CH - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (pre[mid] <= i) lo = mid; else hi = mid - 1;
-            }
-            const int c = blockIdx.x * K3_CH + lo;
-            const uint32_t j = i - pre[lo];
-            const uint32_t slot = (cand_first[c] + j) % (uint32_t) K;
-            const uint32_t *rec = cand + ((size_t) c * K + slot) * CAND_WORDS;
-            const uint32_t hdr = rec[0];
-            if (hdr & CAND_VALID) {                     // else: abandoned before its closing flag
-                const int n = (int) (hdr & 0xffffu);
-                const int rawlen = (int) ((hdr >> 17) & 0x3ffu);
-                const int nbytes = n >> 3, buflen = nbytes + 2; // protodec.c:133-134
-                // protodec.c:1008-1023 on the raw bits: store every bit except the one
-                // that follows five 1s (it is a stuffed 0 inside a frame)
-                {
-                    // whole record first (one latency), parked in LDS so that the bit
-                    // loop below can stay rolled (small code: this kernel shares the
-                    // instruction cache with the FIR and the sequential kernels)
-                    uint32_t raw[CAND_WORDS - CAND_HDR];
-#pragma unroll
-                    for (int q = 0; q < CAND_WORDS - CAND_HDR; ++q) raw[q] = rec[CAND_HDR + q];
-#pragma unroll
-                    for (int q = 0; q < CAND_WORDS - CAND_HDR; ++q) rawlds[tid][q] = raw[q];
-                    // A word at a time.  Inside a candidate a run of 1s is at most five long (a sixth
-                    // closed the frame), so the bits to drop are exactly the 0s that follow five 1s:
-                    // bit i of `five` = raw[i-1] & ... & raw[i-5], across the word boundary through the
-                    // previous word.  The few such bits of a word are cut out one by one, the rest is
-                    // appended to the output through a 64-bit window.
-                    unsigned long long acc = 0;
-                    uint32_t prevw = 0;
-                    int fill = 0, ow = 0;
-                    const int nwords = (rawlen + 31) >> 5;
+                for (int q = 1; q < CAND_WORDS / 4; ++q) {
+                    rawlds[(4 * q - 2) * 256] = r.v[q].x;
+                    rawlds[(4 * q - 1) * 256] = r.v[q].y;
+                    rawlds[(4 * q) * 256] = r.v[q].z;
+                    rawlds[(4 * q + 1) * 256] = r.v[q].w;
+                }
+                // A word at a time.  Inside a candidate a run of 1s is at most five long (a sixth
+                // closed the frame), so the bits to drop are exactly the 0s that follow five 1s:
+                // bit i of `five` = raw[i-1] & ... & raw[i-5], across the word boundary through the
+                // previous word.  The few such bits of a word are cut out one by one, the rest is
+                // appended to the output through a 64-bit window.
+                unsigned long long acc = 0;
+                uint32_t prevw = 0;
+                int fill = 0, ow = 0;
+                const int nwords = (rawlen + 31) >> 5;
 #pragma unroll 1
-                    for (int q = 0; q < nwords; ++q) {
-                        uint32_t rw = rawlds[tid][q];
-                        const int nvq = rawlen - 32 * q < 32 ? rawlen - 32 * q : 32;
-                        const unsigned long long cc = ((unsigned long long) rw << 32) | prevw;
-                        const uint32_t five = (uint32_t) (cc >> 31) & (uint32_t) (cc >> 30) & (uint32_t) (cc >> 29) &
-                                              (uint32_t) (cc >> 28) & (uint32_t) (cc >> 27);
-                        uint32_t stf = five & ~rw & (nvq >= 32 ? ~0u : (1u << nvq) - 1u);
-                        prevw = rw;
-                        int nout = nvq;
-                        while (stf) {                               // highest first: lower positions stay valid
-                            const int pz = 31 - __clz((int) stf);
-                            stf &= ~(1u << pz);
-                            rw = (rw & ((1u << pz) - 1u)) | ((pz >= 31 ? 0u : rw >> (pz + 1)) << pz);
-                            --nout;
-                        }
-                        if (nout < 32) rw &= (1u << nout) - 1u;
-                        acc |= (unsigned long long) rw << fill;
-                        fill += nout;
-                        if (fill >= 32) {
-                            if (ow <= HDLC_BUF_WORDS) stage[tid][ow] = (uint32_t) acc;
-                            ++ow;
-                            acc >>= 32;
-                            fill -= 32;
-                        }
+                for (int q = 0; q < nwords && q < RAW_WORDS; ++q) {
+                    uint32_t rw = rawlds[q * 256];
+                    const int nvq = rawlen - 32 * q < 32 ? rawlen - 32 * q : 32;
+                    const unsigned long long cc = ((unsigned long long) rw << 32) | prevw;
+                    const uint32_t five = (uint32_t) (cc >> 31) & (uint32_t) (cc >> 30) & (uint32_t) (cc >> 29) &
+                                          (uint32_t) (cc >> 28) & (uint32_t) (cc >> 27);
+                    uint32_t stf = five & ~rw & (nvq >= 32 ? ~0u : (1u << nvq) - 1u);
+                    prevw = rw;
+                    int nout = nvq;
+                    while (stf) {                               // highest first: lower positions stay valid
+                        const int pz = 31 - __clz((int) stf);
+                        stf &= ~(1u << pz);
+                        rw = (rw & ((1u << pz) - 1u)) | ((pz >= 31 ? 0u : rw >> (pz + 1)) << pz);
+                        --nout;
                     }
-                    if (ow <= HDLC_BUF_WORDS) stage[tid][ow] = (uint32_t) acc;
-                    for (int q = ow + 1; q <= HDLC_BUF_WORDS; ++q) stage[tid][q] = 0;
-                }
-                uint32_t w[HDLC_BUF_WORDS];
-#pragma unroll
-                for (int q = 0; q < HDLC_BUF_WORDS; ++q) w[q] = stage[tid][q];
-                uint32_t crc = 0xffffu;
-#pragma unroll
-                for (int q = 0; q < HDLC_BUF_WORDS; ++q) {
-#pragma unroll
-                    for (int bq = 0; bq < 4; ++bq) {
-                        if (q * 4 + bq < buflen) {
-                            const uint32_t byte = (w[q] >> (8 * bq)) & 0xffu;
-                            crc = (crc >> 8) ^ tab[(crc ^ byte) & 0xffu];
-                        }
+                    if (nout < 32) rw &= (1u << nout) - 1u;
+                    acc |= (unsigned long long) rw << fill;
+                    fill += nout;
+                    if (fill >= 32) {
+                        if (ow <= HDLC_BUF_WORDS) stage[ow * 256] = (uint32_t) acc;
+                        ++ow;
+                        acc >>= 32;
+                        fill -= 32;
                     }
                 }
-                if (crc == 0xf0b8u) {                   // ~crc == 0x0f47, protodec.c:166
-                    good = true;
-                    atomicAdd(&counters[c], 1);         // protodec.c:1103
-                    out[0] = (uint32_t) c;
-                    out[1] = rec[1];
+                if (ow <= HDLC_BUF_WORDS) stage[ow * 256] = (uint32_t) acc;
+                for (int q = ow + 1; q <= HDLC_BUF_WORDS; ++q) stage[q * 256] = 0;
+            }
+            uint32_t w[HDLC_BUF_WORDS];
 #pragma unroll
-                    for (int q = 0; q < 14; ++q) {
-                        uint32_t v = 0;
-                        if (q * 4 < nbytes) {
-                            v = w[q];
-                            const int keep = nbytes - q * 4;
-                            if (keep < 4) v &= (1u << (8 * keep)) - 1u;
-                        }
-                        // flags: bit 0 CRC ok, bits 5:1 = bits 36:32 of end_bit
-                        if (q == 13) v = (v & 0xffu) | ((1u | ((hdr >> 27) << 1)) << 8) | ((uint32_t) n << 16);
-                        out[2 + q] = v;
-                    }
-                } else {
-                    atomicAdd(&counters[n_ + c], 1);    // protodec.c:1107
-                }
+            for (int q = 0; q < HDLC_BUF_WORDS; ++q) w[q] = stage[q * 256];
+            // buflen bytes: whole words through the four tables, the one to three bytes behind them through table 0
+            uint32_t crc = 0xffffu;
+#pragma unroll
+            for (int q = 0; q < HDLC_BUF_WORDS; ++q)
+                if (4 * q + 4 <= buflen) crc = crc::step4(crc, w[q], tab);
+            {
+                const int qt = buflen >> 2;                          // buflen <= 55: word 13 at most
+                const uint32_t tw = stage[(qt < HDLC_BUF_WORDS ? qt : HDLC_BUF_WORDS) * 256];
+#pragma unroll
+                for (int bq = 0; bq < 3; ++bq)
+                    if (bq < (buflen & 3)) crc = crc::step1(crc, (tw >> (8 * bq)) & 0xffu, tab);
+            }
+            if (crc == 0xf0b8u) {                   // ~crc == 0x0f47, protodec.c:166
+                good = true;
+                atomicAdd(&counters[r.c], 1);       // protodec.c:1103
+            } else {
+                atomicAdd(&counters[n_ + r.c], 1);  // protodec.c:1107
             }
         }
         // ordered compaction of this pass's good frames
@@ -565,6 +592,21 @@ __global__ __launch_bounds__(256) void hdlc_crc_kernel(
         if (good) {
             const uint32_t idx = pass_base + woff + below;
             if (idx < frame_cap) {
+                uint32_t out[16];
+                out[0] = (uint32_t) r.c;
+                out[1] = r.v[0].y;
+#pragma unroll
+                for (int q = 0; q < 14; ++q) {
+                    uint32_t v = 0;
+                    if (q * 4 < nbytes) {
+                        v = stage[q * 256];                 // this thread's own words, untouched since its CRC
+                        const int keep = nbytes - q * 4;
+                        if (keep < 4) v &= (1u << (8 * keep)) - 1u;
+                    }
+                    // flags: bit 0 CRC ok, bits 5:1 = bits 36:32 of end_bit
+                    if (q == 13) v = (v & 0xffu) | ((1u | ((hdr >> 27) << 1)) << 8) | ((uint32_t) n << 16);
+                    out[2 + q] = v;
+                }
                 uint4 *dst = reinterpret_cast<uint4 *>(frames + (size_t) idx * 16);
                 dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
                 dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
@@ -587,13 +629,13 @@ hipError_t launch_hdlc_deframe(const HdlcLaunch &a, hipStream_t stream)
     hipLaunchKernelGGL(hdlc_deframe_kernel, dim3((a.N + lpw - 1) / lpw), dim3(lpw),
                        (PACK_MAX + 1) * lpw * sizeof(uint32_t), stream,
                        a.segbits, a.segcnt, a.ctl, a.cand, a.cand_first, a.cand_count, a.counters,
-                       a.frame_count, a.N, a.n_seg, a.seg_words, a.K);
+                       a.frame_count, a.N, a.n_seg, a.seg_words, a.K, a.ovf_mark | (a.discard ? 1u : 0u));
     return hipGetLastError();
 }
 
 hipError_t launch_hdlc_crc(const HdlcLaunch &a, hipStream_t stream)
 {
-    constexpr size_t K3_DYN_LDS = 256 * ((HDLC_BUF_WORDS + 1) + (CAND_WORDS - CAND_HDR + 1)) * sizeof(uint32_t);
+    constexpr size_t K3_DYN_LDS = 256 * ((HDLC_BUF_WORDS + 1) + (CAND_WORDS - CAND_HDR)) * sizeof(uint32_t);
     hipLaunchKernelGGL(hdlc_crc_kernel, dim3((unsigned) ((a.N + K3_CH - 1) / K3_CH)), dim3(256), K3_DYN_LDS,
                        stream, a.cand, a.cand_first, a.cand_count, a.counters,
                        (uint32_t *) a.frames, a.frame_count, a.frame_cap, a.N, a.K, a.chunks, k3_passes(a.K_call > 0 ? a.K_call : a.K));

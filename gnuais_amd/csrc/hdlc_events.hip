@@ -68,12 +68,13 @@ __global__ __launch_bounds__(64) void hdlc_events_kernel(
     const uint32_t *__restrict__ segbits, const uint32_t *__restrict__ segcnt,
     uint32_t *__restrict__ ctl, uint32_t *__restrict__ cand, uint32_t *__restrict__ cand_first,
     uint32_t *__restrict__ cand_count, int32_t *__restrict__ counters,
-    uint32_t *__restrict__ flags, int N, int n_seg, int seg_words, int K)
+    uint32_t *__restrict__ flags, int N, int n_seg, int seg_words, int K, uint32_t ovf_mark)
 {
     __builtin_amdgcn_s_setprio(3);      // latency-bound chain: take every issue slot it can use (priority 0 / 1: level, profiles/r05_pll_h3_in_the_pipeline.txt)
     extern __shared__ uint32_t lds[];
     const int tpb = TPB > 0 ? TPB : (int) blockDim.x, tx = (int) threadIdx.x;
     const int cg = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((ovf_mark & 1u) && cg == 0) hdlc_discard_ring(flags, ovf_mark & ~1u);
     const bool live = cg < N;
     const size_t c = (size_t) (live ? cg : N - 1), n_ = (size_t) N;
     uint32_t *const Xa = lds + tx, *const NAa = Xa + (EW + 2) * tpb, *const CBa = NAa + EW * tpb,
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(64) void hdlc_events_kernel(
          bufferpos = 0; cur = 0; rawpos = 0; bitstuff = 0; last = 0;                    \
          rec_ok = (nstart - first) < (uint32_t) K;                                      \
          rec = cand + ((size_t) c * K + nstart % (uint32_t) K) * CAND_WORDS;            \
-         if (rec_ok) rec[0] = 0; else flags[1] = 1;                                     \
+         if (rec_ok) rec[0] = 0; else flags[1] = ovf_mark & ~1u;                                    \
          ++nstart; } while (0)
     // one raw bit / a run of raw bits into the open frame's record
 #define RAW_APPEND(v_, n_bits_)                                                         \
@@ -537,7 +538,7 @@ hipError_t launch_hdlc_events(const HdlcLaunch &a, hipStream_t stream)
     const size_t lds = EV_ROWS * lpw * sizeof(uint32_t);
 #define EV_LAUNCH(T)                                                                                                  \
     hipLaunchKernelGGL(hdlc_events_kernel<T>, grid, block, lds, stream, a.segbits, a.segcnt, a.ctl, a.cand, a.cand_first, \
-                       a.cand_count, a.counters, a.frame_count, a.N, a.n_seg, a.seg_words, a.K)
+                       a.cand_count, a.counters, a.frame_count, a.N, a.n_seg, a.seg_words, a.K, a.ovf_mark | (a.discard ? 1u : 0u))
     switch (lpw) {
     case 8: EV_LAUNCH(8); break;
     case 16: EV_LAUNCH(16); break;

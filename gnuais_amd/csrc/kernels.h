@@ -100,7 +100,23 @@ struct HdlcLaunch {
     uint2 *chunks = nullptr;   // optional [blocks of K3][k3_passes(K)]: where each pass of each K3 block put its
                            // frames in the ring (start, count).  (block, pass, position) is the reference's
                            // print order -- channel, then time -- so a ring that holds ONE call needs no sort
+    // gnuais_batch_discard_frames without a dispatch of its own: the deframer launch that carries `discard` empties the
+    // ring's three words in front of its own K3 and behind the previous one (stream order), where the memset used to sit.
+    // Other blocks of the same launch may already have marked a candidate that found no slot in word 1, so that mark is
+    // the value `ovf_mark` (2 or 4: it changes with every discard-carrying launch; readers ask for non-zero) and the
+    // clearing thread ANDs the word with it: whatever earlier launches left is gone (K3's 1, the other value), what this
+    // launch says stays, in either order of the two accesses.  The kernels take both in one word: ovf_mark | discard.
+    bool discard = false;
+    uint32_t ovf_mark = 2;
 };
+#if defined(__HIPCC__)
+__device__ __forceinline__ void hdlc_discard_ring(uint32_t *flags, uint32_t ovf_mark)
+{
+    flags[0] = 0;
+    atomicAnd(&flags[1], ovf_mark);
+    flags[2] = 0;
+}
+#endif
 constexpr int K3_CH = 32;               // channels per K3 block
 inline int k3_blocks(int N) { return (N + K3_CH - 1) / K3_CH; }
 inline int k3_passes(int K) { return (K3_CH * K + 255) / 256; }
