@@ -275,6 +275,15 @@ struct gnuais_batch {
     Buf<uint32_t> uq_tail[2];
     Buf<void> uq_scratch;
     Buf<void> uq_heard;                         // gnuais_batch_drain_frames_heard's own scratch, on its first use
+    // The same over the long ring (gnuais_batch_long_unique, frame_unique_long.hip; 0 = off, only with long_frames): a
+    // window, a double-buffered tail ([n][38] words) and a late count of its own; the hash bits are uq_hash_bits.  The
+    // scratch, the member lists' scratch and the output buffer (records, copies, offsets, members) grow on demand.
+    // Nothing runs per call; only gnuais_batch_drain_long_frames_unique and _heard touch any of it.
+    int lq_window = 0, lq_cur = 0, lq_n_tail = 0;
+    long long lq_late = 0;
+    Buf<uint64_t> lq_tail[2];
+    Buf<void> lq_scratch, lq_heard;
+    Buf<char> lq_out;
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)
@@ -371,6 +380,9 @@ hipStream_t k3_stream(const gnuais_batch *b);
 hipStream_t behind_k3(const gnuais_batch *b);
 // capi_delivery.hip: a pending discard (gnuais_batch::discard_pending) takes effect now, as a memset behind the last K3
 int discard_flush(gnuais_batch *b);
+// gnuais_capi.hip: the long ring's two words once the chain is idle, in the name of the entry `who`: records held, and
+// whether some were dropped (GNUAIS_E_STATE on a batch that never decoded long frames)
+int long_pending(gnuais_batch *b, const char *who, uint32_t &have, bool &overflow);
 double now_ms();
 // capi_ingest.hip: the carries of the stages in front of the chain, for gnuais_batch_reset
 int chan_zero_state(gnuais_batch *b);

@@ -404,6 +404,111 @@ int gnuais_batch_drain_frames_heard(gnuais_batch *b, gnuais_frame *h_out, int64_
     return drain_unique_impl(b, h_out, h_times, h_copies, max, n_out, h_first, h_members, n_members);
 }
 
+// One record per long transmission (gnuais_batch_long_unique): the long ring and the open clusters of earlier drains go
+// through frame_unique_long.hip; the primaries and their copies cross PCIe once.  The same shape as drain_unique_impl: the
+// hashed attempt, then the exact one on the collision word; the carried state moves only when everything has succeeded;
+// it ends as the plain long drain ends, by zeroing the ring's two words.
+// h_first (with h_members and n_members): the clusters' member lists as well (gnuais_batch_drain_long_frames_heard).
+static int drain_long_unique_impl(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
+                                  int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    const char *who = h_first ? "drain_long_frames_heard" : "drain_long_frames_unique";
+    *n_out = 0;
+    if (!b->lq_window) return fail(GNUAIS_E_STATE, "drain_long_frames_unique: the batch does not merge long frames (gnuais_batch_long_unique)");
+    uint32_t have = 0;
+    bool overflow = false;
+    if (int rc = long_pending(b, who, have, overflow)) return rc;
+    if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_long_frames_unique: buffers too small (one entry per pending long frame always suffices)");
+    const size_t m = (size_t) b->lq_n_tail + have;
+    if (m) {                                    // without frames the tail still ages
+        const size_t need = long_unique_scratch_bytes((int) m);
+        HIP_TRY(b->lq_scratch.grow(need, need / 4));
+        Buf<uint64_t> &next = b->lq_tail[b->lq_cur ^ 1];
+        HIP_TRY(next.grow(sizeof(gnuais_long_frame) * m, sizeof(gnuais_long_frame) * m / 4));
+        // the output: records, copies, and for the lists one offset more than records and the members, 8-byte aligned
+        const size_t at_copies = sizeof(gnuais_long_frame) * have, at_first = at_copies + 4 * (size_t) have;
+        const size_t at_members = (at_first + 4 * ((size_t) have + 1) + 7) & ~(size_t) 7;
+        const size_t need_out = at_members + sizeof(gnuais_hearer) * have;
+        HIP_TRY(b->lq_out.grow(need_out, need_out / 4));
+        auto bits_of = [](unsigned long long v) { int n = 1; while (v >> n) ++n; return n; };
+        LongUniqueLaunch a;
+        a.frames = b->long_ring;
+        a.have = (int) have;
+        a.tail = b->lq_tail[b->lq_cur];
+        a.n_tail = b->lq_n_tail;
+        a.tail_out = next;
+        a.window = b->lq_window;
+        a.rows = (long long) b->rows;
+        a.hash_bits = b->uq_hash_bits;
+        a.ch_bits = bits_of((unsigned long long) (b->N - 1));
+        a.time_bits = bits_of(b->rows);          // t + 1 <= rows
+        a.scratch = b->lq_scratch;
+        a.scratch_bytes = b->lq_scratch.bytes;
+        a.out_frames = reinterpret_cast<gnuais_long_frame *>(b->lq_out.p);
+        a.out_copies = reinterpret_cast<int32_t *>(b->lq_out.p + at_copies);
+        if (h_first) {
+            static_assert(sizeof(gnuais_hearer) == 24, "a member is three 64-bit words");
+            const size_t need_h = long_unique_heard_scratch_bytes((int) have);
+            HIP_TRY(b->lq_heard.grow(need_h, need_h / 4));
+            a.heard_scratch = b->lq_heard;
+            a.heard_scratch_bytes = b->lq_heard.bytes;
+            a.out_first = reinterpret_cast<int32_t *>(b->lq_out.p + at_first);
+            a.out_members = reinterpret_cast<gnuais_hearer *>(b->lq_out.p + at_members);
+        }
+        uint32_t info[UNIQUE_INFO_WORDS] = {0};
+        for (int exact = 0; exact < 2; ++exact) {
+            HIP_TRY(long_unique_cluster_enqueue(a, exact != 0, nullptr));
+            HIP_TRY(hipMemcpy(info, long_unique_info(a.scratch), sizeof info, hipMemcpyDeviceToHost));
+            if (!info[UNIQUE_INFO_COLLISION]) break;        // else: two keys share a hash -- once more, by the keys themselves
+        }
+        const uint32_t np = info[UNIQUE_INFO_PRIMARIES];
+        if (np > have || info[UNIQUE_INFO_TAIL] > m) return fail(GNUAIS_E_HIP, "drain_long_frames_unique: the stage's counts are out of range");
+        if (np) {
+            HIP_TRY(long_unique_deliver_enqueue(a, (int) np, nullptr));
+            HIP_TRY(hipMemcpy(h_out, a.out_frames, sizeof(gnuais_long_frame) * np, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+            if (h_first) {
+                HIP_TRY(hipMemcpy(h_first, a.out_first, sizeof(int32_t) * ((size_t) np + 1), hipMemcpyDeviceToHost));
+                const int32_t nm = h_first[np];
+                if (nm < 0 || (uint32_t) nm > have) return fail(GNUAIS_E_HIP, "drain_long_frames_heard: the stage's counts are out of range");
+                HIP_TRY(hipMemcpy(h_members, a.out_members, sizeof(gnuais_hearer) * (size_t) nm, hipMemcpyDeviceToHost));
+                *n_members = (int) nm;
+            }
+        }
+        unsigned long long late = 0;
+        memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
+        b->lq_cur ^= 1;
+        b->lq_n_tail = (int) info[UNIQUE_INFO_TAIL];
+        b->lq_late += (long long) late;
+        *n_out = (int) np;
+    }
+    HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
+    if (overflow) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: long-frame ring overflowed, frames were dropped", who);
+        return fail(GNUAIS_E_OVERFLOW, msg);
+    }
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_drain_long_frames_unique(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max > 0 && (!h_out || !h_copies)))
+        return fail(GNUAIS_E_ARG, "drain_long_frames_unique: argument");
+    return drain_long_unique_impl(b, h_out, h_copies, max, n_out, nullptr, nullptr, nullptr);
+}
+
+// the same drain with, for every cluster, the list of its members: who heard the long transmission, and when
+int gnuais_batch_drain_long_frames_heard(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
+                                         int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    if (!b || !n_out || !n_members || !h_first || max < 0 || (max > 0 && (!h_out || !h_copies || !h_members)))
+        return fail(GNUAIS_E_ARG, "drain_long_frames_heard: argument");
+    *n_members = 0;
+    h_first[0] = 0;
+    return drain_long_unique_impl(b, h_out, h_copies, max, n_out, h_first, h_members, n_members);
+}
+
 int gnuais_batch_drain_nmea(gnuais_batch *b, uint8_t *seqnr, char *out, size_t out_cap, size_t *out_len,
                             int *n_sentences, int *n_frames)
 {

@@ -83,6 +83,23 @@ static int read_out(gnuais_batch *b, const void *d, size_t n, std::vector<T> &v)
     return GNUAIS_OK;
 }
 
+// the long ring's two words and what they say: records held, and whether some were dropped (capi_delivery.hip's merged
+// drains read them too)
+int gnuais::long_pending(gnuais_batch *b, const char *who, uint32_t &have, bool &overflow)
+{
+    if (!b->long_ctl) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: the batch has never decoded long frames (gnuais_batch_long_frames)", who);
+        return fail(GNUAIS_E_STATE, msg);
+    }
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    uint32_t cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpy(cnt, b->long_count, sizeof cnt, hipMemcpyDeviceToHost));
+    have = std::min<uint32_t>(cnt[0], (uint32_t) b->long_cap);
+    overflow = cnt[1] || cnt[0] > (uint32_t) b->long_cap;
+    return GNUAIS_OK;
+}
+
 extern "C" {
 
 const char *gnuais_last_error(void) { return g_err.c_str(); }
@@ -371,6 +388,8 @@ int gnuais_batch_reset(gnuais_batch *b)
     if (b->repaired) HIP_TRY(hipMemset(b->repaired, 0, sizeof(int32_t) * N));
     b->uq_n_tail = 0;                           // gnuais_batch_unique: no open cluster, nothing late (the window stays)
     b->uq_late = 0;
+    b->lq_n_tail = 0;                           // gnuais_batch_long_unique: likewise, a state of its own
+    b->lq_late = 0;
     for (int q = 0; q < gnuais_batch::HB; ++q) HIP_TRY(hipMemset(b->maxval[q], 0, sizeof(int) * N));
     b->max_cur = 0;
     b->max_last = 0;
@@ -1188,6 +1207,8 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "long_cand_cap")) *value = b->long_cand_cap ? b->long_cand_cap : long_ring_capacity(b);
     else if (!strcmp(name, "unique")) *value = b->uq_window;
     else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
+    else if (!strcmp(name, "long_unique")) *value = b->lq_window;
+    else if (!strcmp(name, "long_unique_late")) *value = (double) b->lq_late;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now
         *value = -1;
@@ -1245,6 +1266,9 @@ int gnuais_batch_long_frames(gnuais_batch *b, int on)
     HIP_TRY(hipStreamSynchronize(nullptr));
     b->long_frames = on != 0;
     if (!on) b->long_repair = false;            // gnuais_batch_long_repair: nothing to repair without D'
+    if (!on) b->lq_window = 0;                  // gnuais_batch_long_unique: nothing to merge either
+    b->lq_n_tail = 0;                           // any switch: the ring starts over, and so do the merge's tail and late count
+    b->lq_late = 0;
     return GNUAIS_OK;
 }
 
@@ -1289,22 +1313,6 @@ int gnuais_batch_long_repaired(gnuais_batch *b, int32_t *h_out)
 }
 
 static_assert(sizeof(gnuais_long_frame) == 152 && sizeof(gnuais_long_frame) == 4 * LONG_FRAME_WORDS, "gnuais_long_frame layout");
-
-// the long ring's two words and what they say: records held, and whether some were dropped
-static int long_pending(gnuais_batch *b, const char *who, uint32_t &have, bool &overflow)
-{
-    if (!b->long_ctl) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: the batch has never decoded long frames (gnuais_batch_long_frames)", who);
-        return fail(GNUAIS_E_STATE, msg);
-    }
-    if (int rc = gnuais_batch_sync(b)) return rc;
-    uint32_t cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpy(cnt, b->long_count, sizeof cnt, hipMemcpyDeviceToHost));
-    have = std::min<uint32_t>(cnt[0], (uint32_t) b->long_cap);
-    overflow = cnt[1] || cnt[0] > (uint32_t) b->long_cap;
-    return GNUAIS_OK;
-}
 
 int gnuais_batch_pending_long_frames(gnuais_batch *b, int *n_out)
 {
@@ -1398,6 +1406,28 @@ int gnuais_batch_unique(gnuais_batch *b, int window_rows)
     b->uq_window = window_rows;
     b->uq_n_tail = 0;
     b->uq_late = 0;
+    return GNUAIS_OK;
+}
+
+// The duplicate merge of the long frames on / off (definition in include/gnuais_hip.h).  Like gnuais_batch_unique: the
+// switch sets the window and empties the carried state -- a tail and a late count of its own.
+int gnuais_batch_long_unique(gnuais_batch *b, int window_rows)
+{
+    if (!b || window_rows < 0) return fail(GNUAIS_E_ARG, "long_unique: NULL batch or a negative window");
+    if (!b->long_frames)
+        return fail(GNUAIS_E_STATE, "long_unique: the batch does not decode long frames (gnuais_batch_long_frames): "
+                                    "the merge works on that decoder's records");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    b->lq_window = window_rows;
+    b->lq_n_tail = 0;
+    b->lq_late = 0;
+    return GNUAIS_OK;
+}
+
+int gnuais_batch_long_unique_late(gnuais_batch *b, long long *late)
+{
+    if (!b || !late) return fail(GNUAIS_E_ARG, "long_unique_late: argument");
+    *late = b->lq_late;
     return GNUAIS_OK;
 }
 

@@ -430,4 +430,33 @@ uint32_t *unique_info(void *scratch);
 hipError_t unique_cluster_enqueue(const UniqueLaunch &a, bool exact, hipStream_t s);
 hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStream_t s);
 
+// ---- the same merge over the long frames (frame_unique_long.hip; gnuais_batch_long_unique in include/gnuais_hip.h) ----
+// Entries = [tail | long ring]: a tail entry is a 38-word record with t_last in its t words and word 4 masked to the key;
+// the member time is the record's own t, there are no times and no signal records.  The two calls, the info words
+// (UNIQUE_INFO_*) and the repeat in the exact form are those of the stage above.  Every buffer is 8-byte aligned.
+struct LongUniqueLaunch {
+    const void *frames;            // gnuais_long_frame[have]: the long ring
+    int have;
+    const void *tail;              // [n_tail][38] words
+    int n_tail;
+    void *tail_out;                // room for n_tail + have entries, another buffer than tail
+    long long window, rows;
+    int hash_bits;
+    int ch_bits, time_bits;
+    void *scratch;
+    size_t scratch_bytes;          // >= long_unique_scratch_bytes(n_tail + have)
+    struct gnuais_long_frame *out_frames;
+    int32_t *out_copies;
+    // the member lists (gnuais_batch_drain_long_frames_heard); out_first null: no lists wanted
+    void *heard_scratch = nullptr;
+    size_t heard_scratch_bytes = 0;             // >= long_unique_heard_scratch_bytes(have)
+    int32_t *out_first = nullptr;
+    struct gnuais_hearer *out_members = nullptr;
+};
+size_t long_unique_scratch_bytes(int n_entries);
+size_t long_unique_heard_scratch_bytes(int have);
+uint32_t *long_unique_info(void *scratch);
+hipError_t long_unique_cluster_enqueue(const LongUniqueLaunch &a, bool exact, hipStream_t s);
+hipError_t long_unique_deliver_enqueue(const LongUniqueLaunch &a, int n_primaries, hipStream_t s);
+
 } // namespace gnuais

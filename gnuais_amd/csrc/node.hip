@@ -189,6 +189,9 @@ struct gnuais_node {
     std::vector<gnuais_frame> uq_frames;
     std::vector<int64_t> uq_times;
     std::vector<gnuais_frame_signal> uq_signal;     // gnuais_node_drain_frames_heard: the members' records
+    // gnuais_node_long_unique: the same for the long frames -- the shards' plain long drains, then one gnuais_long_uniq
+    gnuais_long_uniq *lq = nullptr;
+    std::vector<gnuais_long_frame> lq_frames;
 };
 
 extern "C" {
@@ -225,6 +228,7 @@ void gnuais_node_destroy(gnuais_node *nd)
 {
     if (!nd) return;
     gnuais_uniq_destroy(nd->uq);
+    gnuais_long_uniq_destroy(nd->lq);
     for (Shard *s : nd->shards) {
         if (s->w.th.joinable()) {
             s->w.submit([s] {
@@ -318,6 +322,7 @@ int gnuais_node_reset(gnuais_node *nd)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_reset: NULL");
     if (nd->uq) (void) gnuais_uniq_reset(nd->uq);
+    if (nd->lq) (void) gnuais_long_uniq_reset(nd->lq);
     return run_all(nd, [](Shard &s, size_t) { return gnuais_batch_reset(s.b); });
 }
 
@@ -584,6 +589,12 @@ int gnuais_node_repaired(gnuais_node *nd, int32_t *h_out)
 int gnuais_node_long_frames(gnuais_node *nd, int on)
 {
     if (!nd) return node_fail(GNUAIS_E_ARG, "node_long_frames: NULL node");
+    // any switch empties gnuais_node_long_unique's carried state; switching long frames off switches that off
+    if (nd->lq) (void) gnuais_long_uniq_reset(nd->lq);
+    if (!on) {
+        gnuais_long_uniq_destroy(nd->lq);
+        nd->lq = nullptr;
+    }
     return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_long_frames(s.b, on); });
 }
 
@@ -775,6 +786,72 @@ int gnuais_node_drain_frames_heard(gnuais_node *nd, gnuais_frame *h_out, int64_t
     *n_members = 0;
     h_first[0] = 0;
     return node_drain_unique(nd, h_out, h_times, h_copies, max, n_out, h_first, h_members, n_members);
+}
+
+// One record per long transmission over the whole node (gnuais_batch_long_unique's definition): the shards' plain long
+// drains merged, then the host object.  window_rows = 0 switches it off; switching clears the tail and the late count.
+int gnuais_node_long_unique(gnuais_node *nd, int window_rows)
+{
+    if (!nd || window_rows < 0) return node_fail(GNUAIS_E_ARG, "node_long_unique: NULL node or a negative window");
+    for (Shard *s : nd->shards) {
+        double on = 0;
+        if (gnuais_batch_info(s->b, "long_frames", &on) != GNUAIS_OK || on == 0)
+            return node_fail(GNUAIS_E_STATE, "node_long_unique: the node does not decode long frames (gnuais_node_long_frames)");
+    }
+    gnuais_long_uniq_destroy(nd->lq);
+    nd->lq = nullptr;
+    if (window_rows && gnuais_long_uniq_create(&nd->lq, window_rows) != GNUAIS_OK)
+        return node_fail(GNUAIS_E_ARG, "node_long_unique: the merge object could not be made");
+    return GNUAIS_OK;
+}
+
+int gnuais_node_long_unique_late(gnuais_node *nd, long long *late)
+{
+    if (!nd || !late) return node_fail(GNUAIS_E_ARG, "node_long_unique_late: argument");
+    *late = gnuais_long_uniq_late(nd->lq);
+    return GNUAIS_OK;
+}
+
+// h_first: with the clusters' member lists (gnuais_node_drain_long_frames_heard)
+static int node_drain_long_unique(gnuais_node *nd, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
+                                  int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    *n_out = 0;
+    if (!nd->lq) return node_fail(GNUAIS_E_STATE, "node_drain_long_frames_unique: the node does not merge long frames (gnuais_node_long_unique)");
+    std::vector<int> pend(nd->shards.size(), 0);
+    if (int rc = run_all(nd, [&](Shard &s, size_t i) { return gnuais_batch_pending_long_frames(s.b, &pend[i]); })) return rc;
+    long long total = 0;
+    for (int v : pend) total += v;
+    if (total > max) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_unique: buffers too small (one entry per pending long frame always suffices)");
+    nd->lq_frames.resize((size_t) total + 1);
+    int got = 0;
+    const int rc = gnuais_node_drain_long_frames(nd, nd->lq_frames.data(), (int) total, &got);
+    if (rc != GNUAIS_OK && rc != GNUAIS_E_OVERFLOW) return rc;
+    double rows = 0;                    // a node's run calls give every shard the same rows
+    if (gnuais_batch_info(nd->shards[0]->b, "rows", &rows) != GNUAIS_OK) return node_fail(GNUAIS_E_STATE, "node_drain_long_frames_unique: rows");
+    const int pushed = h_first ? gnuais_long_uniq_push_heard(nd->lq, nd->lq_frames.data(), got, (long long) rows, h_out, h_copies,
+                                                             max, n_out, h_first, h_members, n_members)
+                               : gnuais_long_uniq_push(nd->lq, nd->lq_frames.data(), got, (long long) rows, h_out, h_copies, max,
+                                                       n_out);
+    if (pushed != GNUAIS_OK) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_unique: the merge refused its input");
+    return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
+}
+
+int gnuais_node_drain_long_frames_unique(gnuais_node *nd, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max > 0 && (!h_out || !h_copies)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_unique: argument");
+    return node_drain_long_unique(nd, h_out, h_copies, max, n_out, nullptr, nullptr, nullptr);
+}
+
+int gnuais_node_drain_long_frames_heard(gnuais_node *nd, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
+                                        int32_t *h_first, gnuais_hearer *h_members, int *n_members)
+{
+    if (!nd || !n_out || !n_members || !h_first || max < 0 || (max > 0 && (!h_out || !h_copies || !h_members)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_heard: argument");
+    *n_members = 0;
+    h_first[0] = 0;
+    return node_drain_long_unique(nd, h_out, h_copies, max, n_out, h_first, h_members, n_members);
 }
 
 // Streamed sentences of the whole node: gnuais_batch_stream_nmea() on every shard, each from its own thread.  Shard g's

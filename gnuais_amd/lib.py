@@ -131,6 +131,16 @@ SYMBOLS = {
     "gnuais_uniq_late": (C.c_longlong, [_P]),
     "gnuais_batch_drain_frames_heard": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
     "gnuais_uniq_push_heard": (_I, [_P, _P, _P, _P, _I, C.c_longlong, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_batch_long_unique": (_I, [_P, _I]),
+    "gnuais_batch_drain_long_frames_unique": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_batch_drain_long_frames_heard": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_batch_long_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "gnuais_long_uniq_create": (_I, [C.POINTER(_P), C.c_longlong]),
+    "gnuais_long_uniq_destroy": (None, [_P]),
+    "gnuais_long_uniq_reset": (_I, [_P]),
+    "gnuais_long_uniq_push": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_long_uniq_push_heard": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_long_uniq_late": (C.c_longlong, [_P]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
     "gnuais_batch_counters": (_I, [_P, _P]),
     "gnuais_batch_total_received": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -205,6 +215,10 @@ SYMBOLS = {
     "gnuais_node_drain_frames_unique": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
     "gnuais_node_drain_frames_heard": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_node_long_unique": (_I, [_P, _I]),
+    "gnuais_node_drain_long_frames_unique": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_drain_long_frames_heard": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_node_long_unique_late": (_I, [_P, C.POINTER(C.c_longlong)]),
     "gnuais_node_stream_nmea": (_I, [_P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "gnuais_node_discard_frames": (_I, [_P]),
     "gnuais_node_counters": (_I, [_P, _P]),

@@ -525,6 +525,54 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_unique_late(self._h, C.byref(v)))
         return v.value
 
+    def long_unique(self, window: int):
+        """gnuais_batch_long_unique(): window > 0 rows: drain_long_frames_unique() delivers each long transmission once
+        (equal long frames whose own times t chain within the window; the definition is in include/gnuais_hip.h); 0:
+        off.  Needs long_frames(); clears the carried state, which is this merge's own.  Synchronises."""
+        check(self._lib.gnuais_batch_long_unique(self._h, int(window)))
+
+    def _drain_long_merged(self, heard: bool):
+        n = max(self.pending_long_frames(), 1)
+        out = np.zeros(n, dtype=LONG_FRAME_DTYPE)
+        copies = np.zeros(n, dtype=np.int32)
+        got, nm = C.c_int(), C.c_int()
+        if heard:
+            first = np.zeros(n + 1, dtype=np.int32)
+            members = np.zeros(n, dtype=_lib.HEARER_DTYPE)
+            rc = self._lib.gnuais_batch_drain_long_frames_heard(self._h, out.ctypes.data, copies.ctypes.data, n,
+                                                                C.byref(got), first.ctypes.data, members.ctypes.data,
+                                                                C.byref(nm))
+            res = (out[: got.value].copy(), copies[: got.value].copy(), first[: got.value + 1].copy(),
+                   members[: nm.value].copy())
+        else:
+            rc = self._lib.gnuais_batch_drain_long_frames_unique(self._h, out.ctypes.data, copies.ctypes.data, n,
+                                                                 C.byref(got))
+            res = (out[: got.value].copy(), copies[: got.value].copy())
+        if rc == E_OVERFLOW:
+            err = GnuaisError(rc, self._lib.gnuais_last_error().decode())
+            err.frames = res
+            raise err
+        check(rc)
+        return res
+
+    def drain_long_frames_unique(self):
+        """gnuais_batch_drain_long_frames_unique(): (records, int32 copies): one LONG_FRAME_DTYPE record per long
+        transmission -- the earliest intact copy, with its own t -- and how many copies this drain merged into it.
+        GnuaisError(E_OVERFLOW) carries what was delivered in `.frames`."""
+        return self._drain_long_merged(False)
+
+    def drain_long_frames_heard(self):
+        """gnuais_batch_drain_long_frames_heard(): (records, int32 copies, int32 first, members) -- what
+        drain_long_frames_unique() delivers, and who heard each transmission: cluster i's members are
+        members[first[i]:first[i + 1]] (lib.HEARER_DTYPE: channel, flags, t; signal is all zero) in the order (t, channel)"""
+        return self._drain_long_merged(True)
+
+    def long_unique_late(self) -> int:
+        """gnuais_batch_long_unique_late(): long copies that arrived after a drain had delivered their transmission"""
+        v = C.c_longlong()
+        check(self._lib.gnuais_batch_long_unique_late(self._h, C.byref(v)))
+        return v.value
+
     def time_map(self, kind: str = "audio"):
         """gnuais_batch_time_map(): (mul, off) with input sample index = t * mul + off for the batch's configuration as
         it is now; kind: "audio", "iq" or "wideband"."""
@@ -891,3 +939,61 @@ class Uniq:
             raise _lib.GnuaisError(rc, "gnuais_uniq_push_heard: argument, or more records than cap")
         return (out[: got.value].copy(), out_t[: got.value].copy(), out_c[: got.value].copy(),
                 first[: got.value + 1].copy(), members[: nm.value].copy())
+
+
+class LongUniq:
+    """gnuais_long_uniq: the duplicate merge of gnuais_batch_long_unique() as a host object, no device
+    (include/gnuais_hip.h).  push() is one drain of the definition; a record's time is its own t."""
+
+    def __init__(self, window: int):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.gnuais_long_uniq_create(C.byref(self._h), int(window))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_long_uniq_create: the window must be > 0")
+
+    def close(self):
+        if self._h:
+            self._lib.gnuais_long_uniq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        self._lib.gnuais_long_uniq_reset(self._h)
+
+    def late(self) -> int:
+        return int(self._lib.gnuais_long_uniq_late(self._h))
+
+    def push(self, frames: np.ndarray, rows: int, cap: Optional[int] = None):
+        """-> (records, copies) of the clusters this drain delivers; cap: room offered (default: enough)"""
+        frames = np.ascontiguousarray(frames, dtype=LONG_FRAME_DTYPE)
+        assert frames.ndim == 1
+        n = int(frames.size)
+        cap = n if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=LONG_FRAME_DTYPE)
+        out_c = np.zeros(max(cap, 1), dtype=np.int32)
+        got = C.c_int()
+        rc = self._lib.gnuais_long_uniq_push(self._h, frames.ctypes.data, n, int(rows), out.ctypes.data, out_c.ctypes.data,
+                                             cap, C.byref(got))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_long_uniq_push: argument, or more records than cap")
+        return out[: got.value].copy(), out_c[: got.value].copy()
+
+    def push_heard(self, frames: np.ndarray, rows: int, cap: Optional[int] = None):
+        """-> (records, copies, first, members): push() with the clusters' member lists (gnuais_long_uniq_push_heard)"""
+        frames = np.ascontiguousarray(frames, dtype=LONG_FRAME_DTYPE)
+        assert frames.ndim == 1
+        n = int(frames.size)
+        cap = n if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=LONG_FRAME_DTYPE)
+        out_c = np.zeros(max(cap, 1), dtype=np.int32)
+        first = np.zeros(cap + 1, dtype=np.int32)
+        members = np.zeros(max(n, 1), dtype=_lib.HEARER_DTYPE)
+        got, nm = C.c_int(), C.c_int()
+        rc = self._lib.gnuais_long_uniq_push_heard(self._h, frames.ctypes.data, n, int(rows), out.ctypes.data,
+                                                   out_c.ctypes.data, cap, C.byref(got), first.ctypes.data,
+                                                   members.ctypes.data, C.byref(nm))
+        if rc != _lib.OK:
+            raise _lib.GnuaisError(rc, "gnuais_long_uniq_push_heard: argument, or more records than cap")
+        return out[: got.value].copy(), out_c[: got.value].copy(), first[: got.value + 1].copy(), members[: nm.value].copy()

@@ -338,6 +338,48 @@ class ReceiverNode:
         self._raise(self._lib.gnuais_node_unique_late(self._h, self._C.byref(t)))
         return t.value
 
+    def long_unique(self, window: int):
+        """gnuais_node_long_unique(): each long transmission once over the whole node (the shards' long drains merged on
+        the host); window in rows, 0 = off.  Needs long_frames()."""
+        self._raise(self._lib.gnuais_node_long_unique(self._h, int(window)))
+
+    def _drain_long_merged(self, heard: bool):
+        """the node has no count of its long frames: the buffers double until the call takes them (a refused call
+        consumes nothing)"""
+        from .lib import E_ARG, HEARER_DTYPE, LONG_FRAME_DTYPE
+        np_, n = self._np, 1024
+        while True:
+            out, copies = np_.zeros(n, dtype=LONG_FRAME_DTYPE), np_.zeros(n, dtype=np_.int32)
+            first, members = np_.zeros(n + 1, dtype=np_.int32), np_.zeros(n, dtype=HEARER_DTYPE)
+            got, nm = self._C.c_int(), self._C.c_int()
+            if heard:
+                rc = self._lib.gnuais_node_drain_long_frames_heard(self._h, out.ctypes.data, copies.ctypes.data, n,
+                                                                   self._C.byref(got), first.ctypes.data,
+                                                                   members.ctypes.data, self._C.byref(nm))
+            else:
+                rc = self._lib.gnuais_node_drain_long_frames_unique(self._h, out.ctypes.data, copies.ctypes.data, n,
+                                                                    self._C.byref(got))
+            if rc == E_ARG and n < 1 << 24:
+                n *= 4
+                continue
+            self._raise(rc)
+            res = (out[: got.value].copy(), copies[: got.value].copy())
+            return res + (first[: got.value + 1].copy(), members[: nm.value].copy()) if heard else res
+
+    def drain_long_frames_unique(self):
+        """gnuais_node_drain_long_frames_unique(): (records, int32 copies), one record per long transmission"""
+        return self._drain_long_merged(False)
+
+    def drain_long_frames_heard(self):
+        """gnuais_node_drain_long_frames_heard(): (records, int32 copies, int32 first, members): the unique drain and, per
+        transmission, the receivers that heard it (lib.HEARER_DTYPE, global channel numbers)"""
+        return self._drain_long_merged(True)
+
+    def long_unique_late(self) -> int:
+        t = self._C.c_longlong()
+        self._raise(self._lib.gnuais_node_long_unique_late(self._h, self._C.byref(t)))
+        return t.value
+
     def time_map(self, kind: str = "audio"):
         """gnuais_batch_time_map() of the first shard: every shard has the node's configuration"""
         from .lib import INPUT_KINDS, check

@@ -391,7 +391,8 @@ int  gnuais_batch_last_signs(gnuais_batch *b, uint8_t *h_out, int stride);
  * "frame_signal" (gnuais_batch_frame_signal(); 0 = off), "occupancy" (gnuais_batch_occupancy(); epoch_blocks, 0 = off),
  * "repair" (gnuais_batch_repair(); 0 = off), "long_repair" (gnuais_batch_long_repair(); 0 = off), "long_cand_cap" (the
  * candidate records one call of that repair can list), "unique" (gnuais_batch_unique(); the window, 0 = off), "unique_late"
- * (gnuais_batch_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
+ * (gnuais_batch_unique_late()), "long_unique" (gnuais_batch_long_unique(); the window, 0 = off), "long_unique_late"
+ * (gnuais_batch_long_unique_late()), "pll_form" (the form the PLL launch of the last run call took: 7 the time-parallel
  * one, 8 the lane-per-channel one; 0 before any call and after a reset) */
 int  gnuais_batch_info(const gnuais_batch *b, const char *name, double *value);
 
@@ -688,11 +689,11 @@ int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload
  *     l_s / (2 c_s)): D''s kernel walks a call's segments in order and knows s, j, l_s and c_s of the closing bit itself,
  *     so t is filled in whether gnuais_batch_frame_times is on or off.  t = -1 for a frame closed by
  *     gnuais_batch_decode_bits.
- *   Not in this section.  For long frames there is no duplicate merge and no member
- *     lists (gnuais_batch_unique), no signal record and no share in the channel load (gnuais_batch_frame_signal,
- *     gnuais_batch_occupancy), no stdout text line, no device formatter (gnuais_batch_drain_nmea and its family), no
- *     entry in the vessel tables and no streamed delivery.  t and the stamp are in the record, so a host can do these
- *     itself.
+ *   Not in this section.  The duplicate merge and the member lists of the long frames have a section of their own
+ *     (gnuais_batch_long_unique, below).  For long frames there is no signal record and no share in the channel load
+ *     (gnuais_batch_frame_signal, gnuais_batch_occupancy), no stdout text line, no device formatter
+ *     (gnuais_batch_drain_nmea and its family), no entry in the vessel tables and no streamed delivery.  t and the stamp
+ *     are in the record, so a host can do these itself.
  * gnuais_batch_long_frames(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE on a streaming batch, and
  *   while it is on the batch cannot start streaming (gnuais_batch_stream_nmea, gnuais_batch_autotune_delivery and
  *   set_option("streaming", 1) return GNUAIS_E_STATE): the streamed delivery carries no records of long frames.  One more
@@ -869,6 +870,73 @@ int  gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const in
                             const gnuais_frame_signal *signal /* NULL: zeros */, int n, long long rows, gnuais_frame *out,
                             int64_t *out_times, int32_t *out_copies, int cap, int *n_out, int32_t *out_first,
                             gnuais_hearer *out_members, int *n_members);
+
+/* ---- each long transmission once: the copies of the long frames merged, with who heard them -----------------------------
+ * Long messages are broadcasts -- area notices and met/hydro data (type 8), DGNSS corrections (17), safety text (14) -- and
+ * a whole region of receivers hears each one.  This section is gnuais_batch_unique and gnuais_batch_drain_frames_heard
+ * for the records of gnuais_batch_long_frames, statement by statement, with exactly these differences.  Off by default;
+ * nothing runs per call, the stage is the drain; every other entry is unchanged.
+ *   Record words.  A gnuais_long_frame is 38 32-bit words: w0 channel, w1 end_bit, w2..3 t, w4 nbits | flags << 16 |
+ *     reserved << 24, w5..37 the 132 payload bytes.
+ *   Key of a long frame: nbits and the 132 payload bytes: w4 & 0xffff and w5..w37 -- 34 words, 17 pairs.  channel,
+ *     end_bit, t, flags and reserved are not part of it: an intact copy and a repaired copy (GNUAIS_FRAME_REPAIRED, flags
+ *     bit 6, from gnuais_batch_long_repair) share a key.
+ *   Time.  The member time is the record's own t, which D' always fills: gnuais_batch_frame_times is NOT needed.  A
+ *     record with t = -1 (a frame closed by gnuais_batch_decode_bits) is a cluster by itself, copies = 1; those clusters
+ *     come first in the output, in the plain long drain's order (channel, then the 37-bit stamp).
+ *   Taken over unchanged: the member order (t, channel); the chain rule t_i - t_{i-1} <= W; the primary, the first member
+ *     in (flags bit 6, t, channel); the output order of the timed primaries, (t, channel); the tail rule across drains
+ *     with n = "rows" of the batch; `late`, the copies that chain onto a tail entry; a cluster is listed by the drain that
+ *     delivers it; no result depends on the hash or on the order in which records entered the ring.
+ *   THE PROPERTY RELIED ON across drains: every t of a drain lies in [rows before the first call it covers, rows at the
+ *     drain): D' computes t by the frame-time formula at its closing bit, a row of the call that closed the frame
+ *     (tests/test_long_unique_cpu.py asserts it on the reference).
+ *   Member: a gnuais_hearer -- channel, the copy's own flags, the copy's t.  signal = (0, 0, 0) always: long frames have
+ *     no signal record.
+ *   State.  The long stage has a tail and a `late` counter of its own, independent of gnuais_batch_unique's.
+ *     gnuais_batch_reset() clears both; gnuais_batch_protodec_reset() keeps both; any switch of gnuais_batch_long_frames
+ *     clears them, and switching long frames off switches this feature off, as it does gnuais_batch_long_repair;
+ *     switching the feature itself (off, on, or to another window) clears them.  Records consumed by
+ *     gnuais_batch_drain_long_frames() are never seen by the stage; that drain and the two below may be mixed from drain
+ *     to drain.
+ *   Invariant.  Over any placement of drains, sum(copies) + late = the records gnuais_batch_drain_long_frames() would
+ *     have delivered, and the set of clusters is that of one drain over everything.
+ *   Exactness: as above; where two different keys share a hash the drain repeats its grouping by the 17 pairs of key
+ *     words.  set_option("unique_hash_bits", k) truncates this stage's hash too.
+ * gnuais_batch_long_unique(window_rows): > 0 switches the feature on with that window, 0 off; synchronises.
+ *   GNUAIS_E_STATE unless gnuais_batch_long_frames is on.  info "long_unique" (the window, 0 = off) and "long_unique_late".
+ * gnuais_batch_drain_long_frames_unique(): consumes the queued long frames like gnuais_batch_drain_long_frames();
+ *   h_out[i], h_copies[i] describe cluster i.  GNUAIS_E_STATE while the feature is off; GNUAIS_E_ARG, consuming nothing
+ *   and leaving tail and `late` unchanged, when max is smaller than the number of pending long frames (the upper bound).
+ *   A ring that overflowed is reported as gnuais_batch_drain_long_frames() reports it: GNUAIS_E_OVERFLOW, with what the
+ *   ring held, merged.  156 bytes per delivered record cross PCIe.
+ * gnuais_batch_drain_long_frames_heard(): the same drain with the clusters' member lists in CSR form, as
+ *   gnuais_batch_drain_frames_heard(): h_first[0] = 0, h_first[i + 1] - h_first[i] = h_copies[i], cluster i's members are
+ *   h_members[h_first[i] .. h_first[i + 1]) in member order, *n_members = h_first[*n_out]; its first two outputs and
+ *   *n_out are those of the unique drain for the same state, byte for byte.  4 more bytes per record and 24 per member
+ *   cross PCIe.
+ * gnuais_batch_long_unique_late(): `late` since the feature was switched on / the last reset.
+ * gnuais_long_uniq: the same merge as a host object, no device: _push() is one drain of the definition over frames[n] in
+ *   any order with rows = n of the definition; at most cap records are written (GNUAIS_E_ARG, with the object unchanged,
+ *   when the push would deliver more).  _push_heard(): with the lists; out_first has cap + 1 entries, out_members n.  The
+ *   device drains equal them bit for bit. */
+int  gnuais_batch_long_unique(gnuais_batch *b, int window_rows);
+int  gnuais_batch_drain_long_frames_unique(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max,
+                                           int *n_out);
+int  gnuais_batch_drain_long_frames_heard(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max,
+                                          int *n_out, int32_t *h_first /* [max + 1] */,
+                                          gnuais_hearer *h_members /* [max] */, int *n_members);
+int  gnuais_batch_long_unique_late(gnuais_batch *b, long long *late);
+typedef struct gnuais_long_uniq gnuais_long_uniq;
+int  gnuais_long_uniq_create(gnuais_long_uniq **out, long long window);
+void gnuais_long_uniq_destroy(gnuais_long_uniq *u);
+int  gnuais_long_uniq_reset(gnuais_long_uniq *u);
+int  gnuais_long_uniq_push(gnuais_long_uniq *u, const gnuais_long_frame *frames, int n, long long rows,
+                           gnuais_long_frame *out, int32_t *out_copies, int cap, int *n_out);
+int  gnuais_long_uniq_push_heard(gnuais_long_uniq *u, const gnuais_long_frame *frames, int n, long long rows,
+                                 gnuais_long_frame *out, int32_t *out_copies, int cap, int *n_out, int32_t *out_first,
+                                 gnuais_hearer *out_members, int *n_members);
+long long gnuais_long_uniq_late(const gnuais_long_uniq *u);
 
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
@@ -1142,6 +1210,17 @@ int  gnuais_node_unique_late(gnuais_node *nd, long long *late);
 int  gnuais_node_drain_frames_heard(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max,
                                     int *n_out, int32_t *h_first /* [max + 1] */, gnuais_hearer *h_members /* [max] */,
                                     int *n_members);
+/* gnuais_batch_long_unique()'s definition over the whole node, as gnuais_node_unique does it for the chain's frames: the
+ * shards' plain long drains (gnuais_node_drain_long_frames) into a host buffer, then one gnuais_long_uniq kept in the
+ * node, with the node's rows.  _long_unique() needs gnuais_node_long_frames on (else GNUAIS_E_STATE); switching that
+ * switches this off; gnuais_node_reset() clears the tail and `late`.  The shards' own gnuais_batch_long_unique stays
+ * off.  The two drains share the carried state and may be mixed.  Channel numbers are global. */
+int  gnuais_node_long_unique(gnuais_node *nd, int window_rows);
+int  gnuais_node_drain_long_frames_unique(gnuais_node *nd, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out);
+int  gnuais_node_drain_long_frames_heard(gnuais_node *nd, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
+                                         int32_t *h_first /* [max + 1] */, gnuais_hearer *h_members /* [max] */,
+                                         int *n_members);
+int  gnuais_node_long_unique_late(gnuais_node *nd, long long *late);
 /* gnuais_batch_stream_nmea() on every shard (each from its own thread): texts[g] / lens[g] = shard g's sentences of
  * the call `stream_depth` calls ago (n_devices entries; valid until the next call).  Written out in shard order they
  * are the node's sentences in the reference's order for that call: shard g's channels all lie before shard g+1's and

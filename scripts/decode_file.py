@@ -58,7 +58,12 @@
                                                       # decoder and so the chain give up on: a second decoder on the device
                                                       # (gnuais_batch_long_frames) delivers them, and their two or three
                                                       # sentences follow each call's other sentences -- behind TAG blocks of
-                                                      # their own when --times is given; the summary counts them
+                                                      # their own when --times is given; the summary counts them.  With
+                                                      # --unique ROWS the copies of a long transmission are merged on the
+                                                      # device as well (gnuais_batch_long_unique) and its sentences are
+                                                      # printed once; with --heard a "  heard:" line follows them (receiver,
+                                                      # rows behind the printed copy, r = repaired; long frames carry no
+                                                      # signal record); the summary counts transmissions, copies and late copies
   ... --long-repair
                                                       # --long, and a long frame that fails its CRC by one wrong symbol is
                                                       # repaired on the device (gnuais_batch_long_repair); the summary counts
@@ -185,6 +190,8 @@ def main():
         b.long_frames(True)
     if a.long_repair:
         b.long_repair(True)
+    if a.long and a.unique:
+        b.long_unique(a.unique)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -201,7 +208,9 @@ def main():
     afc_report(a, b, 48000)
     if a.long:
         sys.stderr.write(f"{getattr(a, 'long_frames', 0)} long frames (more than two slots)"
-                         + (f", {getattr(a, 'long_repaired', 0)} of them repaired" if a.long_repair else "") + "\n")
+                         + (f", {getattr(a, 'long_repaired', 0)} of them repaired" if a.long_repair else "")
+                         + (f", printed once from {getattr(a, 'long_copies', 0)} copies, {b.long_unique_late()} more copies "
+                            "came after their transmission was printed" if a.unique else "") + "\n")
 
 
 def write_sentences(a, b, seq, kind, rate):
@@ -248,7 +257,18 @@ def write_long(a, b, seq, kind, rate):
     if not a.long:
         return
     from gnuais_amd.receiver import nmea_from_long_frames
-    frames = b.drain_long_frames()
+    first = members = None
+    if a.unique and a.heard:                                # each long transmission once, and who heard it
+        frames, copies, first, members = b.drain_long_frames_heard()
+    elif a.unique:
+        frames, copies = b.drain_long_frames_unique()
+    else:
+        frames = b.drain_long_frames()
+    if a.unique:
+        a.long_copies = getattr(a, "long_copies", 0) + int(copies.sum())
+        if a.verbose:
+            for f, c in zip(frames, copies):
+                sys.stderr.write(f"  copies {int(c)}: receiver {int(f['channel'])}, row {int(f['t'])}, {int(f['nbits'])} bits\n")
     a.long_frames = getattr(a, "long_frames", 0) + len(frames)
     a.long_repaired = getattr(a, "long_repaired", 0) + int(((frames["flags"] & 0x40) != 0).sum())
     num, den, off = b.time_map_ratio(kind) if a.times else (1, 1, 0)
@@ -263,6 +283,10 @@ def write_long(a, b, seq, kind, rate):
             tag = f"\\{body}*{chk:02X}\\"
             text = "".join(tag + line + "\r\n" for line in text.split("\r\n")[:-1])
         sys.stdout.write(text)
+        if members is not None:                             # as write_heard: receiver, rows behind the primary, r = repaired
+            who = [f"{int(m['channel'])} {int(m['t']) - t:+d}" + ("r" if int(m["flags"]) & 0x40 else "")
+                   for m in members[first[i]:first[i + 1]]]
+            sys.stdout.write("  heard: " + ", ".join(who) + "\n")
 
 
 def write_heard(a, b, seq, kind, rate):
@@ -372,6 +396,8 @@ def decode_wideband(a, rate, x, fmt=None):
         b.long_frames(True)
     if a.long_repair:
         b.long_repair(True)
+    if a.long and a.unique:
+        b.long_unique(a.unique)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
