@@ -136,6 +136,34 @@ class LongDeframer:
                 sum(1 for f in self.closed if f["n"] > SHORT_BITS and not f["good"]))
 
 
+class SampleRef:
+    """the restatement behind the samples: the oracle's slices segment by segment into one LongDeframer per channel, and
+    the definition's t from where each closing bit lies"""
+
+    def __init__(self, n_ch, rows=0, bits=None):
+        from oracle_lib import Oracle
+        self.o = Oracle(n_ch)
+        self.n = rows
+        self.ds = [LongDeframer(seen=0 if bits is None else int(bits[c])) for c in range(n_ch)]
+        self.segs = [[] for _ in range(n_ch)]               # per channel: (bits fed before, first row, rows, bits)
+
+    def run(self, x):
+        import frame_time_ref as ftr
+        for s0 in range(0, x.shape[0], ftr.SEG):
+            seg = np.ascontiguousarray(x[s0:s0 + ftr.SEG])
+            for c, bits in enumerate(self.o.run(seg, want_bits=True)["bits"]):
+                self.segs[c].append((self.ds[c].fed, self.n + s0, seg.shape[0], len(bits)))
+                self.ds[c].feed(bits)
+        self.n += x.shape[0]
+
+    def t(self, c, f):
+        import frame_time_ref as ftr
+        for fed, row0, l_s, cnt in self.segs[c]:
+            if fed <= f["index"] < fed + cnt:
+                return ftr.interp(row0, 0, f["index"] - fed, l_s, cnt)
+        raise AssertionError((c, f["index"]))
+
+
 def record(channel, f, t=-1):
     """the 152-byte record of a closed frame as a LONG_FRAME_DTYPE scalar"""
     r = np.zeros((), dtype=LONG_FRAME_DTYPE)

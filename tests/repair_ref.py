@@ -210,17 +210,25 @@ def record(channel, end_bit, n, payload, repaired=False):
 def decode_streams(bit_streams):
     """Deframer over each channel's bits.  Returns (frames, repairs, counters): frames = the good frames and the repaired
     ones as records in drain order (channel, end_bit); repairs [n_channels]; counters [n_channels][3]"""
-    recs, failed, counters = [], [], []
-    for c, bits in enumerate(bit_streams):
+    ds = []
+    for bits in bit_streams:
         d = Deframer()
         d.feed(bits)
+        ds.append(d)
+    return records_of(ds)
+
+
+def records_of(ds):
+    """decode_streams() of channels whose Deframers have been fed already (in parts, a protodec_reset() between them)"""
+    recs, failed, counters = [], [], []
+    for c, d in enumerate(ds):
         for f in d.closed:
             if f["good"]:
                 recs.append((c, f["end_bit"], record(c, f["end_bit"], f["n"], f["payload"])))
             else:
                 failed.append((c, f))
         counters.append((d.received, d.lost, d.lost2))
-    repaired = np.zeros(len(bit_streams), dtype=np.int32)
+    repaired = np.zeros(len(ds), dtype=np.int32)
     by_len = {}
     for c, f in failed:                                 # candidates of one length side by side (brute_force_many)
         by_len.setdefault(f["raw"].size, []).append((c, f))
