@@ -265,6 +265,13 @@ struct gnuais_batch {
     int long_cand_cap = 0;
     int long_parity = 0;
     Buf<uint32_t> long_clean, long_cand, long_cand_count;
+    // The signal record of every long frame and its share in the channel load (gnuais_batch_long_frame_signal,
+    // long_signal.hip; off by default, only with long_frames and frame_signal): while it is on, one more launch behind D'
+    // and the long repair writes long_signal[slot] for the call's records, and -- where gnuais_batch_occupancy was switched
+    // on with it (occ_long: LAG and the rings are those of the 1008-bit span) -- their cover bytes, in front of the call's
+    // epoch finalisers.  fs_long: the signal ring is sized for the long span (it stays so until frame_signal is switched).
+    bool long_frame_signal = false, fs_long = false, occ_long = false;
+    Buf<gnuais_frame_signal> long_signal;       // [long_cap], parallel to long_ring
     // One record per transmission (gnuais_batch_unique, frame_unique.hip; 0 = off): the window in rows, the open
     // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
     // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the
@@ -388,8 +395,11 @@ double now_ms();
 int chan_zero_state(gnuais_batch *b);
 int afc_zero_state(gnuais_batch *b);
 // capi_ingest.hip: gnuais_batch_occupancy's part of a reset (the device is idle), and of the tail of an I/Q-type call of
-// len rows from row b->rows on, behind its frame_signal launch on stream s: the cover launch and the finalisers of the
-// epochs that call makes final
+// len rows from row b->rows on, behind its frame_signal launch on stream s: the cover launch (occ_cover), and the
+// finalisers of the epochs that call makes final (occ_finalise) -- directly behind it, or behind the long frames' cover
+// where they have one (gnuais_batch_long_frame_signal; long_signal_launch fills that launch, cover bytes included)
 int occ_zero_state(gnuais_batch *b);
-int occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s);
+int occ_cover(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s);
+int occ_finalise(gnuais_batch *b, int len, hipStream_t s);
+LongSignalLaunch long_signal_launch(const gnuais_batch *b, int len);
 }

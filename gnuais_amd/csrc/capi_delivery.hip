@@ -450,6 +450,7 @@ static int drain_long_unique_impl(gnuais_batch *b, gnuais_long_frame *h_out, int
             static_assert(sizeof(gnuais_hearer) == 24, "a member is three 64-bit words");
             const size_t need_h = long_unique_heard_scratch_bytes((int) have);
             HIP_TRY(b->lq_heard.grow(need_h, need_h / 4));
+            a.signal = b->long_frame_signal ? b->long_signal.p : nullptr;
             a.heard_scratch = b->lq_heard;
             a.heard_scratch_bytes = b->lq_heard.bytes;
             a.out_first = reinterpret_cast<int32_t *>(b->lq_out.p + at_first);
@@ -498,7 +499,8 @@ int gnuais_batch_drain_long_frames_unique(gnuais_batch *b, gnuais_long_frame *h_
     return drain_long_unique_impl(b, h_out, h_copies, max, n_out, nullptr, nullptr, nullptr);
 }
 
-// the same drain with, for every cluster, the list of its members: who heard the long transmission, and when
+// the same drain with, for every cluster, the list of its members: who heard the long transmission, when, and -- while
+// gnuais_batch_long_frame_signal is on -- how strongly
 int gnuais_batch_drain_long_frames_heard(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
                                          int32_t *h_first, gnuais_hearer *h_members, int *n_members)
 {

@@ -87,7 +87,11 @@ int gnuais::occ_zero_state(gnuais_batch *b)
 // the first whole block of the run the epochs are counted in
 static long long occ_b0(const gnuais_batch *b) { return (long long) ((b->occ_v0 + FS_BLOCK - 1) / FS_BLOCK); }
 
-int gnuais::occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s)
+// the longest frame that covers: the rings and LAG are those of the feature's state when occupancy was switched on
+static int occ_max_nbits(const gnuais_batch *b) { return b->occ_long ? FS_LONG_MAX_NBITS : FS_MAX_NBITS; }
+static_assert(FS_LONG_MAX_NBITS == GNUAIS_LONG_MAX_BITS, "the long span of the signal ring and of LAG");
+
+int gnuais::occ_cover(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t s)
 {
     const size_t N = (size_t) b->N;
     const long long n0 = (long long) b->rows, b0 = occ_b0(b);
@@ -104,8 +108,15 @@ int gnuais::occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t 
     c.pllinc = b->pllinc; c.n_taps = b->NT; c.afc_window = b->afc_W;
     c.v0 = (int64_t) b->occ_v0; c.b0 = b0;
     HIP_TRY(launch_occ_cover(c, s));
+    return GNUAIS_OK;
+}
+
+int gnuais::occ_finalise(gnuais_batch *b, int len, hipStream_t s)
+{
+    const size_t N = (size_t) b->N;
+    const long long n0 = (long long) b->rows, b0 = occ_b0(b);
     // The epochs this call makes final: the host knows them from n0, len and v0 alone
-    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W), E = b->occ_E;
+    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W, occ_max_nbits(b)), E = b->occ_E;
     while (n0 + len > FS_BLOCK * (b0 + (b->occ_next + 1) * E) - 1 + lag) {
         const int slot = (int) (b->occ_seq % OCC_RING_EPOCHS);
         OccEpochLaunch e;
@@ -124,6 +135,25 @@ int gnuais::occ_tail(gnuais_batch *b, const HdlcLaunch &h, int len, hipStream_t 
         b->occ_next++;
     }
     return GNUAIS_OK;
+}
+
+// the launch behind D' and the long repair of a call of len rows from row b->rows on (len <= 0: bits without samples).
+// As for the chain's frames (fill_frame_signal), the records of a call that did not come through run_form get (0, 0, 0)
+// -- v0 behind its last row -- and only a call that did has cover bytes to store.
+LongSignalLaunch gnuais::long_signal_launch(const gnuais_batch *b, int len)
+{
+    LongSignalLaunch a;
+    a.frames = b->long_ring.p; a.frame_count = b->long_count; a.frame_cap = (uint32_t) b->long_cap;
+    a.ring = b->fs_ring; a.signal = b->long_signal.p;
+    a.RB = b->fs_RB; a.N = b->N;
+    a.len = len; a.n0 = (int64_t) b->rows;
+    a.pllinc = b->pllinc; a.n_taps = b->NT; a.afc_window = b->afc_W;
+    a.v0 = (int64_t) (b->fs_iq_call ? b->fs_v0 : b->rows + (unsigned long long) std::max(len, 0));
+    if (b->occ_E && b->occ_long && b->fs_iq_call && len > 0) {
+        a.cover = b->occ_cover; a.CB = b->occ_CB;
+        a.occ_v0 = (int64_t) b->occ_v0; a.b0 = occ_b0(b);
+    }
+    return a;
 }
 
 extern "C" {
@@ -554,6 +584,8 @@ static int power_launch(gnuais_batch *b, const int16_t *d_iq, int len, hipStream
     return GNUAIS_OK;
 }
 
+static int fs_ring_alloc(gnuais_batch *b, bool long_span, const char *who);
+
 // Synchronises: no call is in flight when the switch turns.  The records of what the ring holds start at (0, 0, 0), the
 // run of I/Q-type calls at the current row.
 int gnuais_batch_frame_signal(gnuais_batch *b, int on)
@@ -567,36 +599,88 @@ int gnuais_batch_frame_signal(gnuais_batch *b, int on)
     if (!on && b->occ_E)
         return fail(GNUAIS_E_STATE, "frame_signal: the batch codes the block sums of this ring (gnuais_batch_occupancy); "
                                     "gnuais_batch_occupancy(b, 0, 0) first");
+    if (!on && b->long_frame_signal)
+        return fail(GNUAIS_E_STATE, "frame_signal: the batch measures its long frames from this ring "
+                                    "(gnuais_batch_long_frame_signal); gnuais_batch_long_frame_signal(b, 0) first");
     if (int rc = gnuais_batch_sync(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->frame_signal = false;
     HIP_TRY(b->fs_ring.release());
+    b->fs_long = false;
     if (!on) return GNUAIS_OK;
+    if (int rc = fs_ring_alloc(b, b->long_frame_signal, "frame_signal")) return rc;
+    const size_t N = (size_t) b->N;
+    HIP_TRY(b->fs_carry.ensure(sizeof(uint32_t) * N));
+    HIP_TRY(b->signal.ensure(sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
+    HIP_TRY(hipMemset(b->signal, 0, sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
+    b->frame_signal = true;
+    return GNUAIS_OK;
+}
+
+// The ring of block sums anew (the device is idle), sized for frames of 448 bits, or of GNUAIS_LONG_MAX_BITS with
+// long_span; the run of I/Q-type calls starts at the current row.  A failure leaves the batch without a ring.
+static int fs_ring_alloc(gnuais_batch *b, bool long_span, const char *who)
+{
+    HIP_TRY(b->fs_ring.release());
     // The ring's size.  No slot may be written while a frame launch that can still read it is pending.  The ingest
     // launch of call i is queued before the host waits for the tail of call i - nbuf (gnuais_batch_run: e_done[4][k]),
     // so while the frame launch of call c is pending, ingest launches up to call c + nbuf may run: they write rows
     // below n0_c + (nbuf + 1) * max_len.  That frame launch reads from row q - S on, q = t - d_f - W/2 with t >= n0_c:
-    // at most S_max + d_f + W_max/2 rows below n0_c, S_max the span of the longest frame (448 bits).  nbuf + 2 calls
+    // at most S_max + d_f + W_max/2 rows below n0_c, S_max the span of the longest frame (448 bits; 1008 with long_span:
+    // the launch of long_signal.hip is queued where the frame launch is, in the same tail, and reads a longer span from
+    // the same q on, so the argument holds with the longer S_max).  nbuf + 2 calls
     // instead of nbuf + 1 leave one call of slack; one block more at either end for the two open ones.
     // That wait belongs to the pipelined path.  With the pipeline off (set_option("pipeline", 0)) a call's tail runs on
     // the caller's stream behind its K1, so on one stream the next call's ingest launch is behind the pending frame
     // launch in stream order, and a call on another stream drains the chain's recorded stream first (run_form passes
     // the CHAIN bit to drain()): no ingest launch ever runs beside a pending frame launch there.
-    const long long S_max = fs_span_rows(FS_MAX_NBITS, b->pllinc);
+    const long long S_max = fs_span_rows(long_span ? FS_LONG_MAX_NBITS : FS_MAX_NBITS, b->pllinc);
     const long long rows = (long long) (b->nbuf + 2) * b->max_len + S_max + (b->NT + 1) / 2 + AFC_MAX_WINDOW / 2;
     const long long RB = fs_ceil_div(rows, FS_BLOCK) + 2;
-    if (S_max / FS_BLOCK + 1 > 0xffff || RB > 0x7fffffff)
-        return fail(GNUAIS_E_STATE, "frame_signal: the batch's pllinc gives frames of more than 65535 blocks");
+    if (S_max / FS_BLOCK + 1 > 0xffff || RB > 0x7fffffff) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: the batch's pllinc gives frames of more than 65535 blocks", who);
+        return fail(GNUAIS_E_STATE, msg);
+    }
     const size_t N = (size_t) b->N;
-    if (int rc = alloc_checked(b, b->fs_ring, sizeof(int64_t) * 3 * N * (size_t) RB, "frame_signal", "the ring of block sums"))
+    if (int rc = alloc_checked(b, b->fs_ring, sizeof(int64_t) * 3 * N * (size_t) RB, who, "the ring of block sums"))
         return rc;
-    HIP_TRY(b->fs_carry.ensure(sizeof(uint32_t) * N));
-    HIP_TRY(b->signal.ensure(sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
-    HIP_TRY(hipMemset(b->signal, 0, sizeof(gnuais_frame_signal) * (size_t) b->frame_cap));
     b->fs_RB = (int) RB;
     b->fs_nbuf = b->nbuf;
     b->fs_v0 = b->fs_end = b->rows;
-    b->frame_signal = true;
+    b->fs_long = long_span;
+    return GNUAIS_OK;
+}
+
+// ---- the signal record of every long frame (include/gnuais_hip.h, long_signal.hip) ----
+
+// Synchronises: no call is in flight when the switch turns, so every D' launch either has the long signal launch behind
+// it or has not.  Switching on re-sizes the ring of block sums for the 1008-bit span and starts a new run of I/Q-type
+// calls at the current row, as switching gnuais_batch_frame_signal on does; the records of the short frames already
+// queued stay as they are, those of the long frames already queued are (0, 0, 0).  Switching off keeps the ring.
+int gnuais_batch_long_frame_signal(gnuais_batch *b, int on)
+{
+    if (!b) return fail(GNUAIS_E_ARG, "long_frame_signal: NULL batch");
+    if (!b->long_frames)
+        return fail(GNUAIS_E_STATE, "long_frame_signal: the batch does not decode long frames (gnuais_batch_long_frames): "
+                                    "the records measured are that decoder's");
+    if (!b->frame_signal)
+        return fail(GNUAIS_E_STATE, "long_frame_signal: the batch keeps no block sums (gnuais_batch_frame_signal): a long "
+                                    "frame's record is the sum of its blocks");
+    if (b->occ_E)
+        return fail(GNUAIS_E_STATE, "long_frame_signal: the rings of gnuais_batch_occupancy are sized for the frames that "
+                                    "covered when it was switched on; gnuais_batch_occupancy(b, 0, 0) first");
+    if (int rc = gnuais_batch_sync(b)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    b->long_frame_signal = false;
+    if (!on) return GNUAIS_OK;
+    if (int rc = fs_ring_alloc(b, true, "long_frame_signal")) {
+        b->frame_signal = false;                // the ring is gone: gnuais_batch_frame_signal(b, 1) makes a new one
+        return rc;
+    }
+    HIP_TRY(b->long_signal.ensure(sizeof(gnuais_frame_signal) * (size_t) b->long_cap));
+    HIP_TRY(hipMemset(b->long_signal, 0, sizeof(gnuais_frame_signal) * (size_t) b->long_cap));
+    b->long_frame_signal = true;
     return GNUAIS_OK;
 }
 
@@ -638,6 +722,7 @@ int gnuais_batch_occupancy(gnuais_batch *b, int epoch_blocks, int margin)
     if (int rc = gnuais_batch_sync(b)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     b->occ_E = 0;
+    b->occ_long = false;
     HIP_TRY(b->occ_codes.release());
     HIP_TRY(b->occ_cover.release());
     if (!epoch_blocks) return GNUAIS_OK;
@@ -650,8 +735,11 @@ int gnuais_batch_occupancy(gnuais_batch *b, int epoch_blocks, int margin)
     // f + E + ceil(LAG / 64) + (nbuf + 1) * ceil(max_len / 64) + 1, and the finaliser reads and writes from block f on.
     // nbuf + 2 calls instead of nbuf + 1 leave one call of slack, one block more for the open one.  LAG is that of the
     // AFC window in use; gnuais_batch_afc refuses a wider one while the feature is on.  With the pipeline off every
-    // launch is in one stream's order, as there.
-    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W);
+    // launch is in one stream's order, as there.  Where the long frames cover too (gnuais_batch_long_frame_signal is on
+    // at this switch), LAG is that of the 1008-bit span and their cover launch sits where the chain's does, in the same
+    // tail in front of the same finalisers, and stores up to the same row: the argument holds with the longer LAG.
+    b->occ_long = b->long_frame_signal;
+    const long long lag = occ_lag_rows(b->pllinc, b->NT, b->afc_W, occ_max_nbits(b));
     const long long CB = epoch_blocks + fs_ceil_div(lag, FS_BLOCK) + (long long) (b->nbuf + 2) * fs_ceil_div(b->max_len, FS_BLOCK) + 2;
     if (CB > 0x7fffffff) return fail(GNUAIS_E_STATE, "occupancy: the batch's pllinc gives frames of more than 2^31 blocks");
     const size_t N = (size_t) b->N;

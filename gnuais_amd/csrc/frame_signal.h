@@ -15,6 +15,7 @@ namespace gnuais {
 
 constexpr int FS_BLOCK = 64;            // rows of a block of n
 constexpr int FS_MAX_NBITS = 448;       // the longest frame the deframer delivers (449 stored bits give up)
+constexpr int FS_LONG_MAX_NBITS = 1008; // the longest frame of gnuais_batch_long_frames (GNUAIS_LONG_MAX_BITS)
 
 // floor(a / b) and ceil(a / b) for b > 0 and any a
 FS_HD inline long long fs_floor_div(long long a, long long b) { return a / b - (a % b < 0 ? 1 : 0); }

@@ -229,7 +229,7 @@ int gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const int
                                 out_members, n_members);
 }
 
-// the long frames' merge: the time is the record's own t, the members carry no signal record
+// the long frames' merge: the time is the record's own t; the members carry the records of _push_heard_signal, else zeros
 int gnuais_long_uniq_create(gnuais_long_uniq **out, long long window) { return create(out, window); }
 void gnuais_long_uniq_destroy(gnuais_long_uniq *u) { delete u; }
 int gnuais_long_uniq_reset(gnuais_long_uniq *u) { return reset(u); }
@@ -250,6 +250,17 @@ int gnuais_long_uniq_push_heard(gnuais_long_uniq *u, const gnuais_long_frame *fr
     *n_members = 0;
     out_first[0] = 0;
     return push_impl<LongHost>(u, frames, nullptr, nullptr, n, rows, out, nullptr, out_copies, cap, n_out, out_first,
+                               out_members, n_members);
+}
+
+int gnuais_long_uniq_push_heard_signal(gnuais_long_uniq *u, const gnuais_long_frame *frames, const gnuais_frame_signal *signal,
+                                       int n, long long rows, gnuais_long_frame *out, int32_t *out_copies, int cap, int *n_out,
+                                       int32_t *out_first, gnuais_hearer *out_members, int *n_members)
+{
+    if (!out_first || !n_members || (n > 0 && !out_members)) return GNUAIS_E_ARG;
+    *n_members = 0;
+    out_first[0] = 0;
+    return push_impl<LongHost>(u, frames, nullptr, signal, n, rows, out, nullptr, out_copies, cap, n_out, out_first,
                                out_members, n_members);
 }
 

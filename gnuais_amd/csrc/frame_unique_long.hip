@@ -5,7 +5,7 @@
 // gnuais_long_frame is 152 bytes and 8-byte aligned only, so every record access here is in 64-bit words, 19 per record:
 // word 0 channel | end_bit << 32, word 1 t, word 2 nbits | flags << 16 | reserved << 24 | payload[0..3] << 32, words 3..18
 // the rest of the payload.  The key is words 2..18 with word 2 masked (LongRec::KEY_FIRST_MASK64): 17 words, the 17 pairs
-// of the definition.  The member time is the record's own word 1; there is no times array and no signal record.
+// of the definition.  The member time is the record's own word 1; there is no times array.
 // Entries are [tail | long ring]; a tail entry is a record with t_last in word 1 and word 2 masked to the key.
 // Nothing runs per call: the whole stage is the drain.  No LDS, no scratch memory.
 //
@@ -258,11 +258,12 @@ __global__ __launch_bounds__(LQ_BLOCK) void luniq_slot2q_kernel(
 }
 
 // lane = sorted position j: member j - start of its cluster, into the cluster's list.  A cluster behind a tail entry is
-// late and listed nowhere.  24 bytes per member: channel | flags << 32, t, and a signal record of zeros.
+// late and listed nowhere.  24 bytes per member: channel | flags << 32, t, and the copy's signal record by ring slot
+// (long_signal.hip; zeros without the array).
 __global__ __launch_bounds__(LQ_BLOCK) void luniq_heard_kernel(
     int n_tail, const u64 *__restrict__ frames, int m, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ cid,
     const uint32_t *__restrict__ start, const u64 *__restrict__ prim, const uint32_t *__restrict__ slot2q,
-    const uint32_t *__restrict__ first, u64 *__restrict__ members)
+    const uint32_t *__restrict__ first, const u64 *__restrict__ signal, u64 *__restrict__ members)
 {
     const int j = blockIdx.x * LQ_BLOCK + threadIdx.x;
     if (j >= m) return;
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(LQ_BLOCK) void luniq_heard_kernel(
     u64 *out = members + 3 * pos;
     out[0] = (rec[0] & 0xffffffffull) | ((u64) LR::flags64(rec[LR::KEY_WORD64]) << 32);
     out[1] = (u64) t;
-    out[2] = 0ull;
+    out[2] = signal ? signal[e] : 0ull;
 }
 
 inline dim3 lgrid_for(size_t n) { return dim3((unsigned) ((n + LQ_BLOCK - 1) / LQ_BLOCK)); }
@@ -365,7 +366,7 @@ hipError_t long_unique_deliver_enqueue(const LongUniqueLaunch &a, int n_primarie
     // the sorted index array is idxA in both attempts: one sort into idxB, then one (hashed) or 17 (exact) more
     hipLaunchKernelGGL(luniq_heard_kernel, lgrid_for((size_t) m), dim3(LQ_BLOCK), 0, s, a.n_tail,
                        static_cast<const u64 *>(a.frames), m, l.idxA, l.cid, l.start, l.prim, slot2q, first,
-                       reinterpret_cast<u64 *>(a.out_members));
+                       static_cast<const u64 *>(a.signal), reinterpret_cast<u64 *>(a.out_members));
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <chrono>
 
 #include "batch.h"
+#include "occupancy.h"
 
 namespace gnuais {
 namespace scalar { hipError_t launch_fir_slice(const FirLaunch &a, hipStream_t stream); }
@@ -740,13 +741,27 @@ static int run_tail(gnuais_batch *b, int k, int len, bool tm, const Event *ev,
     if (b->frame_signal && (b->stage_mask & 16)) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, len), sD));
     // the channels' load: the cover of this call's frames behind their times, then the epochs the call makes final, in
     // front of e_done[4][k] (occupancy.hip; only a call that came through run_form has I/Q rows)
-    if (b->occ_E && b->fs_iq_call && (b->stage_mask & 16))
-        if (int rc = occ_tail(b, h, len, sD)) return rc;
+    // Where the long frames cover too (gnuais_batch_long_frame_signal), the finalisers wait for their cover launch: chain
+    // cover, D', long repair, long signal and cover, then the finalisers.  Else the sequence is the one it always was.
+    const bool occ = b->occ_E && b->fs_iq_call && (b->stage_mask & 16);
+    const bool long_sig = b->long_frames && b->long_frame_signal && (b->stage_mask & 8);
+    if (occ) {
+        if (int rc = occ_cover(b, h, len, sD)) return rc;
+        if (!long_sig)
+            if (int rc = occ_finalise(b, len, sD)) return rc;
+    }
     // messages of three to five slots: D' over this call's packs, behind the deframer that moved the bit count it reads
     // and in front of e_done[4][k], which is what the reuse of set k (segbits, segcnt) and, where K3 has a stream of its
     // own, the next deframer launch (ctl) wait for (hdlc_long.hip)
     if (b->long_frames && (b->stage_mask & 8))
         if (int rc = run_long(b, h, len, sD)) return rc;
+    // their power and carrier error, and their cover: behind D' and the long repair, which append the records, and in
+    // front of e_done[4][k] (long_signal.hip)
+    if (long_sig) {
+        HIP_TRY(launch_long_signal(long_signal_launch(b, len), sD));
+        if (occ)
+            if (int rc = occ_finalise(b, len, sD)) return rc;
+    }
     if (b->streaming) b->ring_runs[b->ring_cur]++;
     b->hdlc_calls++;
     if (tm) HIP_TRY(hipEventRecord(ev[4], sD));
@@ -988,6 +1003,8 @@ int gnuais_batch_decode_bits(gnuais_batch *b, const uint8_t *h_bits, int stride,
         if (b->frame_signal) HIP_TRY(launch_frame_signal(fill_frame_signal(b, h, 0), nullptr));   // and (0, 0, 0)
         if (b->long_frames)                                                                        // D' on the same packs: t = -1
             if (int rc = run_long(b, h, 0, nullptr)) return rc;
+        if (b->long_frames && b->long_frame_signal)                                                // their records: (0, 0, 0)
+            HIP_TRY(launch_long_signal(long_signal_launch(b, 0), nullptr));
         if (b->streaming) b->ring_runs[b->ring_cur]++;
         b->hdlc_calls++;
         HIP_TRY(hipDeviceSynchronize());
@@ -1204,6 +1221,10 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
     else if (!strcmp(name, "long_frames")) *value = b->long_frames;
     else if (!strcmp(name, "long_frame_cap")) *value = b->long_cap ? b->long_cap : long_ring_capacity(b);
     else if (!strcmp(name, "long_repair")) *value = b->long_repair;
+    else if (!strcmp(name, "long_frame_signal")) *value = b->long_frame_signal;
+    else if (!strcmp(name, "occupancy_lag"))    // LAG in rows: of the rings in use, else of the next gnuais_batch_occupancy switch
+        *value = (double) occ_lag_rows(b->pllinc, b->NT, b->afc_W,
+                                       (b->occ_E ? b->occ_long : b->long_frame_signal) ? FS_LONG_MAX_NBITS : FS_MAX_NBITS);
     else if (!strcmp(name, "long_cand_cap")) *value = b->long_cand_cap ? b->long_cand_cap : long_ring_capacity(b);
     else if (!strcmp(name, "unique")) *value = b->uq_window;
     else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
@@ -1266,6 +1287,7 @@ int gnuais_batch_long_frames(gnuais_batch *b, int on)
     HIP_TRY(hipStreamSynchronize(nullptr));
     b->long_frames = on != 0;
     if (!on) b->long_repair = false;            // gnuais_batch_long_repair: nothing to repair without D'
+    if (!on) b->long_frame_signal = false;      // gnuais_batch_long_frame_signal: nothing to measure either
     if (!on) b->lq_window = 0;                  // gnuais_batch_long_unique: nothing to merge either
     b->lq_n_tail = 0;                           // any switch: the ring starts over, and so do the merge's tail and late count
     b->lq_late = 0;
@@ -1326,27 +1348,55 @@ int gnuais_batch_pending_long_frames(gnuais_batch *b, int *n_out)
 
 // Everything queued, consumed once, in (channel, 37-bit stamp) order.  Long frames are rare -- the ring holds a handful
 // per drain -- so the records cross PCIe as the kernel appended them and are put in order here.
-int gnuais_batch_drain_long_frames(gnuais_batch *b, gnuais_long_frame *h_out, int max, int *n_out)
+// h_signal: entry for entry, the records of gnuais_batch_long_frame_signal as well, through the sort's own permutation
+static int drain_long_impl(gnuais_batch *b, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max, int *n_out,
+                           const char *who)
 {
-    if (!b || !n_out || max < 0 || (max && !h_out)) return fail(GNUAIS_E_ARG, "drain_long_frames: argument");
+    const std::string name(who);
     *n_out = 0;
     uint32_t have = 0;
     bool overflow = false;
-    if (int rc = long_pending(b, "drain_long_frames", have, overflow)) return rc;
-    if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_long_frames: frame buffer too small");
+    if (int rc = long_pending(b, who, have, overflow)) return rc;
+    if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, (name + ": frame buffer too small").c_str());
     if (have) {
         std::vector<gnuais_long_frame> v(have);
+        std::vector<gnuais_frame_signal> sig(h_signal ? have : 0);
         HIP_TRY(hipMemcpy(v.data(), b->long_ring, sizeof(gnuais_long_frame) * have, hipMemcpyDeviceToHost));
+        if (h_signal) HIP_TRY(hipMemcpy(sig.data(), b->long_signal, sizeof(gnuais_frame_signal) * have, hipMemcpyDeviceToHost));
         const auto stamp = [](const gnuais_long_frame &f) { return (uint64_t) f.end_bit | ((uint64_t) ((f.flags >> 1) & 31) << 32); };
-        std::stable_sort(v.begin(), v.end(), [&](const gnuais_long_frame &x, const gnuais_long_frame &y) {
+        std::vector<uint32_t> order(have);
+        for (uint32_t i = 0; i < have; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t i, uint32_t j) {
+            const gnuais_long_frame &x = v[i], &y = v[j];
             return x.channel != y.channel ? x.channel < y.channel : stamp(x) < stamp(y);
         });
-        memcpy(h_out, v.data(), sizeof(gnuais_long_frame) * have);
+        for (uint32_t i = 0; i < have; ++i) {
+            h_out[i] = v[order[i]];
+            if (h_signal) h_signal[i] = sig[order[i]];
+        }
     }
     *n_out = (int) have;
     HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
-    if (overflow) return fail(GNUAIS_E_OVERFLOW, "drain_long_frames: long-frame ring overflowed, frames were dropped");
+    if (overflow) return fail(GNUAIS_E_OVERFLOW, (name + ": long-frame ring overflowed, frames were dropped").c_str());
     return GNUAIS_OK;
+}
+
+int gnuais_batch_drain_long_frames(gnuais_batch *b, gnuais_long_frame *h_out, int max, int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max && !h_out)) return fail(GNUAIS_E_ARG, "drain_long_frames: argument");
+    return drain_long_impl(b, h_out, nullptr, max, n_out, "drain_long_frames");
+}
+
+// the same with, entry for entry, their power and carrier error (gnuais_batch_long_frame_signal)
+int gnuais_batch_drain_long_frames_signal(gnuais_batch *b, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max,
+                                          int *n_out)
+{
+    if (!b || !n_out || max < 0 || (max && (!h_out || !h_signal))) return fail(GNUAIS_E_ARG, "drain_long_frames_signal: argument");
+    *n_out = 0;
+    if (!b->long_frame_signal)
+        return fail(GNUAIS_E_STATE, "drain_long_frames_signal: the batch does not measure its long frames (gnuais_batch_long_frame_signal)");
+    static gnuais_frame_signal none_s;
+    return drain_long_impl(b, h_out, h_signal ? h_signal : &none_s, max, n_out, "drain_long_frames_signal");
 }
 
 int gnuais_batch_long_counters(gnuais_batch *b, int32_t *h_delivered, int32_t *h_failed)

@@ -387,6 +387,29 @@ struct LongRepairLaunch {
 };
 hipError_t launch_hdlc_long_repair(const LongRepairLaunch &a, hipStream_t stream);
 
+// ---- the signal record of every long frame (long_signal.hip; gnuais_batch_long_frame_signal in include/gnuais_hip.h) ----
+// One launch behind D''s (and the long repair's) of the same call, on its stream.  Writes signal[i] for every record i of
+// the long ring with t < 0 -- (0, 0, 0) -- or n0 <= t < n0 + len; other records are left alone.  With `cover` it also
+// stores 1 into the cover ring for the blocks j >= b0 of the cover span of every record with n0 <= t < n0 + len
+// (launch_occ_cover's rule, with the run's first row occ_v0).
+struct LongSignalLaunch {
+    const void *frames;            // gnuais_long_frame[frame_cap]: the long ring
+    const uint32_t *frame_count;   // its two words ([0] = records appended)
+    uint32_t frame_cap;
+    const int64_t *ring;           // [RB][N][3]: launch_iq_power's ring
+    void *signal;                  // gnuais_frame_signal[frame_cap], by ring slot
+    int RB, N;
+    int len;                       // rows of the call (<= 0: bits without samples)
+    int64_t n0;                    // rows the chain had taken before it
+    uint32_t pllinc;
+    int n_taps, afc_window;
+    int64_t v0;                    // first row of the current run of I/Q-type calls
+    uint8_t *cover = nullptr;      // [CB][N], or null: no cover bytes
+    int CB = 0;
+    int64_t occ_v0 = 0, b0 = 0;    // the run the epochs are counted in: its first row and its first whole block
+};
+hipError_t launch_long_signal(const LongSignalLaunch &a, hipStream_t stream);
+
 // ---- one record per transmission: the duplicate merge of a drain (frame_unique.hip; definition in include/gnuais_hip.h) ----
 // Entries = [tail | ring]: n_tail open clusters of earlier drains (16 words each: t_last, then the key as a record
 // holds it) and the `have` frames of the ring with their times.  unique_cluster_enqueue() queues everything up to the
@@ -432,8 +455,9 @@ hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStr
 
 // ---- the same merge over the long frames (frame_unique_long.hip; gnuais_batch_long_unique in include/gnuais_hip.h) ----
 // Entries = [tail | long ring]: a tail entry is a 38-word record with t_last in its t words and word 4 masked to the key;
-// the member time is the record's own t, there are no times and no signal records.  The two calls, the info words
-// (UNIQUE_INFO_*) and the repeat in the exact form are those of the stage above.  Every buffer is 8-byte aligned.
+// the member time is the record's own t, there are no times; the signal records are long_signal.hip's, where it is on.
+// The two calls, the info words (UNIQUE_INFO_*) and the repeat in the exact form are those of the stage above.  Every
+// buffer is 8-byte aligned.
 struct LongUniqueLaunch {
     const void *frames;            // gnuais_long_frame[have]: the long ring
     int have;
@@ -448,6 +472,7 @@ struct LongUniqueLaunch {
     struct gnuais_long_frame *out_frames;
     int32_t *out_copies;
     // the member lists (gnuais_batch_drain_long_frames_heard); out_first null: no lists wanted
+    const void *signal = nullptr;               // gnuais_frame_signal[have] by ring slot (long_signal.hip), or null: zeros
     void *heard_scratch = nullptr;
     size_t heard_scratch_bytes = 0;             // >= long_unique_heard_scratch_bytes(have)
     int32_t *out_first = nullptr;

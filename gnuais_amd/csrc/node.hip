@@ -192,6 +192,7 @@ struct gnuais_node {
     // gnuais_node_long_unique: the same for the long frames -- the shards' plain long drains, then one gnuais_long_uniq
     gnuais_long_uniq *lq = nullptr;
     std::vector<gnuais_long_frame> lq_frames;
+    std::vector<gnuais_frame_signal> lq_signal;     // gnuais_node_drain_long_frames_heard: the members' records
 };
 
 extern "C" {
@@ -619,9 +620,8 @@ int gnuais_node_long_repaired(gnuais_node *nd, int32_t *h_out)
 
 // every shard drains its own long ring; a shard's records come in (channel, stamp) order with LOCAL channel numbers and
 // the shards own ascending channel blocks, so the parts are renumbered and laid end to end
-int gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out)
+static int node_drain_long(gnuais_node *nd, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max, int *n_out)
 {
-    if (!nd || !n_out || max < 0 || (max && !h_out)) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames: argument");
     *n_out = 0;
     std::vector<Shard *> &sh = nd->shards;
     std::vector<int> pend(sh.size(), 0);
@@ -630,20 +630,45 @@ int gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int
     for (int v : pend) total += v;
     if (total > max) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames: frame buffer too small");
     std::vector<std::vector<gnuais_long_frame>> part(sh.size());
+    std::vector<std::vector<gnuais_frame_signal>> part_s(sh.size());
     std::vector<int> cnt(sh.size(), 0);
     const int rc = run_all(nd, [&](Shard &s, size_t i) {
         part[i].resize((size_t) std::max(pend[i], 1));
-        const int r = gnuais_batch_drain_long_frames(s.b, part[i].data(), pend[i], &cnt[i]);
+        if (h_signal) part_s[i].resize((size_t) std::max(pend[i], 1));
+        const int r = h_signal ? gnuais_batch_drain_long_frames_signal(s.b, part[i].data(), part_s[i].data(), pend[i], &cnt[i])
+                               : gnuais_batch_drain_long_frames(s.b, part[i].data(), pend[i], &cnt[i]);
         for (int k = 0; k < cnt[i]; ++k) part[i][(size_t) k].channel += (uint32_t) s.first;
         return r;
     });
     int w = 0;
     for (size_t i = 0; i < sh.size(); ++i) {
         if (cnt[i] > 0) memcpy(h_out + w, part[i].data(), sizeof(gnuais_long_frame) * (size_t) cnt[i]);
+        if (cnt[i] > 0 && h_signal) memcpy(h_signal + w, part_s[i].data(), sizeof(gnuais_frame_signal) * (size_t) cnt[i]);
         w += cnt[i];
     }
     *n_out = w;
     return rc;              // GNUAIS_E_OVERFLOW of a device is reported with what was drained
+}
+
+int gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max && !h_out)) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames: argument");
+    return node_drain_long(nd, h_out, nullptr, max, n_out);
+}
+
+// gnuais_batch_long_frame_signal on every shard, and the long drain with every record's power and carrier error
+int gnuais_node_long_frame_signal(gnuais_node *nd, int on)
+{
+    if (!nd) return node_fail(GNUAIS_E_ARG, "node_long_frame_signal: NULL node");
+    return run_all(nd, [=](Shard &s, size_t) { return gnuais_batch_long_frame_signal(s.b, on); });
+}
+
+int gnuais_node_drain_long_frames_signal(gnuais_node *nd, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max,
+                                         int *n_out)
+{
+    if (!nd || !n_out || max < 0 || (max && (!h_out || !h_signal)))
+        return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_signal: argument");
+    return node_drain_long(nd, h_out, h_signal, max, n_out);
 }
 
 static int node_drain(gnuais_node *nd, gnuais_frame *h_out, int64_t *h_times, int max, int *n_out,
@@ -825,12 +850,21 @@ static int node_drain_long_unique(gnuais_node *nd, gnuais_long_frame *h_out, int
     if (total > max) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_unique: buffers too small (one entry per pending long frame always suffices)");
     nd->lq_frames.resize((size_t) total + 1);
     int got = 0;
-    const int rc = gnuais_node_drain_long_frames(nd, nd->lq_frames.data(), (int) total, &got);
+    // the lists carry every copy's signal record: the shards' signal drain where they measure their long frames, else zeros
+    bool measured = h_first != nullptr;
+    for (Shard *s : nd->shards) {
+        double on = 0;
+        if (measured && (gnuais_batch_info(s->b, "long_frame_signal", &on) != GNUAIS_OK || on == 0)) measured = false;
+    }
+    if (measured) nd->lq_signal.resize((size_t) total + 1);
+    const int rc = node_drain_long(nd, nd->lq_frames.data(), measured ? nd->lq_signal.data() : nullptr, (int) total, &got);
     if (rc != GNUAIS_OK && rc != GNUAIS_E_OVERFLOW) return rc;
     double rows = 0;                    // a node's run calls give every shard the same rows
     if (gnuais_batch_info(nd->shards[0]->b, "rows", &rows) != GNUAIS_OK) return node_fail(GNUAIS_E_STATE, "node_drain_long_frames_unique: rows");
-    const int pushed = h_first ? gnuais_long_uniq_push_heard(nd->lq, nd->lq_frames.data(), got, (long long) rows, h_out, h_copies,
-                                                             max, n_out, h_first, h_members, n_members)
+    const int pushed = h_first ? gnuais_long_uniq_push_heard_signal(nd->lq, nd->lq_frames.data(),
+                                                                    measured ? nd->lq_signal.data() : nullptr, got,
+                                                                    (long long) rows, h_out, h_copies, max, n_out, h_first,
+                                                                    h_members, n_members)
                                : gnuais_long_uniq_push(nd->lq, nd->lq_frames.data(), got, (long long) rows, h_out, h_copies, max,
                                                        n_out);
     if (pushed != GNUAIS_OK) return node_fail(GNUAIS_E_ARG, "node_drain_long_frames_unique: the merge refused its input");

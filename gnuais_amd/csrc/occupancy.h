@@ -34,10 +34,11 @@ FS_HD inline long long occ_pre_rows(uint32_t pllinc) { return 64LL * 65536 / (lo
 FS_HD inline long long occ_post_rows(uint32_t pllinc) { return 8LL * 65536 / (long long) pllinc; }
 
 // LAG: an epoch whose last row is r is final once a call ends behind row r + LAG -- every frame whose cover span
-// [q - S - S_pre, q + S_post] can begin at or before r has its time by then (t = q + d_f + W/2 <= r + S + S_pre + d_f + W/2)
-FS_HD inline long long occ_lag_rows(uint32_t pllinc, int n_taps, int afc_window)
+// [q - S - S_pre, q + S_post] can begin at or before r has its time by then (t = q + d_f + W/2 <= r + S + S_pre + d_f + W/2).
+// max_nbits: the longest frame that covers -- FS_LONG_MAX_NBITS where the long frames cover too (gnuais_batch_long_frame_signal)
+FS_HD inline long long occ_lag_rows(uint32_t pllinc, int n_taps, int afc_window, int max_nbits = FS_MAX_NBITS)
 {
-    return fs_span_rows(FS_MAX_NBITS, pllinc) + occ_pre_rows(pllinc) + (n_taps + 1) / 2 + afc_window / 2 + FS_BLOCK;
+    return fs_span_rows(max_nbits, pllinc) + occ_pre_rows(pllinc) + (n_taps + 1) / 2 + afc_window / 2 + FS_BLOCK;
 }
 
 // The blocks the cover span of a frame with time t intersects: [*j_lo, *j_lo + *nb).  Returns false, with 0 and 0, where

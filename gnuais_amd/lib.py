@@ -140,7 +140,10 @@ SYMBOLS = {
     "gnuais_long_uniq_reset": (_I, [_P]),
     "gnuais_long_uniq_push": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_long_uniq_push_heard": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "gnuais_long_uniq_push_heard_signal": (_I, [_P, _P, _P, _I, C.c_longlong, _P, _P, _I, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
     "gnuais_long_uniq_late": (C.c_longlong, [_P]),
+    "gnuais_batch_long_frame_signal": (_I, [_P, _I]),
+    "gnuais_batch_drain_long_frames_signal": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_batch_discard_frames": (_I, [_P, _P]),
     "gnuais_batch_counters": (_I, [_P, _P]),
     "gnuais_batch_total_received": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -208,6 +211,8 @@ SYMBOLS = {
     "gnuais_node_repaired": (_I, [_P, _P]),
     "gnuais_node_long_frames": (_I, [_P, _I]),
     "gnuais_node_drain_long_frames": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "gnuais_node_long_frame_signal": (_I, [_P, _I]),
+    "gnuais_node_drain_long_frames_signal": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "gnuais_node_long_counters": (_I, [_P, _P, _P]),
     "gnuais_node_long_repair": (_I, [_P, _I]),
     "gnuais_node_long_repaired": (_I, [_P, _P]),

@@ -414,6 +414,30 @@ class ReceiverBatch:
         check(self._lib.gnuais_batch_long_repaired(self._h, out.ctypes.data))
         return out
 
+    def long_frame_signal(self, on: bool = True):
+        """gnuais_batch_long_frame_signal(): from now on every long frame of I/Q and wideband input gets its signal power
+        and carrier error, and covers its air time in occupancy() when that is switched on afterwards (the definition is
+        in include/gnuais_hip.h); one more launch per call.  Needs long_frames() and frame_signal(), and occupancy() off
+        at the switch.  Synchronises."""
+        check(self._lib.gnuais_batch_long_frame_signal(self._h, int(bool(on))))
+
+    def drain_long_frames_signal(self):
+        """gnuais_batch_drain_long_frames_signal(): (records, signal): drain_long_frames() with signal[i] (lib.SIGNAL_DTYPE:
+        power, ferr, blocks; blocks 0: no measurement) the record of records[i].  GnuaisError(E_OVERFLOW) carries what was
+        delivered in `.frames`."""
+        n = max(self.pending_long_frames(), 1)
+        out = np.zeros(n, dtype=LONG_FRAME_DTYPE)
+        sig = np.zeros(n, dtype=_lib.SIGNAL_DTYPE)
+        got = C.c_int()
+        rc = self._lib.gnuais_batch_drain_long_frames_signal(self._h, out.ctypes.data, sig.ctypes.data, n, C.byref(got))
+        res = (out[: got.value].copy(), sig[: got.value].copy())
+        if rc == E_OVERFLOW:
+            err = GnuaisError(rc, self._lib.gnuais_last_error().decode())
+            err.frames = res
+            raise err
+        check(rc)
+        return res
+
     def long_fsm_state(self) -> np.ndarray:
         """gnuais_batch_long_fsm_state(): the second decoder's live fields, as fsm_state()"""
         return self._struct_array(self._lib.gnuais_batch_long_fsm_state, FSM_DTYPE)
@@ -564,7 +588,8 @@ class ReceiverBatch:
     def drain_long_frames_heard(self):
         """gnuais_batch_drain_long_frames_heard(): (records, int32 copies, int32 first, members) -- what
         drain_long_frames_unique() delivers, and who heard each transmission: cluster i's members are
-        members[first[i]:first[i + 1]] (lib.HEARER_DTYPE: channel, flags, t; signal is all zero) in the order (t, channel)"""
+        members[first[i]:first[i + 1]] (lib.HEARER_DTYPE: channel, flags, t, and the copy's signal record while
+        long_frame_signal() is on, else zeros) in the order (t, channel)"""
         return self._drain_long_merged(True)
 
     def long_unique_late(self) -> int:
@@ -980,20 +1005,29 @@ class LongUniq:
             raise _lib.GnuaisError(rc, "gnuais_long_uniq_push: argument, or more records than cap")
         return out[: got.value].copy(), out_c[: got.value].copy()
 
-    def push_heard(self, frames: np.ndarray, rows: int, cap: Optional[int] = None):
-        """-> (records, copies, first, members): push() with the clusters' member lists (gnuais_long_uniq_push_heard)"""
+    def push_heard(self, frames: np.ndarray, rows: int, cap: Optional[int] = None, signal: Optional[np.ndarray] = None):
+        """-> (records, copies, first, members): push() with the clusters' member lists (gnuais_long_uniq_push_heard);
+        signal: the frames' records (lib.SIGNAL_DTYPE) for the members (gnuais_long_uniq_push_heard_signal), None: zeros"""
         frames = np.ascontiguousarray(frames, dtype=LONG_FRAME_DTYPE)
         assert frames.ndim == 1
         n = int(frames.size)
+        if signal is not None:
+            signal = np.ascontiguousarray(signal, dtype=_lib.SIGNAL_DTYPE)
+            assert signal.shape == (n,)
         cap = n if cap is None else int(cap)
         out = np.zeros(max(cap, 1), dtype=LONG_FRAME_DTYPE)
         out_c = np.zeros(max(cap, 1), dtype=np.int32)
         first = np.zeros(cap + 1, dtype=np.int32)
         members = np.zeros(max(n, 1), dtype=_lib.HEARER_DTYPE)
         got, nm = C.c_int(), C.c_int()
-        rc = self._lib.gnuais_long_uniq_push_heard(self._h, frames.ctypes.data, n, int(rows), out.ctypes.data,
-                                                   out_c.ctypes.data, cap, C.byref(got), first.ctypes.data,
-                                                   members.ctypes.data, C.byref(nm))
+        if signal is None:
+            rc = self._lib.gnuais_long_uniq_push_heard(self._h, frames.ctypes.data, n, int(rows), out.ctypes.data,
+                                                       out_c.ctypes.data, cap, C.byref(got), first.ctypes.data,
+                                                       members.ctypes.data, C.byref(nm))
+        else:
+            rc = self._lib.gnuais_long_uniq_push_heard_signal(self._h, frames.ctypes.data, signal.ctypes.data, n, int(rows),
+                                                              out.ctypes.data, out_c.ctypes.data, cap, C.byref(got),
+                                                              first.ctypes.data, members.ctypes.data, C.byref(nm))
         if rc != _lib.OK:
             raise _lib.GnuaisError(rc, "gnuais_long_uniq_push_heard: argument, or more records than cap")
         return out[: got.value].copy(), out_c[: got.value].copy(), first[: got.value + 1].copy(), members[: nm.value].copy()

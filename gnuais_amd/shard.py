@@ -245,6 +245,26 @@ class ReceiverNode:
             self._raise(rc)
             return out[: got.value].copy()
 
+    def long_frame_signal(self, on: bool = True):
+        """gnuais_batch_long_frame_signal() on every shard"""
+        self._raise(self._lib.gnuais_node_long_frame_signal(self._h, int(bool(on))))
+
+    def drain_long_frames_signal(self):
+        """gnuais_node_drain_long_frames_signal(): (records, signal): drain_long_frames() with every record's power,
+        carrier error and blocks (lib.SIGNAL_DTYPE)"""
+        from .lib import E_ARG, LONG_FRAME_DTYPE, SIGNAL_DTYPE
+        n = 1024
+        while True:
+            out = self._np.zeros(n, dtype=LONG_FRAME_DTYPE)
+            sig = self._np.zeros(n, dtype=SIGNAL_DTYPE)
+            got = self._C.c_int()
+            rc = self._lib.gnuais_node_drain_long_frames_signal(self._h, out.ctypes.data, sig.ctypes.data, n, self._C.byref(got))
+            if rc == E_ARG and n < 1 << 24:
+                n *= 4
+                continue
+            self._raise(rc)
+            return out[: got.value].copy(), sig[: got.value].copy()
+
     def long_counters(self):
         """gnuais_node_long_counters(): (delivered, failed), int32 [n_channels] each, per global channel"""
         d = self._np.zeros(self.n_channels, dtype=self._np.int32)

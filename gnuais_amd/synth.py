@@ -168,14 +168,14 @@ def make_iq_stream(n_samples: int, seed: int = SEED, channel: int = 0, sps: int 
 
 def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz, seed: int = SEED, stream: int = 0,
                          amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
-                         offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False):
+                         offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False, payloads=None):
     """One wide complex stream as an SDR records it: a channel of AIS at each of `offsets_hz` (Hz from the tuned
     frequency) at `in_rate_hz`, for a channeliser that decimates by `decim` to the chain's rate.
 
     Offset k carries noise-free make_iq_stream() bursts at sps = 5 * decim from a seed of its own, shifted by
     e^{+j 2 pi f_k n / R}; the offsets are summed, white Gaussian noise of `sigma` is added to I and Q, and the result is
     rounded and clamped to int16.  offset_hz: a carrier error of the whole stream (every channel lies that much off its
-    nominal offset); rate_hz: the narrowband rate (the wide one is rate_hz * decim); gated as in make_iq_stream.  Returns (int16[n_samples][2], [placed payloads of offset k, for each k]).
+    nominal offset); rate_hz: the narrowband rate (the wide one is rate_hz * decim); gated and payloads as in make_iq_stream.  Returns (int16[n_samples][2], [placed payloads of offset k, for each k]).
     """
     n = np.arange(n_samples, dtype=np.float64)
     acc = np.zeros(n_samples, dtype=np.complex128)
@@ -183,7 +183,7 @@ def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz
     for k, f in enumerate(offsets_hz):
         iq, pl = make_iq_stream(n_samples, seed=seed + 65537 * (k + 1), channel=stream, sps=5 * decim,
                                 amplitude=amplitude, sigma=0.0, occupancy=occupancy, offset_hz=offset_hz,
-                                rate_hz=float(rate_hz) * decim, gated=gated)
+                                rate_hz=float(rate_hz) * decim, gated=gated, payloads=payloads)
         z = iq[:, 0].astype(np.float64) + 1j * iq[:, 1].astype(np.float64)
         acc += z * np.exp(2j * np.pi * float(f) * n / float(in_rate_hz))
         placed.append(pl)
@@ -195,14 +195,14 @@ def make_wideband_stream(n_samples: int, decim: int, in_rate_hz: int, offsets_hz
 
 def make_resampled_wideband_stream(n_samples: int, up: int, down: int, offsets_hz, seed: int = SEED, stream: int = 0,
                                    amplitude: float = 10000.0, sigma: float = 1500.0, occupancy: float = 0.5,
-                                   offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False):
+                                   offset_hz: float = 0.0, rate_hz: float = 48000, gated: bool = False, payloads=None):
     """One wide complex stream at rate_hz * down / up, for a channeliser that resamples by up / down to the chain's rate
     (ReceiverBatch.resampler): make_wideband_stream() without its noise at rate_hz * down, every `up`-th sample of it
     kept, then white Gaussian noise of `sigma` on I and Q from the same generator, rounded and clamped to int16.
     Returns (int16[n_samples][2], [placed payloads of offset k, for each k])."""
     x, placed = make_wideband_stream(n_samples * up, down, int(rate_hz) * down, offsets_hz, seed=seed, stream=stream,
                                      amplitude=amplitude, sigma=0.0, occupancy=occupancy, offset_hz=offset_hz,
-                                     rate_hz=rate_hz, gated=gated)
+                                     rate_hz=rate_hz, gated=gated, payloads=payloads)
     out = x[::up].astype(np.float64)
     if sigma > 0:
         out += np.random.default_rng([seed, stream, 0x5744]).normal(0.0, sigma, out.shape)

@@ -690,8 +690,8 @@ int  gnuais_repair_candidate(const uint8_t *raw_bits, int n_raw, uint8_t payload
  *     so t is filled in whether gnuais_batch_frame_times is on or off.  t = -1 for a frame closed by
  *     gnuais_batch_decode_bits.
  *   Not in this section.  The duplicate merge and the member lists of the long frames have a section of their own
- *     (gnuais_batch_long_unique, below).  For long frames there is no signal record and no share in the channel load
- *     (gnuais_batch_frame_signal, gnuais_batch_occupancy), no stdout text line, no device formatter
+ *     (gnuais_batch_long_unique, below), and so have their signal records and their share in the channel load
+ *     (gnuais_batch_long_frame_signal, below).  For long frames there is no stdout text line, no device formatter
  *     (gnuais_batch_drain_nmea and its family), no entry in the vessel tables and no streamed delivery.  t and the stamp
  *     are in the record, so a host can do these itself.
  * gnuais_batch_long_frames(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE on a streaming batch, and
@@ -891,8 +891,8 @@ int  gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const in
  *   THE PROPERTY RELIED ON across drains: every t of a drain lies in [rows before the first call it covers, rows at the
  *     drain): D' computes t by the frame-time formula at its closing bit, a row of the call that closed the frame
  *     (tests/test_long_unique_cpu.py asserts it on the reference).
- *   Member: a gnuais_hearer -- channel, the copy's own flags, the copy's t.  signal = (0, 0, 0) always: long frames have
- *     no signal record.
+ *   Member: a gnuais_hearer -- channel, the copy's own flags, the copy's t, and the copy's signal record: that of
+ *     gnuais_batch_long_frame_signal (below) while it is on, (0, 0, 0) while it is off.
  *   State.  The long stage has a tail and a `late` counter of its own, independent of gnuais_batch_unique's.
  *     gnuais_batch_reset() clears both; gnuais_batch_protodec_reset() keeps both; any switch of gnuais_batch_long_frames
  *     clears them, and switching long frames off switches this feature off, as it does gnuais_batch_long_repair;
@@ -918,8 +918,9 @@ int  gnuais_uniq_push_heard(gnuais_uniq *u, const gnuais_frame *frames, const in
  * gnuais_batch_long_unique_late(): `late` since the feature was switched on / the last reset.
  * gnuais_long_uniq: the same merge as a host object, no device: _push() is one drain of the definition over frames[n] in
  *   any order with rows = n of the definition; at most cap records are written (GNUAIS_E_ARG, with the object unchanged,
- *   when the push would deliver more).  _push_heard(): with the lists; out_first has cap + 1 entries, out_members n.  The
- *   device drains equal them bit for bit. */
+ *   when the push would deliver more).  _push_heard(): with the lists; out_first has cap + 1 entries, out_members n.
+ *   _push_heard_signal(): _push_heard() with signal[n], the frames' records (gnuais_batch_long_frame_signal), in the
+ *   members; NULL gives zeros, and then it equals _push_heard() byte for byte.  The device drains equal them bit for bit. */
 int  gnuais_batch_long_unique(gnuais_batch *b, int window_rows);
 int  gnuais_batch_drain_long_frames_unique(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max,
                                            int *n_out);
@@ -936,7 +937,45 @@ int  gnuais_long_uniq_push(gnuais_long_uniq *u, const gnuais_long_frame *frames,
 int  gnuais_long_uniq_push_heard(gnuais_long_uniq *u, const gnuais_long_frame *frames, int n, long long rows,
                                  gnuais_long_frame *out, int32_t *out_copies, int cap, int *n_out, int32_t *out_first,
                                  gnuais_hearer *out_members, int *n_members);
+int  gnuais_long_uniq_push_heard_signal(gnuais_long_uniq *u, const gnuais_long_frame *frames,
+                                        const gnuais_frame_signal *signal /* NULL: zeros */, int n, long long rows,
+                                        gnuais_long_frame *out, int32_t *out_copies, int cap, int *n_out, int32_t *out_first,
+                                        gnuais_hearer *out_members, int *n_members);
 long long gnuais_long_uniq_late(const gnuais_long_uniq *u);
+
+/* ---- how strong a long frame was: signal power, carrier error and channel-load share for long frames ---------------------
+ * The records of gnuais_batch_long_frames get what gnuais_batch_frame_signal gives the chain's frames, from the same ring
+ * of block sums, and cover their air time in gnuais_batch_occupancy.  Off by default: while off, a call launches exactly
+ * what it launches without this section and every result above is what it is without it.  While on, every call launches
+ * one more kernel behind D' and, where gnuais_batch_long_repair is on, behind the repair launch.
+ *   Record.  A long record with time t and nbits gets a gnuais_frame_signal by exactly the formulas of the
+ *     gnuais_batch_frame_signal section: q, S = floor((nbits + 24) * 65536 / pllinc), j_lo, j_hi, nb, power, ferr, blocks,
+ *     with the same n, x[n], block sums and v0.  Repaired records count, with their own n' and the candidate's t.  nb is
+ *     up to 81 at 48 kHz.  gnuais_frame_signal_span() is the span arithmetic for any nbits up to 65535: it has no long twin.
+ *     The record is (0, 0, 0) when t < 0 (frames of gnuais_batch_decode_bits), nb <= 0 or 64 * j_lo < v0; for frames closed
+ *     by an audio-type run call; and for records appended while the feature was off.
+ *   Channel load.  When gnuais_batch_occupancy is switched on while this feature is on, cover_j also counts the long
+ *     records -- the same cover span [q - S - S_pre, q + S_post] with the record's own nbits, covering only if
+ *     q - S - S_pre >= v0 -- and LAG takes GNUAIS_LONG_MAX_BITS + 24 in place of 448 + 24:
+ *       LAG = floor((1008 + 24) * 65536 / pllinc) + S_pre + d_f + W/2 + 64;
+ *     the ring sizes follow that LAG (info "occupancy_lag": LAG in rows, of the rings in use, else of the next switch).
+ *     The call's epoch finalisers then run behind the long frames' cover: chain cover, D', long repair, long signal and
+ *     cover, finalisers.  With this feature off when occupancy is switched on, LAG, sizes and results are what they are
+ *     without this section.
+ * gnuais_batch_long_frame_signal(on): switches the feature; synchronises the batch.  GNUAIS_E_STATE unless
+ *   gnuais_batch_long_frames and gnuais_batch_frame_signal are on, and -- in either direction -- while
+ *   gnuais_batch_occupancy is on (its rings are sized by LAG).  While it is on gnuais_batch_frame_signal(b, 0) returns
+ *   GNUAIS_E_STATE; gnuais_batch_long_frames(b, 0) switches it off, as it does gnuais_batch_long_repair.  Switching on
+ *   re-sizes the ring of block sums for the span of GNUAIS_LONG_MAX_BITS bits in place of 448 and starts a new run (v0 =
+ *   the current row), exactly as switching gnuais_batch_frame_signal on does; the records of frames already queued stay
+ *   as they are (long ones: (0, 0, 0)).  Switching off keeps the larger ring until gnuais_batch_frame_signal is switched.
+ * gnuais_batch_drain_long_frames_signal(): gnuais_batch_drain_long_frames() with h_signal[i] = the record of h_out[i].
+ *   GNUAIS_E_STATE while the feature is off.  Every other drain keeps working while it is on;
+ *   gnuais_batch_drain_long_frames_heard() then carries each copy's record in its members.
+ * gnuais_batch_info "long_frame_signal" (0 / 1) and "occupancy_lag". */
+int  gnuais_batch_long_frame_signal(gnuais_batch *b, int on);
+int  gnuais_batch_drain_long_frames_signal(gnuais_batch *b, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max,
+                                           int *n_out);
 
 int  gnuais_batch_n_channels(const gnuais_batch *b);
 int  gnuais_batch_n_taps(const gnuais_batch *b);
@@ -1189,6 +1228,11 @@ int  gnuais_node_drain_occupancy(gnuais_node *nd, gnuais_occupancy *h_out /* [ma
  * in (channel, stamp) order */
 int  gnuais_node_long_frames(gnuais_node *nd, int on);
 int  gnuais_node_drain_long_frames(gnuais_node *nd, gnuais_long_frame *h_out, int max, int *n_out);
+/* gnuais_batch_long_frame_signal() on every shard, and the long drain with every record's power and carrier error;
+ * gnuais_node_drain_long_frames_heard() carries the records in its members while the feature is on */
+int  gnuais_node_long_frame_signal(gnuais_node *nd, int on);
+int  gnuais_node_drain_long_frames_signal(gnuais_node *nd, gnuais_long_frame *h_out, gnuais_frame_signal *h_signal, int max,
+                                          int *n_out);
 int  gnuais_node_long_counters(gnuais_node *nd, int32_t *h_delivered /* [n_channels] */, int32_t *h_failed /* [n_channels] */);
 /* gnuais_batch_long_repair() on every shard, and the long frames repaired per global channel */
 int  gnuais_node_long_repair(gnuais_node *nd, int on);

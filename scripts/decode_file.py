@@ -62,8 +62,12 @@
                                                       # --unique ROWS the copies of a long transmission are merged on the
                                                       # device as well (gnuais_batch_long_unique) and its sentences are
                                                       # printed once; with --heard a "  heard:" line follows them (receiver,
-                                                      # rows behind the printed copy, r = repaired; long frames carry no
-                                                      # signal record); the summary counts transmissions, copies and late copies
+                                                      # rows behind the printed copy, r = repaired, and for --iq / --wideband
+                                                      # input the copy's power and carrier error); the summary counts
+                                                      # transmissions, copies and late copies.  With --signal every long frame
+                                                      # gets its "  signal:" line on stderr like the others
+                                                      # (gnuais_batch_long_frame_signal), and with --occupancy the long frames
+                                                      # cover their air time
   ... --long-repair
                                                       # --long, and a long frame that fails its CRC by one wrong symbol is
                                                       # repaired on the device (gnuais_batch_long_repair); the summary counts
@@ -182,8 +186,6 @@ def main():
         b.repair(True)
     if a.measure or a.occupancy:
         b.frame_signal(True)
-    if a.occupancy:
-        b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
     if a.long:
@@ -192,6 +194,10 @@ def main():
         b.long_repair(True)
     if a.long and a.unique:
         b.long_unique(a.unique)
+    if a.long and a.measure:                                # before the occupancy switch: the long frames cover as well
+        b.long_frame_signal(True)
+    if a.occupancy:
+        b.occupancy(a.occupancy)
     for part in io.chunks(x, a.call):
         d = torch.from_numpy(np.ascontiguousarray(part)).cuda()
         if a.iq:
@@ -262,6 +268,15 @@ def write_long(a, b, seq, kind, rate):
         frames, copies, first, members = b.drain_long_frames_heard()
     elif a.unique:
         frames, copies = b.drain_long_frames_unique()
+    elif a.signal:                                          # as write_sentences: one line per frame on stderr
+        from gnuais_amd.lib import signal_dbfs, signal_hz
+        frames, sig = b.drain_long_frames_signal()
+        for f, s in zip(frames, sig):
+            if s["blocks"]:
+                sys.stderr.write(f"  signal: receiver {int(f['channel'])}, row {int(f['t'])}, {signal_dbfs(s['power']):.1f} dBFS, "
+                                 f"{signal_hz(s['ferr'], CHAIN_RATE):+.0f} Hz\n")
+            else:
+                sys.stderr.write(f"  signal: receiver {int(f['channel'])}, row {int(f['t'])}, not measured\n")
     else:
         frames = b.drain_long_frames()
     if a.unique:
@@ -283,9 +298,14 @@ def write_long(a, b, seq, kind, rate):
             tag = f"\\{body}*{chk:02X}\\"
             text = "".join(tag + line + "\r\n" for line in text.split("\r\n")[:-1])
         sys.stdout.write(text)
-        if members is not None:                             # as write_heard: receiver, rows behind the primary, r = repaired
-            who = [f"{int(m['channel'])} {int(m['t']) - t:+d}" + ("r" if int(m["flags"]) & 0x40 else "")
-                   for m in members[first[i]:first[i + 1]]]
+        if members is not None:                             # as write_heard: receiver, rows behind the primary, r = repaired,
+            from gnuais_amd.lib import signal_dbfs, signal_hz       # and the copy's level and carrier error where measured
+            who = []
+            for m in members[first[i]:first[i + 1]]:
+                txt = f"{int(m['channel'])} {int(m['t']) - t:+d}" + ("r" if int(m["flags"]) & 0x40 else "")
+                if m["signal"]["blocks"]:
+                    txt += f" {signal_dbfs(m['signal']['power']):.1f}dBFS {signal_hz(m['signal']['ferr'], CHAIN_RATE):+.0f}Hz"
+                who.append(txt)
             sys.stdout.write("  heard: " + ", ".join(who) + "\n")
 
 
@@ -388,8 +408,6 @@ def decode_wideband(a, rate, x, fmt=None):
         b.repair(True)
     if a.measure or a.occupancy:
         b.frame_signal(True)
-    if a.occupancy:
-        b.occupancy(a.occupancy)
     if a.unique:
         b.unique(a.unique)
     if a.long:
@@ -398,6 +416,10 @@ def decode_wideband(a, rate, x, fmt=None):
         b.long_repair(True)
     if a.long and a.unique:
         b.long_unique(a.unique)
+    if a.long and a.measure:                                # before the occupancy switch: the long frames cover as well
+        b.long_frame_signal(True)
+    if a.occupancy:
+        b.occupancy(a.occupancy)
     # --call counts chain rows; a wide call is whole periods of D samples = U rows each, at least one
     for part in io.chunks(x, max(a.call // U, 1) * D):
         b.run_wideband(torch.from_numpy(np.ascontiguousarray(part)).cuda(), fmt=fmt)
