@@ -272,25 +272,20 @@ struct gnuais_batch {
     // epoch finalisers.  fs_long: the signal ring is sized for the long span (it stays so until frame_signal is switched).
     bool long_frame_signal = false, fs_long = false, occ_long = false;
     Buf<gnuais_frame_signal> long_signal;       // [long_cap], parallel to long_ring
-    // One record per transmission (gnuais_batch_unique, frame_unique.hip; 0 = off): the window in rows, the open
-    // clusters carried from drain to drain ([n][16] words, double-buffered: a drain reads uq_tail[uq_cur] and writes the
-    // other), the late copies counted so far, the bits of the hash in use (set_option("unique_hash_bits")), and the
-    // stage's scratch, which grows on first use like nmea_scratch.  Nothing runs per call; only
-    // gnuais_batch_drain_frames_unique and _heard (the same drain with the clusters' member lists) touch any of it.
-    int uq_window = 0, uq_hash_bits = 64, uq_cur = 0, uq_n_tail = 0;
-    long long uq_late = 0;
-    Buf<uint32_t> uq_tail[2];
-    Buf<void> uq_scratch;
-    Buf<void> uq_heard;                         // gnuais_batch_drain_frames_heard's own scratch, on its first use
-    // The same over the long ring (gnuais_batch_long_unique, frame_unique_long.hip; 0 = off, only with long_frames): a
-    // window, a double-buffered tail ([n][38] words) and a late count of its own; the hash bits are uq_hash_bits.  The
-    // scratch, the member lists' scratch and the output buffer (records, copies, offsets, members) grow on demand.
-    // Nothing runs per call; only gnuais_batch_drain_long_frames_unique and _heard touch any of it.
-    int lq_window = 0, lq_cur = 0, lq_n_tail = 0;
-    long long lq_late = 0;
-    Buf<uint64_t> lq_tail[2];
-    Buf<void> lq_scratch, lq_heard;
-    Buf<char> lq_out;
+    // One record per transmission (frame_unique.hip), a state per kind of frame: uq for gnuais_batch_unique, lq for
+    // gnuais_batch_long_unique (only with long_frames).  Nothing runs per call; only the drains
+    // gnuais_batch_drain_frames_unique / _heard and gnuais_batch_drain_long_frames_unique / _heard touch any of it.
+    struct UniqueState {
+        int window = 0;                         // in rows; 0 = off
+        int cur = 0, n_tail = 0;                // the open clusters carried from drain to drain ([n][16] / [n][38] words),
+        Buf<uint64_t> tail[2];                  // double-buffered: a drain reads tail[cur] and writes the other
+        long long late = 0;                     // the late copies counted so far
+        Buf<void> scratch;                      // the stage's scratch, which grows on first use like nmea_scratch
+        Buf<void> heard;                        // the member lists' own scratch, on the first _heard drain
+    };
+    UniqueState uq, lq;
+    int uq_hash_bits = 64;                      // the bits of the hash in use, for both (set_option("unique_hash_bits"))
+    Buf<char> lq_out;                           // the long drain's output (records, copies, offsets, members), on demand
     // 0 whenever the batch is not streaming: only gnuais_batch_stream_nmea advances it, behind the point where it has
     // set `streaming`; set_option("streaming", 0), the one place that clears `streaming`, and reset set it to 0
     // (rings_reset)

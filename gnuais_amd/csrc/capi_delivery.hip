@@ -300,87 +300,107 @@ int gnuais_batch_drain_frames_signal(gnuais_batch *b, gnuais_frame *h_out, int64
                       h_signal ? h_signal : &none_s);
 }
 
+// The middle of a merging drain, the same for both kinds of frame (frame_unique.hip).  `a` comes with what is the kind's
+// own: kind, frames, times, signal, have, and where the output goes on the device (out_first and out_members only where the
+// lists are wanted); `name` is the drain's, for the errors.  Here: the scratch and the next tail grow, the hashed attempt,
+// then the exact one on the collision word, the range checks, the deliver step, the copies to the host.  The carried
+// state -- the tail, the late count -- moves only when everything has succeeded.
+static int unique_merge(gnuais_batch *b, gnuais_batch::UniqueState &st, UniqueLaunch &a, const char *name, void *h_out,
+                        int64_t *h_times, int32_t *h_copies, int *n_out, int32_t *h_first, gnuais_hearer *h_members,
+                        int *n_members)
+{
+    static_assert(sizeof(gnuais_hearer) == 24 && sizeof(gnuais_frame_signal) == 8, "a member is three 64-bit words");
+    const uint32_t have = (uint32_t) a.have;
+    const size_t m = (size_t) st.n_tail + have;
+    const size_t rec = a.kind == UniqueKind::Long ? sizeof(gnuais_long_frame) : sizeof(gnuais_frame);
+    const size_t need = unique_scratch_bytes((int) m, a.kind);
+    HIP_TRY(st.scratch.grow(need, need / 4));
+    Buf<uint64_t> &next = st.tail[st.cur ^ 1];
+    HIP_TRY(next.grow(rec * m, rec * m / 4));
+    auto bits_of = [](unsigned long long v) { int n = 1; while (v >> n) ++n; return n; };
+    a.tail = st.tail[st.cur];
+    a.n_tail = st.n_tail;
+    a.tail_out = next;
+    a.window = st.window;
+    a.rows = (long long) b->rows;
+    a.hash_bits = b->uq_hash_bits;
+    a.ch_bits = bits_of((unsigned long long) (b->N - 1));
+    a.time_bits = bits_of(b->rows);          // t + 1 <= rows
+    a.scratch = st.scratch;
+    a.scratch_bytes = st.scratch.bytes;
+    if (h_first) {
+        const size_t need_h = unique_heard_scratch_bytes((int) have);
+        HIP_TRY(st.heard.grow(need_h, need_h / 4));
+        a.heard_scratch = st.heard;
+        a.heard_scratch_bytes = st.heard.bytes;
+    }
+    uint32_t info[UNIQUE_INFO_WORDS] = {0};
+    for (int exact = 0; exact < 2; ++exact) {
+        HIP_TRY(unique_cluster_enqueue(a, exact != 0, nullptr));
+        HIP_TRY(hipMemcpy(info, unique_info(a.scratch), sizeof info, hipMemcpyDeviceToHost));
+        if (!info[UNIQUE_INFO_COLLISION]) break;        // else: two keys share a hash -- once more, by the keys themselves
+    }
+    const uint32_t np = info[UNIQUE_INFO_PRIMARIES];
+    if (np > have || info[UNIQUE_INFO_TAIL] > m)
+        return fail(GNUAIS_E_HIP, (std::string(name) + "_unique: the stage's counts are out of range").c_str());
+    if (np) {
+        HIP_TRY(unique_deliver_enqueue(a, (int) np, nullptr));
+        HIP_TRY(hipMemcpy(h_out, a.out_frames, rec * np, hipMemcpyDeviceToHost));
+        if (a.out_times) HIP_TRY(hipMemcpy(h_times, a.out_times, sizeof(int64_t) * np, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+        if (h_first) {
+            HIP_TRY(hipMemcpy(h_first, a.out_first, sizeof(int32_t) * ((size_t) np + 1), hipMemcpyDeviceToHost));
+            const int32_t nm = h_first[np];
+            if (nm < 0 || (uint32_t) nm > have)
+                return fail(GNUAIS_E_HIP, (std::string(name) + "_heard: the stage's counts are out of range").c_str());
+            HIP_TRY(hipMemcpy(h_members, a.out_members, sizeof(gnuais_hearer) * (size_t) nm, hipMemcpyDeviceToHost));
+            *n_members = (int) nm;
+        }
+    }
+    unsigned long long late = 0;
+    memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
+    st.cur ^= 1;
+    st.n_tail = (int) info[UNIQUE_INFO_TAIL];
+    st.late += (long long) late;
+    *n_out = (int) np;
+    return GNUAIS_OK;
+}
+
 // One record per transmission (gnuais_batch_unique): the queued frames and the open clusters of earlier drains go
-// through frame_unique.hip; the primaries, their times and the copies cross PCIe once.  The carried state -- the tail,
-// the late count -- moves only when everything has succeeded.
+// through unique_merge; the primaries, their times and the copies cross PCIe once.
 // h_first (with h_members and n_members): the clusters' member lists as well (gnuais_batch_drain_frames_heard); the
 // launches of a drain without them are what they were.
 static int drain_unique_impl(gnuais_batch *b, gnuais_frame *h_out, int64_t *h_times, int32_t *h_copies, int max, int *n_out,
                              int32_t *h_first, gnuais_hearer *h_members, int *n_members)
 {
     *n_out = 0;
-    if (!b->uq_window) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch does not merge duplicates (gnuais_batch_unique)");
+    if (!b->uq.window) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch does not merge duplicates (gnuais_batch_unique)");
     if (b->streaming) return fail(GNUAIS_E_STATE, "drain_frames_unique: the batch is streaming (gnuais_batch_stream_nmea)");
     Pending pend;
     if (int rc = read_pending(b, pend)) return rc;
     const uint32_t have = pend.have;
     if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_frames_unique: buffers too small (one entry per pending frame always suffices)");
-    const size_t m = (size_t) b->uq_n_tail + have;
-    if (m) {                                    // without frames the tail still ages
+    if (b->uq.n_tail + have) {                  // without frames the tail still ages
         if (have)
             if (int rc = ensure_post_buffers(b, have)) return rc;
-        const size_t need = unique_scratch_bytes((int) m);
-        HIP_TRY(b->uq_scratch.grow(need, need / 4));
-        Buf<uint32_t> &next = b->uq_tail[b->uq_cur ^ 1];
-        HIP_TRY(next.grow(64 * m, 16 * m));
-        auto bits_of = [](unsigned long long v) { int n = 1; while (v >> n) ++n; return n; };
         UniqueLaunch a;
         a.frames = b->ring[0];
         a.times = b->times;
         a.have = (int) have;
-        a.tail = b->uq_tail[b->uq_cur];
-        a.n_tail = b->uq_n_tail;
-        a.tail_out = next;
-        a.window = b->uq_window;
-        a.rows = (long long) b->rows;
-        a.hash_bits = b->uq_hash_bits;
-        a.ch_bits = bits_of((unsigned long long) (b->N - 1));
-        a.time_bits = bits_of(b->rows);          // t + 1 <= rows
-        a.scratch = b->uq_scratch;
-        a.scratch_bytes = b->uq_scratch.bytes;
         // the text buffer holds 164 bytes per frame: a record, its time and its copies fit side by side
-        a.out_frames = reinterpret_cast<gnuais_frame *>(b->d_text.p);
-        a.out_times = reinterpret_cast<int64_t *>(a.out_frames + have);
+        gnuais_frame *out = reinterpret_cast<gnuais_frame *>(b->d_text.p);
+        a.out_frames = out;
+        a.out_times = reinterpret_cast<int64_t *>(out + have);
         a.out_copies = reinterpret_cast<int32_t *>(a.out_times + have);
         if (h_first) {
             // ... and behind them the lists: 4 bytes per cluster and one more, 24 per member, 104 * have + 16 in all
-            static_assert(sizeof(gnuais_hearer) == 24 && sizeof(gnuais_frame_signal) == 8, "a member is three 64-bit words");
-            const size_t need_h = unique_heard_scratch_bytes((int) have);
-            HIP_TRY(b->uq_heard.grow(need_h, need_h / 4));
             a.signal = b->frame_signal ? b->signal.p : nullptr;
-            a.heard_scratch = b->uq_heard;
-            a.heard_scratch_bytes = b->uq_heard.bytes;
             a.out_first = a.out_copies + have;
             const uintptr_t at = reinterpret_cast<uintptr_t>(a.out_first + have + 1);
             a.out_members = reinterpret_cast<gnuais_hearer *>((at + 15) & ~(uintptr_t) 15);
         }
-        uint32_t info[UNIQUE_INFO_WORDS] = {0};
-        for (int exact = 0; exact < 2; ++exact) {
-            HIP_TRY(unique_cluster_enqueue(a, exact != 0, nullptr));
-            HIP_TRY(hipMemcpy(info, unique_info(a.scratch), sizeof info, hipMemcpyDeviceToHost));
-            if (!info[UNIQUE_INFO_COLLISION]) break;        // else: two keys share a hash -- once more, by the keys themselves
-        }
-        const uint32_t np = info[UNIQUE_INFO_PRIMARIES];
-        if (np > have || info[UNIQUE_INFO_TAIL] > m) return fail(GNUAIS_E_HIP, "drain_frames_unique: the stage's counts are out of range");
-        if (np) {
-            HIP_TRY(unique_deliver_enqueue(a, (int) np, nullptr));
-            HIP_TRY(hipMemcpy(h_out, a.out_frames, sizeof(gnuais_frame) * np, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(h_times, a.out_times, sizeof(int64_t) * np, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
-            if (h_first) {
-                HIP_TRY(hipMemcpy(h_first, a.out_first, sizeof(int32_t) * ((size_t) np + 1), hipMemcpyDeviceToHost));
-                const int32_t nm = h_first[np];
-                if (nm < 0 || (uint32_t) nm > have) return fail(GNUAIS_E_HIP, "drain_frames_heard: the stage's counts are out of range");
-                HIP_TRY(hipMemcpy(h_members, a.out_members, sizeof(gnuais_hearer) * (size_t) nm, hipMemcpyDeviceToHost));
-                *n_members = (int) nm;
-            }
-        }
-        unsigned long long late = 0;
-        memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
-        b->uq_cur ^= 1;
-        b->uq_n_tail = (int) info[UNIQUE_INFO_TAIL];
-        b->uq_late += (long long) late;
-        *n_out = (int) np;
+        if (int rc = unique_merge(b, b->uq, a, "drain_frames", h_out, h_times, h_copies, n_out, h_first, h_members, n_members))
+            return rc;
     }
     return finish_drain(b, pend, h_first ? "drain_frames_heard" : "drain_frames_unique", "; results are incomplete");
 }
@@ -405,83 +425,38 @@ int gnuais_batch_drain_frames_heard(gnuais_batch *b, gnuais_frame *h_out, int64_
 }
 
 // One record per long transmission (gnuais_batch_long_unique): the long ring and the open clusters of earlier drains go
-// through frame_unique_long.hip; the primaries and their copies cross PCIe once.  The same shape as drain_unique_impl: the
-// hashed attempt, then the exact one on the collision word; the carried state moves only when everything has succeeded;
-// it ends as the plain long drain ends, by zeroing the ring's two words.
+// through unique_merge; the primaries and their copies cross PCIe once.  It ends as the plain long drain ends, by zeroing
+// the ring's two words.
 // h_first (with h_members and n_members): the clusters' member lists as well (gnuais_batch_drain_long_frames_heard).
 static int drain_long_unique_impl(gnuais_batch *b, gnuais_long_frame *h_out, int32_t *h_copies, int max, int *n_out,
                                   int32_t *h_first, gnuais_hearer *h_members, int *n_members)
 {
     const char *who = h_first ? "drain_long_frames_heard" : "drain_long_frames_unique";
     *n_out = 0;
-    if (!b->lq_window) return fail(GNUAIS_E_STATE, "drain_long_frames_unique: the batch does not merge long frames (gnuais_batch_long_unique)");
+    if (!b->lq.window) return fail(GNUAIS_E_STATE, "drain_long_frames_unique: the batch does not merge long frames (gnuais_batch_long_unique)");
     uint32_t have = 0;
     bool overflow = false;
     if (int rc = long_pending(b, who, have, overflow)) return rc;
     if ((uint32_t) max < have) return fail(GNUAIS_E_ARG, "drain_long_frames_unique: buffers too small (one entry per pending long frame always suffices)");
-    const size_t m = (size_t) b->lq_n_tail + have;
-    if (m) {                                    // without frames the tail still ages
-        const size_t need = long_unique_scratch_bytes((int) m);
-        HIP_TRY(b->lq_scratch.grow(need, need / 4));
-        Buf<uint64_t> &next = b->lq_tail[b->lq_cur ^ 1];
-        HIP_TRY(next.grow(sizeof(gnuais_long_frame) * m, sizeof(gnuais_long_frame) * m / 4));
+    if (b->lq.n_tail + have) {                  // without frames the tail still ages
         // the output: records, copies, and for the lists one offset more than records and the members, 8-byte aligned
         const size_t at_copies = sizeof(gnuais_long_frame) * have, at_first = at_copies + 4 * (size_t) have;
         const size_t at_members = (at_first + 4 * ((size_t) have + 1) + 7) & ~(size_t) 7;
         const size_t need_out = at_members + sizeof(gnuais_hearer) * have;
         HIP_TRY(b->lq_out.grow(need_out, need_out / 4));
-        auto bits_of = [](unsigned long long v) { int n = 1; while (v >> n) ++n; return n; };
-        LongUniqueLaunch a;
+        UniqueLaunch a;
+        a.kind = UniqueKind::Long;
         a.frames = b->long_ring;
         a.have = (int) have;
-        a.tail = b->lq_tail[b->lq_cur];
-        a.n_tail = b->lq_n_tail;
-        a.tail_out = next;
-        a.window = b->lq_window;
-        a.rows = (long long) b->rows;
-        a.hash_bits = b->uq_hash_bits;
-        a.ch_bits = bits_of((unsigned long long) (b->N - 1));
-        a.time_bits = bits_of(b->rows);          // t + 1 <= rows
-        a.scratch = b->lq_scratch;
-        a.scratch_bytes = b->lq_scratch.bytes;
-        a.out_frames = reinterpret_cast<gnuais_long_frame *>(b->lq_out.p);
+        a.out_frames = b->lq_out.p;
         a.out_copies = reinterpret_cast<int32_t *>(b->lq_out.p + at_copies);
         if (h_first) {
-            static_assert(sizeof(gnuais_hearer) == 24, "a member is three 64-bit words");
-            const size_t need_h = long_unique_heard_scratch_bytes((int) have);
-            HIP_TRY(b->lq_heard.grow(need_h, need_h / 4));
             a.signal = b->long_frame_signal ? b->long_signal.p : nullptr;
-            a.heard_scratch = b->lq_heard;
-            a.heard_scratch_bytes = b->lq_heard.bytes;
             a.out_first = reinterpret_cast<int32_t *>(b->lq_out.p + at_first);
             a.out_members = reinterpret_cast<gnuais_hearer *>(b->lq_out.p + at_members);
         }
-        uint32_t info[UNIQUE_INFO_WORDS] = {0};
-        for (int exact = 0; exact < 2; ++exact) {
-            HIP_TRY(long_unique_cluster_enqueue(a, exact != 0, nullptr));
-            HIP_TRY(hipMemcpy(info, long_unique_info(a.scratch), sizeof info, hipMemcpyDeviceToHost));
-            if (!info[UNIQUE_INFO_COLLISION]) break;        // else: two keys share a hash -- once more, by the keys themselves
-        }
-        const uint32_t np = info[UNIQUE_INFO_PRIMARIES];
-        if (np > have || info[UNIQUE_INFO_TAIL] > m) return fail(GNUAIS_E_HIP, "drain_long_frames_unique: the stage's counts are out of range");
-        if (np) {
-            HIP_TRY(long_unique_deliver_enqueue(a, (int) np, nullptr));
-            HIP_TRY(hipMemcpy(h_out, a.out_frames, sizeof(gnuais_long_frame) * np, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(h_copies, a.out_copies, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
-            if (h_first) {
-                HIP_TRY(hipMemcpy(h_first, a.out_first, sizeof(int32_t) * ((size_t) np + 1), hipMemcpyDeviceToHost));
-                const int32_t nm = h_first[np];
-                if (nm < 0 || (uint32_t) nm > have) return fail(GNUAIS_E_HIP, "drain_long_frames_heard: the stage's counts are out of range");
-                HIP_TRY(hipMemcpy(h_members, a.out_members, sizeof(gnuais_hearer) * (size_t) nm, hipMemcpyDeviceToHost));
-                *n_members = (int) nm;
-            }
-        }
-        unsigned long long late = 0;
-        memcpy(&late, info + UNIQUE_INFO_LATE, sizeof late);
-        b->lq_cur ^= 1;
-        b->lq_n_tail = (int) info[UNIQUE_INFO_TAIL];
-        b->lq_late += (long long) late;
-        *n_out = (int) np;
+        if (int rc = unique_merge(b, b->lq, a, "drain_long_frames", h_out, nullptr, h_copies, n_out, h_first, h_members, n_members))
+            return rc;
     }
     HIP_TRY(hipMemset(b->long_count, 0, sizeof(uint32_t) * 2));
     if (overflow) {
@@ -545,7 +520,7 @@ static int stream_setup(gnuais_batch *b)
                                                "delivery's order table describes the CRC stage's records only");
     if (b->frame_signal) return fail(GNUAIS_E_STATE, "stream_nmea: the batch measures its frames (gnuais_batch_frame_signal); "
                                                      "the streamed delivery carries no records of them");
-    if (b->uq_window) return fail(GNUAIS_E_STATE, "stream_nmea: the batch merges duplicates (gnuais_batch_unique); the "
+    if (b->uq.window) return fail(GNUAIS_E_STATE, "stream_nmea: the batch merges duplicates (gnuais_batch_unique); the "
                                                   "streamed delivery has no such stage");
     if (b->long_frames) return fail(GNUAIS_E_STATE, "stream_nmea: the batch decodes long frames (gnuais_batch_long_frames); "
                                                     "the streamed delivery carries no records of them");

@@ -1,7 +1,7 @@
 // frame_unique.cpp -- gnuais_uniq and gnuais_long_uniq: the duplicate merge of the definition in include/gnuais_hip.h
 // (gnuais_batch_unique, gnuais_batch_long_unique) on the host, one drain per push.  One statement, push_impl, over the
-// kind of record (frame_unique.h: ShortRec, LongRec).  It is the exact statement the device stages (frame_unique.hip,
-// frame_unique_long.hip) must equal bit for bit, and what a node runs over the merged drains of its shards.  Plain C++,
+// kind of record (frame_unique.h: ShortRec, LongRec).  It is the exact statement the device stage (frame_unique.hip over
+// ShortDev and LongDev) must equal bit for bit, and what a node runs over the merged drains of its shards.  Plain C++,
 // no HIP.
 #include "frame_unique.h"
 

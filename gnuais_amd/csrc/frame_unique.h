@@ -1,8 +1,8 @@
-// frame_unique.h -- what the host objects (frame_unique.cpp) and the device stages (frame_unique.hip,
-// frame_unique_long.hip) of the duplicate merge share: how a record's key, repaired bit, 37-bit stamp and time are read
-// -- one traits type per kind of record, ShortRec (gnuais_frame) and LongRec (gnuais_long_frame) -- and the sort words of
-// the definition (include/gnuais_hip.h, gnuais_batch_unique and gnuais_batch_long_unique).  Plain C++, no HIP; internal
-// to csrc.
+// frame_unique.h -- what the host objects (frame_unique.cpp) and the device stage (frame_unique.hip, through the record
+// policies of frame_unique_dev.h) of the duplicate merge share: how a record's key, repaired bit, 37-bit stamp and time
+// are read -- one traits type per kind of record, ShortRec (gnuais_frame) and LongRec (gnuais_long_frame) -- and the sort
+// words of the definition (include/gnuais_hip.h, gnuais_batch_unique and gnuais_batch_long_unique).  Plain C++, no HIP;
+// internal to csrc.
 #pragma once
 #include <stdint.h>
 

@@ -387,10 +387,10 @@ int gnuais_batch_reset(gnuais_batch *b)
     b->hdlc_calls = 0;
     HIP_TRY(hipMemset(b->counters, 0, sizeof(int32_t) * N * 3));      // protodec.c:62-64
     if (b->repaired) HIP_TRY(hipMemset(b->repaired, 0, sizeof(int32_t) * N));
-    b->uq_n_tail = 0;                           // gnuais_batch_unique: no open cluster, nothing late (the window stays)
-    b->uq_late = 0;
-    b->lq_n_tail = 0;                           // gnuais_batch_long_unique: likewise, a state of its own
-    b->lq_late = 0;
+    b->uq.n_tail = 0;                           // gnuais_batch_unique: no open cluster, nothing late (the window stays)
+    b->uq.late = 0;
+    b->lq.n_tail = 0;                           // gnuais_batch_long_unique: likewise, a state of its own
+    b->lq.late = 0;
     for (int q = 0; q < gnuais_batch::HB; ++q) HIP_TRY(hipMemset(b->maxval[q], 0, sizeof(int) * N));
     b->max_cur = 0;
     b->max_last = 0;
@@ -465,7 +465,7 @@ int gnuais_batch_set_option(gnuais_batch *b, const char *name, int value)
             return fail(GNUAIS_E_STATE, "streaming: the batch repairs frames (gnuais_batch_repair); the streamed delivery's order table describes the CRC stage's records only");
         if (value != 0 && b->frame_signal)
             return fail(GNUAIS_E_STATE, "streaming: the batch measures its frames (gnuais_batch_frame_signal); the streamed delivery carries no records of them");
-        if (value != 0 && b->uq_window)
+        if (value != 0 && b->uq.window)
             return fail(GNUAIS_E_STATE, "streaming: the batch merges duplicates (gnuais_batch_unique); the streamed delivery has no such stage");
         if (value != 0 && b->long_repair)
             return fail(GNUAIS_E_STATE, "streaming: the batch repairs long frames (gnuais_batch_long_repair); the streamed delivery carries no records of them");
@@ -1226,10 +1226,10 @@ int gnuais_batch_info(const gnuais_batch *b, const char *name, double *value)
         *value = (double) occ_lag_rows(b->pllinc, b->NT, b->afc_W,
                                        (b->occ_E ? b->occ_long : b->long_frame_signal) ? FS_LONG_MAX_NBITS : FS_MAX_NBITS);
     else if (!strcmp(name, "long_cand_cap")) *value = b->long_cand_cap ? b->long_cand_cap : long_ring_capacity(b);
-    else if (!strcmp(name, "unique")) *value = b->uq_window;
-    else if (!strcmp(name, "unique_late")) *value = (double) b->uq_late;
-    else if (!strcmp(name, "long_unique")) *value = b->lq_window;
-    else if (!strcmp(name, "long_unique_late")) *value = (double) b->lq_late;
+    else if (!strcmp(name, "unique")) *value = b->uq.window;
+    else if (!strcmp(name, "unique_late")) *value = (double) b->uq.late;
+    else if (!strcmp(name, "long_unique")) *value = b->lq.window;
+    else if (!strcmp(name, "long_unique_late")) *value = (double) b->lq.late;
     else if (!strncmp(name, "stream_of_stage_", 16) && name[16] >= '0' && name[16] <= '3' && !name[17]) {
         // which of the batch's POOL candidate streams (creation order) serves stage 0 K2, 1 spare, 2 K2b, 3 K3 right now
         *value = -1;
@@ -1249,7 +1249,7 @@ int gnuais_batch_frame_times(gnuais_batch *b, int on)
     if (!b) return fail(GNUAIS_E_ARG, "frame_times: NULL batch");
     if (b->streaming) return fail(GNUAIS_E_STATE, "frame_times: the batch is streaming (gnuais_batch_stream_nmea); "
                                                   "set_option(\"streaming\", 0) leaves that mode");
-    if (!on && b->uq_window)
+    if (!on && b->uq.window)
         return fail(GNUAIS_E_STATE, "frame_times: the batch merges duplicates by their times (gnuais_batch_unique); "
                                     "gnuais_batch_unique(b, 0) first");
     if (!on && b->frame_signal)
@@ -1288,9 +1288,9 @@ int gnuais_batch_long_frames(gnuais_batch *b, int on)
     b->long_frames = on != 0;
     if (!on) b->long_repair = false;            // gnuais_batch_long_repair: nothing to repair without D'
     if (!on) b->long_frame_signal = false;      // gnuais_batch_long_frame_signal: nothing to measure either
-    if (!on) b->lq_window = 0;                  // gnuais_batch_long_unique: nothing to merge either
-    b->lq_n_tail = 0;                           // any switch: the ring starts over, and so do the merge's tail and late count
-    b->lq_late = 0;
+    if (!on) b->lq.window = 0;                  // gnuais_batch_long_unique: nothing to merge either
+    b->lq.n_tail = 0;                           // any switch: the ring starts over, and so do the merge's tail and late count
+    b->lq.late = 0;
     return GNUAIS_OK;
 }
 
@@ -1453,9 +1453,9 @@ int gnuais_batch_unique(gnuais_batch *b, int window_rows)
         return fail(GNUAIS_E_STATE, "unique: the batch does not time its frames (gnuais_batch_frame_times): copies are "
                                     "merged by their receive times");
     if (int rc = gnuais_batch_sync(b)) return rc;
-    b->uq_window = window_rows;
-    b->uq_n_tail = 0;
-    b->uq_late = 0;
+    b->uq.window = window_rows;
+    b->uq.n_tail = 0;
+    b->uq.late = 0;
     return GNUAIS_OK;
 }
 
@@ -1468,23 +1468,23 @@ int gnuais_batch_long_unique(gnuais_batch *b, int window_rows)
         return fail(GNUAIS_E_STATE, "long_unique: the batch does not decode long frames (gnuais_batch_long_frames): "
                                     "the merge works on that decoder's records");
     if (int rc = gnuais_batch_sync(b)) return rc;
-    b->lq_window = window_rows;
-    b->lq_n_tail = 0;
-    b->lq_late = 0;
+    b->lq.window = window_rows;
+    b->lq.n_tail = 0;
+    b->lq.late = 0;
     return GNUAIS_OK;
 }
 
 int gnuais_batch_long_unique_late(gnuais_batch *b, long long *late)
 {
     if (!b || !late) return fail(GNUAIS_E_ARG, "long_unique_late: argument");
-    *late = b->lq_late;
+    *late = b->lq.late;
     return GNUAIS_OK;
 }
 
 int gnuais_batch_unique_late(gnuais_batch *b, long long *late)
 {
     if (!b || !late) return fail(GNUAIS_E_ARG, "unique_late: argument");
-    *late = b->uq_late;
+    *late = b->uq.late;
     return GNUAIS_OK;
 }
 

@@ -410,78 +410,55 @@ struct LongSignalLaunch {
 };
 hipError_t launch_long_signal(const LongSignalLaunch &a, hipStream_t stream);
 
-// ---- one record per transmission: the duplicate merge of a drain (frame_unique.hip; definition in include/gnuais_hip.h) ----
-// Entries = [tail | ring]: n_tail open clusters of earlier drains (16 words each: t_last, then the key as a record
-// holds it) and the `have` frames of the ring with their times.  unique_cluster_enqueue() queues everything up to the
-// compacted primaries and the next tail (tail_out: room for n_tail + have entries, another buffer than tail) and leaves
-// UNIQUE_INFO_WORDS words at unique_info(scratch); `exact`: group by the key words themselves instead of the hash --
-// what the caller repeats the call with when the collision word came back set (nothing of the first attempt is kept).
-// unique_deliver_enqueue() then sorts the n_primaries into output order and gathers out_frames / out_times / out_copies.
+// ---- one record per transmission: the duplicate merge of a drain, for the short and the long frames (frame_unique.hip;
+// gnuais_batch_unique and gnuais_batch_long_unique in include/gnuais_hip.h) ----
+// Entries = [tail | ring]: n_tail open clusters of earlier drains and the `have` frames of the ring.  Short kind: a tail
+// entry is 16 words (t_last, then the key as a record holds it), the frames' times lie beside the ring, every buffer is
+// 16-byte aligned.  Long kind: a tail entry is a 38-word record with t_last in its t words and word 4 masked to the key,
+// the member time is the record's own t (times and out_times stay null), every buffer is 8-byte aligned, and the signal
+// records are long_signal.hip's, where it is on.
+// unique_cluster_enqueue() queues everything up to the compacted primaries and the next tail (tail_out: room for
+// n_tail + have entries, another buffer than tail) and leaves UNIQUE_INFO_WORDS words at unique_info(scratch); `exact`:
+// group by the key words themselves instead of the hash -- what the caller repeats the call with when the collision word
+// came back set (nothing of the first attempt is kept).  unique_deliver_enqueue() then sorts the n_primaries into output
+// order and gathers out_frames / out_times / out_copies.
 constexpr int UNIQUE_INFO_COLLISION = 0;    // != 0: equal hashes with unequal keys were seen
 constexpr int UNIQUE_INFO_CLUSTERS = 1;
 constexpr int UNIQUE_INFO_PRIMARIES = 2;    // records to deliver
 constexpr int UNIQUE_INFO_TAIL = 3;         // entries written to tail_out
 constexpr int UNIQUE_INFO_LATE = 4;         // two words: late copies of this drain (uint64)
 constexpr int UNIQUE_INFO_WORDS = 8;
+enum class UniqueKind { Short, Long };      // gnuais_frame (the default wherever a kind is taken) / gnuais_long_frame
 struct UniqueLaunch {
-    const void *frames;            // gnuais_frame[have]: the ring
-    const int64_t *times;          // [have], by ring slot
+    UniqueKind kind = UniqueKind::Short;
+    const void *frames;            // gnuais_frame[have] / gnuais_long_frame[have]: the ring
+    const int64_t *times = nullptr;     // short: [have], by ring slot
     int have;
-    const void *tail;              // [n_tail][16] words
+    const void *tail;              // [n_tail][16] / [n_tail][38] words
     int n_tail;
     void *tail_out;
     long long window, rows;        // W, and the batch's row count at the drain
     int hash_bits;                 // 1..64: bits of the hash in use (set_option("unique_hash_bits"))
     int ch_bits, time_bits;        // channel < 2^ch_bits, t + 1 < 2^time_bits: the width of the member-order word
     void *scratch;
-    size_t scratch_bytes;          // >= unique_scratch_bytes(n_tail + have)
-    struct gnuais_frame *out_frames;
-    int64_t *out_times;
+    size_t scratch_bytes;          // >= unique_scratch_bytes(n_tail + have, kind)
+    void *out_frames;              // records of the kind
+    int64_t *out_times = nullptr;  // short
     int32_t *out_copies;
-    // the member lists (gnuais_batch_drain_frames_heard); out_first null: no lists wanted, and the rest is not read.
-    // unique_deliver_enqueue() then also fills out_first[n_primaries + 1] (the running sum of out_copies, from 0) and
-    // out_members[sum of the copies <= have] (16-byte aligned), from the records, times and `signal` by ring slot.
+    // the member lists (gnuais_batch_drain_frames_heard, _long_frames_heard); out_first null: no lists wanted, and the
+    // rest is not read.  unique_deliver_enqueue() then also fills out_first[n_primaries + 1] (the running sum of
+    // out_copies, from 0) and out_members[sum of the copies <= have] (16-byte aligned for the short kind, 8-byte for the
+    // long), from the records, times and `signal` by ring slot.
     const void *signal = nullptr;               // gnuais_frame_signal[have], or null: zeros
     void *heard_scratch = nullptr;
     size_t heard_scratch_bytes = 0;             // >= unique_heard_scratch_bytes(have)
     int32_t *out_first = nullptr;
     struct gnuais_hearer *out_members = nullptr;
 };
-size_t unique_scratch_bytes(int n_entries);
+size_t unique_scratch_bytes(int n_entries, UniqueKind kind = UniqueKind::Short);
 size_t unique_heard_scratch_bytes(int have);
 uint32_t *unique_info(void *scratch);
 hipError_t unique_cluster_enqueue(const UniqueLaunch &a, bool exact, hipStream_t s);
 hipError_t unique_deliver_enqueue(const UniqueLaunch &a, int n_primaries, hipStream_t s);
-
-// ---- the same merge over the long frames (frame_unique_long.hip; gnuais_batch_long_unique in include/gnuais_hip.h) ----
-// Entries = [tail | long ring]: a tail entry is a 38-word record with t_last in its t words and word 4 masked to the key;
-// the member time is the record's own t, there are no times; the signal records are long_signal.hip's, where it is on.
-// The two calls, the info words (UNIQUE_INFO_*) and the repeat in the exact form are those of the stage above.  Every
-// buffer is 8-byte aligned.
-struct LongUniqueLaunch {
-    const void *frames;            // gnuais_long_frame[have]: the long ring
-    int have;
-    const void *tail;              // [n_tail][38] words
-    int n_tail;
-    void *tail_out;                // room for n_tail + have entries, another buffer than tail
-    long long window, rows;
-    int hash_bits;
-    int ch_bits, time_bits;
-    void *scratch;
-    size_t scratch_bytes;          // >= long_unique_scratch_bytes(n_tail + have)
-    struct gnuais_long_frame *out_frames;
-    int32_t *out_copies;
-    // the member lists (gnuais_batch_drain_long_frames_heard); out_first null: no lists wanted
-    const void *signal = nullptr;               // gnuais_frame_signal[have] by ring slot (long_signal.hip), or null: zeros
-    void *heard_scratch = nullptr;
-    size_t heard_scratch_bytes = 0;             // >= long_unique_heard_scratch_bytes(have)
-    int32_t *out_first = nullptr;
-    struct gnuais_hearer *out_members = nullptr;
-};
-size_t long_unique_scratch_bytes(int n_entries);
-size_t long_unique_heard_scratch_bytes(int have);
-uint32_t *long_unique_info(void *scratch);
-hipError_t long_unique_cluster_enqueue(const LongUniqueLaunch &a, bool exact, hipStream_t s);
-hipError_t long_unique_deliver_enqueue(const LongUniqueLaunch &a, int n_primaries, hipStream_t s);
 
 } // namespace gnuais

@@ -6,7 +6,9 @@ object it is about to build).  Two things went unnoticed for rounds because noth
   * a padded register request: K3 used 59 VGPRs and asked for 104 -- the compiler derives an occupancy from a workgroup's
     STATIC shared memory and raises NumVGPRsForWavesPerEU to match it, and a wave that asks for 104 registers waits for a
     FIR wave to retire where one that asks for 72 fits.
-usage: check_kernel_resources.py file.s name_substring [name_substring ...]   (every kernel whose symbol contains one)"""
+usage: check_kernel_resources.py file.s name[=N] [name[=N] ...]   (every kernel whose symbol contains a name; each name
+must match at least one kernel, with =N exactly N: a kernel that was renamed, or an instance that is no longer built, does
+not leave the check silently)"""
 import re
 import sys
 
@@ -27,13 +29,15 @@ def kernels(text):
 
 
 def main():
-    path, wanted = sys.argv[1], sys.argv[2:]
+    path, wanted = sys.argv[1], [w.partition("=") for w in sys.argv[2:]]
     bad = 0
-    seen = 0
+    matches = {w: 0 for w, _, _ in wanted}
     for name, k in kernels(open(path).read()).items():
-        if not any(w in name for w in wanted) or "NumVgprs" not in k:
+        hit = [w for w in matches if w in name]
+        if not hit or "NumVgprs" not in k:
             continue
-        seen += 1
+        for w in hit:
+            matches[w] += 1
         used = k["NumVgprs"] + k.get("NumAgprs", 0)
         asked = k.get("NumVGPRsForWavesPerEU", used)
         line = f"{name[:70]}: {used} registers in use, {asked} requested, {k.get('ScratchSize', 0)} bytes of scratch"
@@ -45,9 +49,13 @@ def main():
             bad += 1
         else:
             print(line)
-    if not seen:
-        print(f"{path}: no kernel matching {wanted}")
-        return 1
+    for w, _, n in wanted:
+        if n and matches[w] != int(n):
+            print(f"{path}: {matches[w]} kernels matching {w}, {n} expected")
+            bad += 1
+        elif not matches[w]:
+            print(f"{path}: no kernel matching {w}")
+            bad += 1
     return 1 if bad else 0
 
 

@@ -1,4 +1,4 @@
-"""What delivering each long transmission once on the device (gnuais_batch_long_unique, frame_unique_long.hip) costs
+"""What delivering each long transmission once on the device (gnuais_batch_long_unique, frame_unique.hip) costs
 against the merge a user could do with the host object alone, at C3's width (16384 channels): --copies receivers hear
 each stream of long bursts, with delays below 41 rows.
 

@@ -1,4 +1,4 @@
-// long_unique_kernel_main.cpp -- TEST INFRASTRUCTURE: frame_unique_long.hip's own text on the CPU
+// long_unique_kernel_main.cpp -- TEST INFRASTRUCTURE: frame_unique.hip's own text on the CPU, over the long frames
 // (tests/test_long_unique_cpu.py builds it under ASan + UBSan with tests/c/hip_serial_shim in front of the HIP and rocPRIM
 // headers: the kernels have no barrier, no LDS and no cross-lane operation, so a launch is a loop over lanes), driven as
 // gnuais_batch_drain_long_frames_unique / _heard drive it: the hashed attempt, the exact one when the collision word is
@@ -13,7 +13,7 @@
 #include <vector>
 Idx threadIdx, blockIdx, gridDim;
 #include "../../include/gnuais_hip.h"
-#include LONG_UNIQUE_KERNEL_TEXT
+#include UNIQUE_KERNEL_TEXT
 using namespace gnuais;
 static int bits_of(unsigned long long v) { int n = 1; while (v >> n) ++n; return n; }
 // a buffer of exactly `bytes` bytes, 8-byte aligned as the interface asks (ASan sees the first byte behind it)
@@ -41,7 +41,7 @@ int main(int argc, char **argv)
             const bool heard = (d & 1) == 0;
             int32_t *first = heard ? exact<int32_t>(4 * (N + 1)) : nullptr;
             gnuais_hearer *mem = heard ? exact<gnuais_hearer>(sizeof(gnuais_hearer) * N) : nullptr;
-            char *hscratch = heard ? exact<char>(long_unique_heard_scratch_bytes(n)) : nullptr;
+            char *hscratch = heard ? exact<char>(unique_heard_scratch_bytes(n)) : nullptr;
             uint32_t max_ch = 0;
             for (size_t i = 0; i < N; ++i) max_ch = fr[i].channel > max_ch ? fr[i].channel : max_ch;
             const int m = n_tail + n;
@@ -49,10 +49,11 @@ int main(int argc, char **argv)
             uint32_t np = 0;
             if (heard) first[0] = 0;
             if (m) {
-                const size_t sb = long_unique_scratch_bytes(m);
+                const size_t sb = unique_scratch_bytes(m, UniqueKind::Long);
                 char *scratch = exact<char>(sb);
                 uint64_t *next = exact<uint64_t>(sizeof(gnuais_long_frame) * (size_t) m);
-                LongUniqueLaunch a;
+                UniqueLaunch a;
+                a.kind = UniqueKind::Long;
                 a.frames = fr; a.have = n;
                 a.tail = n_tail ? tail : nullptr; a.n_tail = n_tail; a.tail_out = next;
                 a.window = head[0]; a.rows = rows; a.hash_bits = hash_bits;
@@ -60,18 +61,18 @@ int main(int argc, char **argv)
                 a.scratch = scratch; a.scratch_bytes = sb;
                 a.out_frames = out; a.out_copies = oc;
                 if (heard) {
-                    a.heard_scratch = hscratch; a.heard_scratch_bytes = long_unique_heard_scratch_bytes(n);
+                    a.heard_scratch = hscratch; a.heard_scratch_bytes = unique_heard_scratch_bytes(n);
                     a.out_first = first; a.out_members = mem;
                 }
-                const uint32_t *info = long_unique_info(a.scratch);
+                const uint32_t *info = unique_info(a.scratch);
                 for (int ex = 0; ex < 2; ++ex) {
-                    if (long_unique_cluster_enqueue(a, ex != 0, nullptr) != hipSuccess) return 7;
+                    if (unique_cluster_enqueue(a, ex != 0, nullptr) != hipSuccess) return 7;
                     exact_runs += ex;
                     if (!info[UNIQUE_INFO_COLLISION]) break;
                 }
                 np = info[UNIQUE_INFO_PRIMARIES];
                 if (np > (uint32_t) n || info[UNIQUE_INFO_TAIL] > (uint32_t) m) return 8;
-                if (long_unique_deliver_enqueue(a, (int) np, nullptr) != hipSuccess) return 9;
+                if (unique_deliver_enqueue(a, (int) np, nullptr) != hipSuccess) return 9;
                 if (heard && np) nm = first[np];
                 if (nm > n) return 11;
                 unsigned long long add = 0;

@@ -1,5 +1,6 @@
 """scripts/check_kernel_resources.py -- the build-time check of what the chain's kernels ask the hardware for -- on
-hand-made ISA listings: a clean kernel passes, scratch fails, a padded register request fails, an unknown name fails."""
+hand-made ISA listings: a clean kernel passes, scratch fails, a padded register request fails, a name that matches no kernel fails even beside names that do, and name=N asks for
+exactly N kernels."""
 import os
 import subprocess
 import sys
@@ -41,6 +42,26 @@ def test_only_the_named_kernels_are_judged(tmp_path):
     assert run(tmp_path, text, "hdlc_crc_kernel")[0] == 0
     assert run(tmp_path, text, "hdlc_deframe_kernel")[0] == 1
     assert run(tmp_path, text, "no_such_kernel")[0] == 1
+
+
+def test_every_name_given_must_match_a_kernel(tmp_path):
+    text = listing("_ZN6gnuais15hdlc_crc_kernelE", 68, 68, 0) + listing("_ZN6gnuais19hdlc_deframe_kernelE", 72, 72, 0)
+    assert run(tmp_path, text, "hdlc_crc_kernel", "hdlc_deframe_kernel")[0] == 0
+    rc, out = run(tmp_path, text, "hdlc_crc_kernel", "no_such_kernel", "hdlc_deframe_kernel")
+    assert rc == 1 and "no kernel matching no_such_kernel" in out and "hdlc_crc_kernel" in out
+
+
+def test_a_count_asks_for_exactly_that_many_kernels(tmp_path):
+    two = listing("_ZN6gnuais16uniq_keys_kernelINS_8ShortDevEEE", 24, 24, 0) + listing("_ZN6gnuais16uniq_keys_kernelINS_7LongDevEEE", 42, 42, 0)
+    one = listing("_ZN6gnuais18uniq_slot2q_kernelE", 6, 6, 0)
+    assert run(tmp_path, two + one, "uniq_keys_kernel=2", "uniq_slot2q_kernel=1")[0] == 0
+    assert run(tmp_path, two + one, "uniq_keys_kernel", "uniq_slot2q_kernel")[0] == 0
+    rc, out = run(tmp_path, two + one, "uniq_keys_kernel=3", "uniq_slot2q_kernel=1")       # too few
+    assert rc == 1 and "2 kernels matching uniq_keys_kernel, 3 expected" in out
+    rc, out = run(tmp_path, two + one, "uniq_keys_kernel=1", "uniq_slot2q_kernel=1")       # too many
+    assert rc == 1 and "2 kernels matching uniq_keys_kernel, 1 expected" in out
+    rc, out = run(tmp_path, one, "uniq_keys_kernel=2", "uniq_slot2q_kernel=1")             # none at all
+    assert rc == 1 and "0 kernels matching uniq_keys_kernel, 2 expected" in out
 
 
 def test_the_makefile_runs_the_check_on_the_chain_kernels():

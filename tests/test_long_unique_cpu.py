@@ -1,8 +1,8 @@
 """Each long transmission once, on the CPU: the host object gnuais_long_uniq (frame_unique.cpp over LongRec) against the
 restatement tests/long_unique_ref.py over random record sets cut into drains, with the lists and the invariants of the
-definition; the unit by itself under ASan + UBSan; the device stage's own text (frame_unique_long.hip) behind the serial
-shim under ASan + UBSan with the full and with a truncated hash; on the oracle, the property the tail rule rests on and
-that the GPU tests' input really merges; and the header, the exports and the build's resource check."""
+definition; the unit by itself under ASan + UBSan; the device stage's own text (frame_unique.hip over LongDev) behind
+the serial shim under ASan + UBSan with the full and with a truncated hash; on the oracle, the property the tail rule
+rests on and that the GPU tests' input really merges; and the header, the exports and the build's resource check."""
 import collections
 import os
 import subprocess
@@ -229,14 +229,14 @@ def kernel_exe(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("luq") / "long_unique_kernel.bin")
     subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "tests", "c", "hip_serial_shim"),
-                           "-I", CSRC, f'-DLONG_UNIQUE_KERNEL_TEXT="{os.path.join(CSRC, "frame_unique_long.hip")}"',
+                           "-I", CSRC, f'-DUNIQUE_KERNEL_TEXT="{os.path.join(CSRC, "frame_unique.hip")}"',
                            os.path.join(ROOT, "tests", "c", "long_unique_kernel_main.cpp"), "-o", exe])
     return exe
 
 
 @pytest.mark.parametrize("hash_bits", [64, 3, 1])
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path, kernel_exe, hash_bits):
-    """frame_unique_long.hip compiled for the CPU behind tests/c/hip_serial_shim under ASan + UBSan, driven as the drain
+    """frame_unique.hip compiled for the CPU behind tests/c/hip_serial_shim under ASan + UBSan, driven as the drain
     drives it with buffers of exactly the sizes the interface asks for, drains with and without the lists alternating: the
     records, copies, lists and the late count are the restatement's -- with the full hash without ever taking the exact
     path, with 3 and 1 bits through it in more than 100 drains"""
@@ -305,13 +305,20 @@ def test_symbols_declared_exported_bound_and_the_kernels_are_in_the_builds_resou
         assert name in lib.SYMBOLS and name + "(" in header and hasattr(lib.load(), name), name
     assert "no duplicate merge" not in header and '"long_unique"' in header and '"long_unique_late"' in header
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    kernels = ["luniq_keys_kernel", "luniq_digit_kernel", "luniq_boundary_kernel", "luniq_members_kernel",
-               "luniq_clusters_kernel", "luniq_tail_kernel", "luniq_gather_kernel", "luniq_slot2q_kernel", "luniq_heard_kernel"]
-    assert "$(CHECK_RES) $(BUILD)/frame_unique_long.s " + " ".join(kernels) in mk and "$(BUILD)/frame_unique_long.o" in mk
-    text = open(os.path.join(CSRC, "frame_unique_long.hip")).read()
+    # every kernel of the long stage: an instance of frame_unique.hip's templates, counted with the short kind's (=2); the
+    # tail kernel is the long kind's alone, slot2q is no template (=1)
+    kernels = {"uniq_keys_kernel": 2, "uniq_digit_kernel": 2, "uniq_boundary_kernel": 2, "uniq_members_kernel": 2,
+               "uniq_clusters_kernel": 2, "uniq_tail_kernel": 1, "uniq_gather_kernel": 2, "uniq_slot2q_kernel": 1,
+               "uniq_heard_kernel": 2}
+    assert "$(CHECK_RES) $(BUILD)/frame_unique.s " + " ".join(f"{k}={n}" for k, n in kernels.items()) + "\n" in mk
+    assert "$(BUILD)/frame_unique.o" in mk
+    text = open(os.path.join(CSRC, "frame_unique.hip")).read()
     for k in kernels:
         assert f"void {k}(" in text
+    assert "cluster_enqueue<LongDev>" in text and "deliver_enqueue<LongDev>" in text
     assert "__shared__" not in text and "asm" not in text
+    dev = open(os.path.join(CSRC, "frame_unique_dev.h")).read()
+    assert "__shared__" not in dev and "asm" not in dev
     from gnuais_amd import receiver
     for m in ("long_unique", "drain_long_frames_unique", "drain_long_frames_heard", "long_unique_late"):
         assert hasattr(receiver.ReceiverBatch, m)

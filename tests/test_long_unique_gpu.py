@@ -1,4 +1,4 @@
-"""Each long transmission once on the device (gnuais_batch_long_unique, frame_unique_long.hip).  The expected value is
+"""Each long transmission once on the device (gnuais_batch_long_unique, frame_unique.hip over LongDev).  The expected value is
 always the restatement tests/long_unique_ref.py applied to what drain_long_frames() of a TWIN batch gives for the same
 calls -- a path that exists and is tested by itself -- so the new drains are never compared with themselves.  Every test
 also checks that the chain's frames, counters, fsm_state and pll_state equal the twin's."""
