@@ -318,7 +318,9 @@ __global__ __launch_bounds__(256) void nmea_write_kernel(
 // mantissa times 10^N as a 128-bit integer, shifted, rounded half to even on the exact value -- what
 // glibc prints).
 
-constexpr int MSG_LINE_MAX = 512;               // longest line: type 6 / 8 with the weather report, < 460 bytes
+constexpr int MSG_LINE_MAX = 512;               // longest line: type 6 with the weather report, every field at its widest,
+                                                // ten-digit MMSIs, 45 bytes: 435 bytes with its '\n', as the reference
+                                                // prints it (tests/test_message_sweep_cpu.py: LONGEST_LINE)
 
 struct LineOut {
     char *p;

@@ -146,6 +146,17 @@ def make_fir_plan(harness):
     print("fir_plan.npz", os.path.getsize(path), len(tables), "tables,", int(out["plan_rows"].sum()), "plans;", census)
 
 
+def make_message_sweep():
+    """message_sweep.npz: what the reference sends and prints for every frame of tests/message_cases.py.  It may not
+    outgrow ref_pins.npz as committed with it (618 165 bytes): thin the integer-only sweeps if it does, never the ones
+    that feed a %.Nf field."""
+    import ref_pins
+    ref_pins.store_message_sweep()
+    size = os.path.getsize(ref_pins.MESSAGE_SWEEP)
+    print("message_sweep.npz", size)
+    assert size <= 618165, size
+
+
 def cases_frame_dtype():
     from oracle_lib import FRAME_DTYPE
     return FRAME_DTYPE
@@ -164,6 +175,8 @@ def main():
     if sys.argv[1:] == ["ref_pins"]:
         import ref_pins
         return ref_pins.store()
+    if sys.argv[1:] == ["message_sweep"]:
+        return make_message_sweep()
     ref = reference()
     # 1. full chain, 48 kHz, 2 channels (config C1 shape)
     np.savez_compressed(os.path.join(HERE, "chain_48k.npz"), **run_chain(cases.chain_48k()))
@@ -211,6 +224,8 @@ def main():
     # 7. the reference's answers on the seeded inputs of the pin tests (tests/ref_pins.py)
     import ref_pins
     ref_pins.store()
+    # 8. the sentences and stdout lines of the field sweeps (tests/message_cases.py)
+    make_message_sweep()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

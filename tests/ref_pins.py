@@ -9,11 +9,13 @@ import numpy as np
 
 import cases
 import deframer_cases
+import message_cases
 import pll_ref
 from gnuais_amd import params, synth
 from oracle_lib import have_reference, reference
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_pins.npz")
+MESSAGE_SWEEP = os.path.join(os.path.dirname(GOLDEN), "message_sweep.npz")      # a fixture of its own: it is large
 FSM = ("state", "nstartsign", "antallpreamble", "antallenner", "bitstuff", "last", "bufferpos")
 PINS = {}
 
@@ -172,6 +174,12 @@ def _vessels(seed, n_mmsi):
     return {"table": _bytes(reference().cache_of_frames(fr, n_ch, pieces=[300, 301]).tobytes())}
 
 
+def _message_sweep():
+    """what the reference sends and prints for the frames of tests/message_cases.py, group after group"""
+    nm, seq, tx = reference().nmea_of_frames(message_cases.everything(), message_cases.N_CH, stdout=True)
+    return {"nmea": _bytes(nm), "seq": seq, "text": _bytes(tx)}
+
+
 PINS["taps"] = _taps
 for _s in (1, 2, 3):
     PINS["signal_streams_%d" % _s] = (lambda s: lambda: _chain(signal_streams(s), bits_of=s % 4))(_s)
@@ -202,6 +210,18 @@ def want(key):
     return got
 
 
+def want_message_sweep():
+    """want()'s rule for the sweep of tests/message_cases.py, whose answer is stored in MESSAGE_SWEEP"""
+    if have_reference():
+        return _message_sweep()
+    with np.load(MESSAGE_SWEEP) as z:
+        return {k: z[k] for k in z.files}
+
+
 def store():
     """tests/golden/make_golden.py: every pin's answer from the live reference into GOLDEN."""
     np.savez_compressed(GOLDEN, **{"%s/%s" % (k, n): v for k, fn in PINS.items() for n, v in fn().items()})
+
+
+def store_message_sweep():
+    np.savez_compressed(MESSAGE_SWEEP, **_message_sweep())
