@@ -75,7 +75,7 @@ __global__ void hdlc_long_reset_kernel(uint32_t *__restrict__ lctl, int32_t *__r
     }
 }
 
-extern __shared__ uint32_t long_pack[];                     // [LPACK_MAX + 1][blockDim.x]
+HIP_DYNAMIC_SHARED(uint32_t, long_pack)                     // [LPACK_MAX + 1][blockDim.x]
 
 // The kernel in its two compile-time forms.  KEEP_RAW = false is D' as gnuais_batch_long_frames defines it and is what
 // runs while the repair of long frames is off: its last five arguments are not read.  KEEP_RAW = true (gnuais_batch_long_repair) keeps what that form destroys:

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(RP_BLOCK) void hdlc_repair_kernel(
     __shared__ uint16_t fail_row[RP_BLOCK];
     __shared__ uint32_t n_fail;
     __shared__ uint32_t recbuf[RP_WAVES][16];
-    extern __shared__ uint32_t rp_rows[];           // [RP_BLOCK][RP_ROW]
+    HIP_DYNAMIC_SHARED(uint32_t, rp_rows)           // [RP_BLOCK][RP_ROW]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int c_own = blockIdx.x * K3_CH + tid;
 

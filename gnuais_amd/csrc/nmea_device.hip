@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void nmea_write_kernel(
     // dynamic shared memory (NMEA_WRITE_LDS_BYTES at launch): as a static array the 42 KB made the compiler pad this
     // kernel's register request from 32 to 136 per wave (the occupancy it derives from static LDS), and the kernel runs
     // inside the delivery loop beside the chain's stages
-    extern __shared__ __attribute__((aligned(16))) char nmea_write_dyn[];
+    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) char, nmea_write_dyn)
     char *const buf = nmea_write_dyn;
     __shared__ uint32_t s_base, s_end, s_sent;
     const int tid = threadIdx.x;
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(256) void message_pack_kernel(const char *__restric
                                                            const uint32_t *__restrict__ off, int n, char *__restrict__ out,
                                                            unsigned long long out_cap, uint32_t *__restrict__ info)
 {
-    extern __shared__ __attribute__((aligned(16))) char message_pack_dyn[];     // MESSAGE_PACK_LDS bytes at launch (see nmea_write_kernel)
+    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) char, message_pack_dyn)     // MESSAGE_PACK_LDS bytes at launch (see nmea_write_kernel)
     char *const buf = message_pack_dyn;
     __shared__ uint32_t s_lines;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;

@@ -41,7 +41,7 @@ constexpr int OCC_HIST_WORDS = OCC_BINS * 32;
 constexpr int OCC_LDS_WORDS = OCC_HIST_WORDS + OCC_THREADS + OCC_LANES + 3 * OCC_THREADS;
 static_assert(OCC_BINS % OCC_WAVES == 0, "a wave's share of the bins");
 
-extern __shared__ uint32_t occ_lds[];
+HIP_DYNAMIC_SHARED(uint32_t, occ_lds)       // OCC_LDS_WORDS at the finaliser's launch
 
 // grid: 1-D, block b = (block-of-n group b / n_groups, channel group b % n_groups); a thread walks the blocks of n of its
 // group with stride `stride` = the number of groups

@@ -1,5 +1,5 @@
 // heard_kernel_main.cpp -- TEST INFRASTRUCTURE: frame_unique.hip's own text on the CPU with the member lists wanted
-// (tests/test_heard_cpu.py builds it under ASan + UBSan with tests/c/hip_serial_shim in front of the HIP and rocPRIM
+// (tests/test_heard_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu (serial mode) in front of the HIP and rocPRIM
 // headers), driven as gnuais_batch_drain_frames_heard drives it: the hashed attempt, the exact one when the collision
 // word is set, the lists behind the kept attempt only, the double-buffered tail.  Drains with and without the lists
 // alternate on one state.  Every buffer is allocated at exactly the size the launch interface asks for; the members
@@ -11,9 +11,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-Idx threadIdx, blockIdx, gridDim;
 #include "../../include/gnuais_hip.h"
-#include UNIQUE_KERNEL_TEXT
+#include "frame_unique.hip"
 using namespace gnuais;
 static int bits_of(unsigned long long v) { int n = 1; while (v >> n) ++n; return n; }
 int main(int argc, char **argv)

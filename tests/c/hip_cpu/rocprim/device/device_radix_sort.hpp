@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: rocprim::radix_sort_pairs' interface on the CPU (tests/c/hip_serial_shim): a size query with a
+// TEST INFRASTRUCTURE: rocprim::radix_sort_pairs' interface on the CPU (tests/c/hip_cpu): a size query with a
 // null temporary, then a STABLE sort on bits [begin_bit, end_bit) of the keys, into the output arrays
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,3 +1,3 @@
-// TEST INFRASTRUCTURE: rocprim::plus for the CPU build of frame_unique.hip (tests/c/hip_serial_shim)
+// TEST INFRASTRUCTURE: rocprim::plus for the CPU builds of the kernel files (tests/c/hip_cpu)
 #pragma once
 namespace rocprim { template <class T> struct plus { T operator()(T a, T b) const { return a + b; } }; }

@@ -1,22 +1,16 @@
-// long_kernel_main.cpp -- TEST INFRASTRUCTURE: hdlc_long.hip's kernel, its own text, on the CPU (tests/test_long_cpu.py
-// builds it under ASan + UBSan with tests/c/hip_wave_shim in front of the HIP headers): a std::thread per lane, one block
-// of 64 at a time.  Every buffer has exactly the size the launch interface promises (kernels.h: LongLaunch).  The chain's
+// long_kernel_main.cpp -- TEST INFRASTRUCTURE: hdlc_long.hip's own text on the CPU, run through launch_hdlc_long_reset()
+// and launch_hdlc_long() (tests/test_long_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu in front of the HIP
+// headers).  Every buffer has exactly the size the launch interface promises (kernels.h: LongLaunch).  The chain's
 // deframer, whose bit count D' reads, is stood in for by its count alone: ctl[2] / ctl[5] move on by the bits of a call's
 // packs before the kernel runs, as they have when the launch behind K3 starts.
 // argv: in out.  in: int64 N, n_seg, seg_words, frame_cap, n_calls; uint64 bits fed before the first call [N]; then per
 // call int64 len, n0, uint32 segbits [N][n_seg][16], uint32 segcnt [N][n_seg].
 // out: per call uint32 lctl [3][N]; then int32 counters [2][N], uint32 frame_count [2], the ring's records.
 #include <hip/hip_runtime.h>
-#include <thread>
+#include <algorithm>
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
-thread_local Idx threadIdx;
-Idx blockIdx, blockDim;
-std::barrier<> *g_block_barrier;
-std::barrier<> *g_wave_barrier[4];
-unsigned char g_pred[256];
-namespace gnuais { uint32_t long_pack[(16 + 1) * 64]; }
 #include "hdlc_long.hip"
 
 int main(int argc, char **argv)
@@ -34,12 +28,11 @@ int main(int argc, char **argv)
     const int n_calls = (int) hd[4];
     std::vector<uint64_t> seen(N);
     if (fread(seen.data(), 8, N, f) != (size_t) N) return 4;
-    std::vector<uint32_t> ctl((size_t) HDLC_CTL_WORDS * N, 0), lctl((size_t) LONG_CTL_WORDS * N, 0);
+    std::vector<uint32_t> ctl((size_t) HDLC_CTL_WORDS * N, 0), lctl((size_t) LONG_CTL_WORDS * N, 0xdeadbeefu);
     std::vector<uint32_t> open((size_t) LONG_REC_WORDS * N, 0xdeadbeefu), frames((size_t) cap * LONG_FRAME_WORDS, 0xdeadbeefu);
     std::vector<int32_t> counters((size_t) 2 * N, 0);
     uint32_t count[2] = {0, 0};
-    for (int c = 0; c < N; ++c) lctl[c] = 1;     // ST_SKURR: what launch_hdlc_long_reset() leaves
-    blockDim.x = 64;
+    if (launch_hdlc_long_reset(lctl.data(), nullptr, N, nullptr) != hipSuccess) return 8;
     for (int call = 0; call < n_calls; ++call) {
         int64_t lh[2];
         if (fread(lh, 8, 2, f) != 2) return 6;
@@ -51,20 +44,11 @@ int main(int argc, char **argv)
             ctl[(size_t) 2 * N + c] = (uint32_t) seen[c];
             ctl[(size_t) 5 * N + c] = (uint32_t) (seen[c] >> 32);
         }
-        for (int b = 0; b < (N + 63) / 64; ++b) {
-            blockIdx.x = b;
-            std::barrier<> bb(64), w0(64);
-            g_block_barrier = &bb;
-            g_wave_barrier[0] = &w0;
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < 64; ++t)
-                th.emplace_back([&, t] {
-                    threadIdx.x = t;
-                    hdlc_long_kernel(segbits.data(), segcnt.data(), ctl.data(), lctl.data(), open.data(), counters.data(),
-                                     frames.data(), count, cap, N, n_seg, seg_words, (int) lh[0], (long long) lh[1]);
-                });
-            for (auto &t : th) t.join();
-        }
+        LongLaunch a;
+        a.segbits = segbits.data(); a.segcnt = segcnt.data(); a.ctl = ctl.data(); a.lctl = lctl.data(); a.open = open.data();
+        a.counters = counters.data(); a.frames = frames.data(); a.frame_count = count; a.frame_cap = cap;
+        a.N = N; a.n_seg = n_seg; a.seg_words = seg_words; a.len = (int) lh[0]; a.n0 = lh[1];
+        if (launch_hdlc_long(a, nullptr) != hipSuccess) return 9;
         fwrite(lctl.data(), 4, lctl.size(), g);
     }
     fwrite(counters.data(), 4, counters.size(), g);

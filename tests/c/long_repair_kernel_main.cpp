@@ -1,43 +1,21 @@
 // long_repair_kernel_main.cpp -- TEST INFRASTRUCTURE: hdlc_long.hip's kernel in its form that keeps the raw bits and
-// hdlc_long_repair.hip's kernel, their own text, on the CPU (tests/test_long_repair_cpu.py builds it under ASan + UBSan
-// with tests/c/hip_wave_shim in front of the HIP headers): a std::thread per lane, one block of 64 at a time.  Every
+// hdlc_long_repair.hip's kernel, their own text, on the CPU, run through their launch functions
+// (tests/test_long_repair_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu in front of the HIP headers).  Every
 // buffer has exactly the size the launch interface promises (kernels.h: LongLaunch, LongRepairLaunch).  Per call: the
 // chain's deframer's count moves on (as in long_kernel_main.cpp), D' runs over the packs, then the repair over what D'
-// listed, on `blocks` workgroups; the two candidate counters are used by call parity as the library uses them.
+// listed, on LongRepairLaunch::blocks = `blocks` workgroups; the two candidate counters are used by call parity as the
+// library uses them.
 // argv: in out.  in: int64 N, n_seg, seg_words, frame_cap, n_calls, cand_cap, blocks; uint64 bits fed before the first
 // call [N]; then per call int64 len, n0, uint32 segbits [N][n_seg][16], uint32 segcnt [N][n_seg].
 // out: per call uint32 lctl [3][N], uint32 candidates listed; then int32 counters [3][N], uint32 frame_count [2], the
 // ring's records.
 #include <hip/hip_runtime.h>
-#include <thread>
+#include <algorithm>
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
-thread_local Idx threadIdx;
-Idx blockIdx, blockDim;
-std::barrier<> *g_block_barrier;
-std::barrier<> *g_wave_barrier[4];
-unsigned char g_pred[256];
-namespace gnuais { uint32_t long_pack[(16 + 1) * 64]; }
 #include "hdlc_long.hip"
-#undef __shared__
-#define __shared__ static       // the repair kernel's arrays are static shared memory: one per block, one block at a time
 #include "hdlc_long_repair.hip"
-
-template <class F> static void run_block(unsigned b, F f)
-{
-    blockIdx.x = b;
-    std::barrier<> bb(64), w0(64);
-    g_block_barrier = &bb;
-    g_wave_barrier[0] = &w0;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 64; ++t)
-        th.emplace_back([&, t] {
-            threadIdx.x = t;
-            f();
-        });
-    for (auto &t : th) t.join();
-}
 
 int main(int argc, char **argv)
 {
@@ -56,14 +34,13 @@ int main(int argc, char **argv)
     const int blocks = (int) hd[6];
     std::vector<uint64_t> seen(N);
     if (fread(seen.data(), 8, N, f) != (size_t) N) return 4;
-    std::vector<uint32_t> ctl((size_t) HDLC_CTL_WORDS * N, 0), lctl((size_t) LONG_CTL_WORDS * N, 0);
+    std::vector<uint32_t> ctl((size_t) HDLC_CTL_WORDS * N, 0), lctl((size_t) LONG_CTL_WORDS * N, 0xdeadbeefu);
     std::vector<uint32_t> open((size_t) LONG_REC_WORDS * N, 0xdeadbeefu), clean((size_t) LONG_REC_WORDS * N, 0xdeadbeefu);
     std::vector<uint32_t> frames((size_t) cap * LONG_FRAME_WORDS, 0xdeadbeefu), cand((size_t) cand_cap * LONG_CAND_WORDS, 0xdeadbeefu);
-    std::vector<int32_t> counters((size_t) 3 * N, 0);
+    std::vector<int32_t> counters((size_t) 3 * N, -1);
     uint32_t count[2] = {0, 0}, cand_count[2] = {0, 0};
     int parity = 0;
-    for (int c = 0; c < N; ++c) lctl[c] = 1;     // ST_SKURR: what launch_hdlc_long_reset() leaves
-    blockDim.x = 64;
+    if (launch_hdlc_long_reset(lctl.data(), counters.data(), N, nullptr) != hipSuccess) return 9;
     for (int call = 0; call < n_calls; ++call) {
         int64_t lh[2];
         if (fread(lh, 8, 2, f) != 2) return 6;
@@ -76,17 +53,17 @@ int main(int argc, char **argv)
             ctl[(size_t) 5 * N + c] = (uint32_t) (seen[c] >> 32);
         }
         if (cand_count[parity] != 0) return 8;  // the call before cleared this call's counter
-        for (int b = 0; b < (N + 63) / 64; ++b)
-            run_block((unsigned) b, [&] {
-                hdlc_long_kernel<true>(segbits.data(), segcnt.data(), ctl.data(), lctl.data(), open.data(), counters.data(),
-                                       frames.data(), count, cap, N, n_seg, seg_words, (int) lh[0], (long long) lh[1],
-                                       clean.data(), cand.data(), cand_count, cand_cap, parity);
-            });
-        for (int b = 0; b < blocks; ++b)
-            run_block((unsigned) b, [&] {
-                hdlc_long_repair_kernel(cand.data(), cand_count + parity, cand_cap, counters.data() + (size_t) 2 * N,
-                                        frames.data(), count, cap, N, blocks);
-            });
+        LongLaunch a;
+        a.segbits = segbits.data(); a.segcnt = segcnt.data(); a.ctl = ctl.data(); a.lctl = lctl.data(); a.open = open.data();
+        a.counters = counters.data(); a.frames = frames.data(); a.frame_count = count; a.frame_cap = cap;
+        a.N = N; a.n_seg = n_seg; a.seg_words = seg_words; a.len = (int) lh[0]; a.n0 = lh[1];
+        a.clean = clean.data(); a.cand = cand.data(); a.cand_count = cand_count; a.cand_cap = cand_cap; a.parity = parity;
+        if (launch_hdlc_long(a, nullptr) != hipSuccess) return 10;
+        LongRepairLaunch r;
+        r.cand = cand.data(); r.cand_count = cand_count + parity; r.cand_cap = cand_cap;
+        r.repaired = counters.data() + (size_t) 2 * N; r.frames = frames.data(); r.frame_count = count; r.frame_cap = cap;
+        r.N = N; r.blocks = blocks;
+        if (launch_hdlc_long_repair(r, nullptr) != hipSuccess) return 11;
         fwrite(lctl.data(), 4, lctl.size(), g);
         fwrite(cand_count + parity, 4, 1, g);
         parity ^= 1;

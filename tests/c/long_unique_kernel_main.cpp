@@ -1,5 +1,5 @@
 // long_unique_kernel_main.cpp -- TEST INFRASTRUCTURE: frame_unique.hip's own text on the CPU, over the long frames
-// (tests/test_long_unique_cpu.py builds it under ASan + UBSan with tests/c/hip_serial_shim in front of the HIP and rocPRIM
+// (tests/test_long_unique_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu (serial mode) in front of the HIP and rocPRIM
 // headers: the kernels have no barrier, no LDS and no cross-lane operation, so a launch is a loop over lanes), driven as
 // gnuais_batch_drain_long_frames_unique / _heard drive it: the hashed attempt, the exact one when the collision word is
 // set, the deliver step behind the kept attempt only, the double-buffered tail.  Drains with and without the lists
@@ -11,9 +11,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-Idx threadIdx, blockIdx, gridDim;
 #include "../../include/gnuais_hip.h"
-#include UNIQUE_KERNEL_TEXT
+#include "frame_unique.hip"
 using namespace gnuais;
 static int bits_of(unsigned long long v) { int n = 1; while (v >> n) ++n; return n; }
 // a buffer of exactly `bytes` bytes, 8-byte aligned as the interface asks (ASan sees the first byte behind it)

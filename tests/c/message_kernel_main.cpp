@@ -1,6 +1,5 @@
 // message_kernel_main.cpp -- TEST INFRASTRUCTURE: nmea_device.hip's own text on the CPU (tests/test_message_kernel_cpu.py
-// builds it under ASan + UBSan with tests/c/hip_launch_shim in front of the HIP headers).  MESSAGE_KERNEL_TEXT is a copy of
-// nmea_device.hip whose two dynamic shared arrays are ordinary declarations of the arrays below.
+// builds it under ASan + UBSan with tests/c/hip_cpu in front of the HIP and rocPRIM headers).
 //   argv: frames in out   the launch interface as the drain drives it, every buffer of exactly the size it asks for.
 //         in:  int32 groups; per group int32 n, u8 seq_in[8], char chanid[8], n records.
 //         out: per group u32 totals[4], the sentences, u8 seq_out[8], u32 info2[2], the lines, u32 vessels, the table.
@@ -10,19 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-thread_local Idx threadIdx, blockIdx;
-Idx gridDim;
-std::barrier<> *g_block_barrier;
-std::vector<size_t> g_dynamic_lds;
-namespace gnuais { namespace {
-alignas(16) char nmea_write_dyn[256 * 164 + 32 + 256 * 17 * 4];
-alignas(16) char message_pack_dyn[64 * 512 + 32];
-} }
-#include MESSAGE_KERNEL_TEXT
-namespace gnuais { namespace {
-static_assert(sizeof nmea_write_dyn == NMEA_WRITE_LDS_BYTES, "the array is what the launch asks for");
-static_assert(sizeof message_pack_dyn == PACK_FRAMES * MSG_LINE_MAX + 32, "the array is what the launch asks for");
-} }
+#include "nmea_device.hip"
 // frame_time.hip's, behind frames_sort_timed(..., times != nullptr), which this program never calls
 hipError_t gnuais::launch_frame_times_gather(const int64_t *, const uint32_t *, int, int64_t *, hipStream_t) { abort(); }
 using namespace gnuais;
@@ -53,15 +40,10 @@ static int run_frames(const char *in, const char *out)
         uint8_t *seq_out = exact<uint8_t>(N_CH);
         memcpy(seq_out, seq_in, N_CH);
         uint32_t totals[4] = {9, 9, 9, 9};
-        g_dynamic_lds.clear();
         if (nmea_format_enqueue(frames, n, n, N_CH, seq_in, seq_out, nmea, nmea_cap, scratch, scratch_bytes, totals, nullptr, 0, 0,
                                 nullptr, nullptr) != hipSuccess) return 5;
         if (messages_format_enqueue(frames, n, N_CH, seq_in, chanid, scratch, scratch_bytes, lines, len, off, text, text_cap, info2,
                                     nullptr) != hipSuccess) return 6;
-        size_t dyn[2] = {0, 0};
-        for (size_t d : g_dynamic_lds)
-            if (d) { if (dyn[1]) return 7; dyn[dyn[0] ? 1 : 0] = d; }
-        if (dyn[0] != sizeof nmea_write_dyn || dyn[1] != sizeof message_pack_dyn) return 7;
         if (totals[3] || (size_t) totals[0] + totals[1] > nmea_cap || info2[0] > text_cap) return 8;
         fwrite(totals, 4, 4, g);
         fwrite(nmea, 1, (size_t) totals[0] + totals[1], g);

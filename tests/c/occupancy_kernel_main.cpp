@@ -1,44 +1,16 @@
 // occupancy_kernel_main.cpp -- TEST INFRASTRUCTURE: the three kernels of occupancy.hip, their own text, on the CPU
-// (tests/test_occupancy_cpu.py builds it under ASan + UBSan with tests/c/hip_grid_shim in front of the HIP headers): a
-// std::thread per lane, one block at a time.  OCC_KERNEL_TEXT is a copy of occupancy.hip whose dynamic shared array is an
-// ordinary declaration.  Every buffer has exactly the size its launch is given.
+// (tests/test_occupancy_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu in front of the HIP headers).  Every
+// buffer has exactly the size its launch is given.  The finaliser runs through launch_occ_epoch().  The code and cover
+// kernels are launched on grids smaller than the library's, which makes their grid-stride loops turn; for the first epoch
+// launch_occ_code() and launch_occ_cover() run as well, on copies of the same input, and must leave the same bytes.
 // argv: in out.  in: int64 N, E, margin, CB, n_epochs, n_frames, pllinc, n_taps, W, v0; P int64 [n_epochs * E][N]; frames
 // int64 [n_frames][3] = channel, nbits, t.  The epochs are made final one by one, each by the shortest call that does so.
 // out, per epoch: the records [N], the tap words [E][N], the carried busy bytes [N].
 #include <hip/hip_runtime.h>
-#include <thread>
 #include <vector>
-#include <functional>
 #include <cstdio>
 #include <cstdlib>
-thread_local Idx threadIdx;
-Idx blockIdx, gridDim;
-std::barrier<> *g_block_barrier;
-std::barrier<> *g_wave_barrier[4];
-unsigned char g_pred[256];
-constexpr int LDS_WORDS = 288 * 32 + 256 + 64 + 3 * 256;
-namespace gnuais { namespace { uint32_t occ_lds[LDS_WORDS]; } }
-#include OCC_KERNEL_TEXT
-static_assert(LDS_WORDS == gnuais::OCC_LDS_WORDS, "the finaliser's launch size");
-
-// `blocks` blocks of 256 threads, one block at a time
-static void run_grid(unsigned blocks, const std::function<void()> &kernel)
-{
-    gridDim.x = blocks;
-    for (unsigned b = 0; b < blocks; ++b) {
-        blockIdx.x = b;
-        std::barrier<> bb(256), w0(64), w1(64), w2(64), w3(64);
-        g_block_barrier = &bb;
-        g_wave_barrier[0] = &w0; g_wave_barrier[1] = &w1; g_wave_barrier[2] = &w2; g_wave_barrier[3] = &w3;
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < 256; ++t)
-            th.emplace_back([&, t] {
-                threadIdx.x = t;
-                kernel();
-            });
-        for (auto &t : th) t.join();
-    }
-}
+#include "occupancy.hip"
 
 int main(int argc, char **argv)
 {
@@ -62,7 +34,7 @@ int main(int argc, char **argv)
     std::vector<uint8_t> cover((size_t) CB * N, 0), carry((size_t) N, 0xaa);
     std::vector<uint2> out((size_t) N);
     std::vector<uint32_t> frames((size_t) n_frames * 16, 0xdeadbeef), count(4, 0);
-    std::vector<long long> times((size_t) n_frames);
+    std::vector<int64_t> times((size_t) n_frames);
     for (int i = 0; i < n_frames; ++i) {
         frames[(size_t) i * 16] = (uint32_t) fr[(size_t) i * 3];
         frames[(size_t) i * 16 + 15] = (uint32_t) fr[(size_t) i * 3 + 1] << 16 | 0xbeefu;
@@ -79,15 +51,29 @@ int main(int argc, char **argv)
         for (int i = 0; i < E; ++i)
             for (int c = 0; c < N; ++c)
                 sums[((size_t) ((first + i) % RB) * N + c) * 3] = P[((size_t) k * E + i) * N + c];
+        std::vector<uint16_t> codes_lib(codes);
+        std::vector<uint8_t> cover_lib(cover);
         const int n_groups = (N + 255) / 256, stride = 3;
-        run_grid((unsigned) (n_groups * stride),
-                 [&] { occ_code_kernel(sums.data(), RB, codes.data(), CB, N, first, E, n_groups, stride); });
-        run_grid(2, [&] {
-            occ_cover_kernel(frames.data(), count.data(), (uint32_t) n_frames, times.data(), cover.data(), CB, N, n0,
-                             (int) (end - n0), pllinc, n_taps, W, v0, b0);
-        });
-        run_grid((unsigned) ((N + 63) / 64),
-                 [&] { occ_epoch_kernel(codes.data(), cover.data(), carry.data(), out.data(), CB, N, E, margin, first, k == 0); });
+        hipLaunchKernelGGL(occ_code_kernel, dim3((unsigned) (n_groups * stride)), dim3(OCC_THREADS), 0, nullptr, sums.data(), RB,
+                           codes.data(), CB, N, first, E, n_groups, stride);
+        OccCoverLaunch a;
+        a.frames = frames.data(); a.frame_count = count.data(); a.frame_cap = (uint32_t) n_frames; a.times = times.data();
+        a.cover = cover.data(); a.CB = CB; a.N = N; a.len = (int) (end - n0); a.n0 = n0; a.pllinc = pllinc; a.n_taps = n_taps;
+        a.afc_window = W; a.v0 = v0; a.b0 = b0;
+        hipLaunchKernelGGL(occ_cover_kernel, dim3(2), dim3(OCC_THREADS), 0, nullptr, (const uint32_t *) a.frames, a.frame_count,
+                           a.frame_cap, (const long long *) a.times, a.cover, a.CB, a.N, (long long) a.n0, a.len, a.pllinc,
+                           a.n_taps, a.afc_window, (long long) a.v0, (long long) a.b0);
+        if (k == 0) {
+            a.cover = cover_lib.data();
+            if (launch_occ_code(sums.data(), RB, codes_lib.data(), CB, N, first, E, nullptr) != hipSuccess ||
+                launch_occ_cover(a, nullptr) != hipSuccess)
+                return 6;
+            if (codes_lib != codes || cover_lib != cover) return 7;
+        }
+        OccEpochLaunch e;
+        e.codes = codes.data(); e.cover = cover.data(); e.carry = carry.data(); e.out = out.data();
+        e.CB = CB; e.N = N; e.E = E; e.margin = margin; e.first = first; e.first_epoch = k == 0;
+        if (launch_occ_epoch(e, nullptr) != hipSuccess) return 8;
         fwrite(out.data(), 8, (size_t) N, g);
         for (int i = 0; i < E; ++i) fwrite(codes.data() + (size_t) ((first + i) % CB) * N, 2, (size_t) N, g);
         fwrite(carry.data(), 1, (size_t) N, g);

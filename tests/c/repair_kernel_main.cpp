@@ -1,20 +1,12 @@
-// repair_kernel_main.cpp -- TEST INFRASTRUCTURE: hdlc_repair_kernel's own text on the CPU (tests/test_repair_cpu.py builds
-// it under ASan + UBSan with tests/c/hip_block_shim in front of the HIP headers): a std::thread per lane, one block at a
-// time.  REPAIR_KERNEL_TEXT is a copy of hdlc_repair.hip whose dynamic shared array is an ordinary declaration.
+// repair_kernel_main.cpp -- TEST INFRASTRUCTURE: hdlc_repair.hip's own text on the CPU, run through launch_hdlc_repair()
+// (tests/test_repair_cpu.py builds it under ASan + UBSan with tests/c/hip_cpu in front of the HIP headers).
 // argv: in out.  in: int32 N, K, frame_cap; cand [N][K][20] u32; cand_first [N]; cand_count [N].
 // out: the ring's four counters, repaired [N], the ring's records.
 #include <hip/hip_runtime.h>
-#include <thread>
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
-thread_local Idx threadIdx;
-Idx blockIdx;
-std::barrier<> *g_block_barrier;
-std::barrier<> *g_wave_barrier[4];
-unsigned char g_pred[256];
-namespace gnuais { namespace { uint32_t rp_rows[256 * 21]; } }
-#include REPAIR_KERNEL_TEXT
+#include "hdlc_repair.hip"
 int main(int argc, char **argv)
 {
     FILE *f = fopen(argv[1], "rb");
@@ -26,21 +18,10 @@ int main(int argc, char **argv)
     fclose(f);
     std::vector<int32_t> repaired(N, 0);
     uint32_t flags[4] = {0, 0, 0, 0};
-    const int blocks = (N + 31) / 32;
-    for (int b = 0; b < blocks; ++b) {
-        blockIdx.x = b;
-        std::barrier<> bb(256), w0(64), w1(64), w2(64), w3(64);
-        g_block_barrier = &bb;
-        g_wave_barrier[0] = &w0; g_wave_barrier[1] = &w1; g_wave_barrier[2] = &w2; g_wave_barrier[3] = &w3;
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < 256; ++t)
-            th.emplace_back([&, t] {
-                threadIdx.x = t;
-                gnuais::hdlc_repair_kernel(cand.data(), first.data(), count.data(), repaired.data(), frames.data(), flags,
-                                           (uint32_t) cap, N, K);
-            });
-        for (auto &t : th) t.join();
-    }
+    gnuais::RepairLaunch a;
+    a.cand = cand.data(); a.cand_first = first.data(); a.cand_count = count.data(); a.repaired = repaired.data();
+    a.frames = frames.data(); a.frame_count = flags; a.frame_cap = (uint32_t) cap; a.N = N; a.K = K;
+    if (gnuais::launch_hdlc_repair(a, nullptr) != hipSuccess) return 4;
     FILE *g = fopen(argv[2], "wb");
     fwrite(flags, 4, 4, g);
     fwrite(repaired.data(), 4, N, g);

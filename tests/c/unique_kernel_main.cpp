@@ -1,5 +1,5 @@
 // unique_kernel_main.cpp -- TEST INFRASTRUCTURE: frame_unique.hip's own text on the CPU (tests/test_unique_cpu.py builds it
-// under ASan + UBSan with tests/c/hip_serial_shim in front of the HIP and rocPRIM headers), driven as
+// under ASan + UBSan with tests/c/hip_cpu (serial mode) in front of the HIP and rocPRIM headers), driven as
 // gnuais_batch_drain_frames_unique drives it: the hashed attempt, the exact one when the collision word is set, the
 // double-buffered tail.  Every buffer is allocated at exactly the size the launch interface asks for.
 // argv: in out hash_bits.  in: int32 W, int32 drains, per drain int32 n, int64 rows, n records, n times.
@@ -8,9 +8,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-Idx threadIdx, blockIdx, gridDim;
 #include "../../include/gnuais_hip.h"
-#include UNIQUE_KERNEL_TEXT
+#include "frame_unique.hip"
 using namespace gnuais;
 static int bits_of(unsigned long long v) { int n = 1; while (v >> n) ++n; return n; }
 int main(int argc, char **argv)

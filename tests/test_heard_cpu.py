@@ -1,7 +1,7 @@
 """Who heard each transmission on the CPU: the host object's gnuais_uniq_push_heard (frame_unique.cpp) against the plain
 restatement tests/heard_ref.py over the random record sets of test_unique_cpu.py -- whole and cut into drains, push and
 push_heard alternating on one object -- with the invariants of the definition; its edges; the unit by itself under
-ASan + UBSan; the kernels' own text behind tests/c/hip_serial_shim; and the new names of the ABI."""
+ASan + UBSan; the kernels' own text behind tests/c/hip_cpu; and the new names of the ABI."""
 import os
 import subprocess
 
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import heard_ref as hr
+import hip_cpu_build
 import unique_ref as ur
 from oracle_lib import FRAME_DTYPE
 from test_unique_cpu import cut_into_drains, random_set
@@ -218,16 +219,12 @@ def test_host_unit_standalone_under_asan_and_ubsan(tmp_path, L, with_signal):
 
 @pytest.mark.parametrize("hash_bits", [64, 3, 1])
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path, L, hash_bits):
-    """frame_unique.hip compiled for the CPU behind tests/c/hip_serial_shim under ASan + UBSan, driven by
+    """frame_unique.hip compiled for the CPU behind tests/c/hip_cpu's serial mode under ASan + UBSan, driven by
     tests/c/heard_kernel_main.cpp as the heard drain drives it, every buffer at exactly the size the launch interface
     asks for: records, times, copies, offsets, members and the late count are the restatement's -- with the full hash
     without ever taking the exact path, with 3 and 1 bits through it -- and drains without lists in between leave the
     same state.  Run as a program; nothing is loaded into Python."""
-    exe = str(tmp_path / "heard_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "tests", "c", "hip_serial_shim"),
-                           "-I", CSRC, f'-DUNIQUE_KERNEL_TEXT="{os.path.join(CSRC, "frame_unique.hip")}"',
-                           os.path.join(ROOT, "tests", "c", "heard_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("heard_kernel_main.cpp", tmp_path / "heard_kernel.bin", "-DHIP_CPU_SERIAL")
     cases = make_cases(80, L)
     src, dst = str(tmp_path / "sets.in"), str(tmp_path / "sets.out")
     with_signal = hash_bits != 3

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import deframer_cases as dc
+import hip_cpu_build
 import long_ref as lr
 import repair_ref as rr
 from gnuais_amd import synth
@@ -122,13 +123,10 @@ def fields_of(word0):
 
 
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path):
-    """hdlc_long.hip compiled for the CPU behind tests/c/hip_wave_shim (a thread per lane, a block of 64 at a time) under
-    ASan + UBSan: the bit packs of 70 channels over three calls that cut the bursts -- the middle call a single bit --
+    """hdlc_long.hip compiled for the CPU behind tests/c/hip_cpu (a thread per lane, a block of 64 at a time) under ASan +
+    UBSan and run through launch_hdlc_long_reset() and launch_hdlc_long(): the bit packs of 70 channels over three calls that cut the bursts -- the middle call a single bit --
     with stamps above 2^32: records, counters and the carried state after every call are the restatement's."""
-    exe = str(tmp_path / "long_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-I", os.path.join(ROOT, "tests", "c", "hip_wave_shim"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "c", "long_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("long_kernel_main.cpp", tmp_path / "long_kernel.bin")
     N, n_seg, seg_words, cap = 70, 16, 15, 512
     rng = np.random.default_rng(31)
     streams = [lr.channel_bits(rng, c) for c in range(N)]

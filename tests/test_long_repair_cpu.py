@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import hip_cpu_build
 import long_ref as lr
 import long_repair_ref as lrr
 import repair_ref as rr
@@ -293,13 +294,11 @@ def test_long_repair_candidate_standalone_under_asan_and_ubsan(L, tmp_path):
 # ---- both kernels' own text on the CPU --------------------------------------------------------------------------------
 def test_both_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path):
     """hdlc_long.hip in its form that keeps the raw bits and hdlc_long_repair.hip compiled for the CPU behind
-    tests/c/hip_wave_shim (a thread per lane, a block of 64 at a time) under ASan + UBSan: 70 channels over three calls
-    that cut the bursts, so candidates straddle calls, with stamps above 2^32 and the repair on three workgroups: records,
-    the three counters and the carried state after every call are the restatement's."""
-    exe = str(tmp_path / "long_repair_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-I", os.path.join(ROOT, "tests", "c", "hip_wave_shim"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "c", "long_repair_kernel_main.cpp"), "-o", exe])
+    tests/c/hip_cpu (a thread per lane, a block of 64 at a time) under ASan + UBSan and run through their launch
+    functions: 70 channels over three calls that cut the bursts, so candidates straddle calls, with stamps above 2^32 and
+    the repair on three workgroups: records, the three counters and the carried state after every call are the
+    restatement's."""
+    exe = hip_cpu_build.build("long_repair_kernel_main.cpp", tmp_path / "long_repair_kernel.bin")
     N, n_seg, seg_words, cap, cand_cap, blocks = 70, 16, 15, 512, 512, 3
     rng = np.random.default_rng(32)
     streams = [lrr.damaged_channel_bits(rng, c) for c in range(N)]

@@ -1,7 +1,7 @@
 """Each long transmission once, on the CPU: the host object gnuais_long_uniq (frame_unique.cpp over LongRec) against the
 restatement tests/long_unique_ref.py over random record sets cut into drains, with the lists and the invariants of the
 definition; the unit by itself under ASan + UBSan; the device stage's own text (frame_unique.hip over LongDev) behind
-the serial shim under ASan + UBSan with the full and with a truncated hash; on the oracle, the property the tail rule
+tests/c/hip_cpu under ASan + UBSan with the full and with a truncated hash; on the oracle, the property the tail rule
 rests on and that the GPU tests' input really merges; and the header, the exports and the build's resource check."""
 import collections
 import os
@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import hip_cpu_build
 import long_unique_ref as lur
 import unique_ref as ur
 from gnuais_amd.lib import HEARER_DTYPE, LONG_FRAME_DTYPE
@@ -226,17 +227,13 @@ def test_host_unit_standalone_under_asan_and_ubsan(tmp_path):
 
 @pytest.fixture(scope="module")
 def kernel_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("luq") / "long_unique_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "tests", "c", "hip_serial_shim"),
-                           "-I", CSRC, f'-DUNIQUE_KERNEL_TEXT="{os.path.join(CSRC, "frame_unique.hip")}"',
-                           os.path.join(ROOT, "tests", "c", "long_unique_kernel_main.cpp"), "-o", exe])
-    return exe
+    return hip_cpu_build.build("long_unique_kernel_main.cpp", tmp_path_factory.mktemp("luq") / "long_unique_kernel.bin",
+                               "-DHIP_CPU_SERIAL")
 
 
 @pytest.mark.parametrize("hash_bits", [64, 3, 1])
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path, kernel_exe, hash_bits):
-    """frame_unique.hip compiled for the CPU behind tests/c/hip_serial_shim under ASan + UBSan, driven as the drain
+    """frame_unique.hip compiled for the CPU behind tests/c/hip_cpu's serial mode under ASan + UBSan, driven as the drain
     drives it with buffers of exactly the sizes the interface asks for, drains with and without the lists alternating: the
     records, copies, lists and the late count are the restatement's -- with the full hash without ever taking the exact
     path, with 3 and 1 bits through it in more than 100 drains"""

@@ -1,5 +1,5 @@
-"""nmea_device.hip's own text on the CPU: compiled by g++ behind tests/c/hip_launch_shim (a thread per lane, the blocks of a
-launch one after the other, rocPRIM's sort and scans stood in for) under ASan + UBSan, as a stand-alone program
+"""nmea_device.hip's own text on the CPU: compiled by g++ behind tests/c/hip_cpu (a thread per lane, the blocks of a launch
+one after the other, rocPRIM's sort and scans stood in for) under ASan + UBSan, as a stand-alone program
 (tests/c/message_kernel_main.cpp).  The kernels' control flow, their bounds and the hand-written printf("%.Nf") of
 LineOut::fixed cannot be checked on a device by the CPU suite; this is that check.  The chunk-table path and the carried
 vessel table stay with their GPU tests."""
@@ -10,41 +10,20 @@ import time
 import numpy as np
 import pytest
 
+import hip_cpu_build
 import message_cases as mc
 from gnuais_amd.receiver import VESSEL_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gnuais_amd", "csrc")
-SHARED = (("extern __shared__ __attribute__((aligned(16))) char nmea_write_dyn[];", "extern char nmea_write_dyn[];"),
-          ("extern __shared__ __attribute__((aligned(16))) char message_pack_dyn[];", "extern char message_pack_dyn[];"))
 SEQ_IN = np.array([3, 9, 0, 7, 1, 8, 5, 2], dtype=np.uint8)
 CHANID = b"ABXYZQRS"
 SWEEP_STRIDE = 31
 COMPARED = 38290985             # what the program counts at that stride
 
 
-def build_harness(tmp, text):
-    """`text`: the kernel file's text.  Its two dynamic shared arrays become declarations of the program's own arrays,
-    which have exactly the size the launches ask for."""
-    for old, new in SHARED:
-        assert text.count(old) == 1, old
-        text = text.replace(old, new + " " * (len(old) - len(new)))
-    inc = os.path.join(str(tmp), "kernel_text.inc")
-    with open(inc, "w") as f:
-        f.write(text)
-    exe = os.path.join(str(tmp), "message_kernel.bin")
-    shims = os.path.join(ROOT, "tests", "c")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-subobject-linkage",
-                           "-I", os.path.join(shims, "hip_launch_shim"), "-I", os.path.join(shims, "hip_serial_shim"),
-                           "-I", CSRC, f'-DMESSAGE_KERNEL_TEXT="{inc}"',
-                           os.path.join(shims, "message_kernel_main.cpp"), "-o", exe])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return build_harness(tmp_path_factory.mktemp("message_kernel"), open(os.path.join(CSRC, "nmea_device.hip")).read())
+    return hip_cpu_build.build("message_kernel_main.cpp", tmp_path_factory.mktemp("message_kernel") / "message_kernel.bin",
+                               "-Wno-unused-function", "-Wno-subobject-linkage", "-Wno-ignored-attributes")
 
 
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")

@@ -10,12 +10,11 @@ import numpy as np
 import pytest
 
 import frame_time_ref as ftr
+import hip_cpu_build
 import iq_ref
 import occupancy_ref as orf
 from gnuais_amd import lib, params, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gnuais_amd", "csrc")
 E, MARGIN, SEEDS = 1024, 16, (4, 5, 6)
 N_ROWS = 64 * 2 * E + orf.lag(0x10000 // 5) + 64           # two epochs become final
 SETTINGS = [(10000.0, 800.0), (3000.0, 500.0), (10000.0, 1500.0)]
@@ -190,18 +189,12 @@ def test_collisions_show_as_busy_blocks_that_are_not_covered():
 
 
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path):
-    """occupancy.hip compiled for the CPU behind tests/c/hip_grid_shim (a thread per lane, a block at a time) under ASan +
-    UBSan, every buffer at exactly its launch size: six epochs of 64 blocks, which take the rings round more than three
+    """occupancy.hip compiled for the CPU behind tests/c/hip_cpu (a thread per lane, a block at a time) under ASan + UBSan,
+    every buffer at exactly its launch size, the finaliser through launch_occ_epoch(), the other two on small grids and,
+    once, through their launch functions with the same result: six epochs of 64 blocks, which take the rings round more than three
     times, 130 channels (three finaliser workgroups, the last one partly empty), v0 no multiple of 64, codes at both
     ends, ties at the rank, frames of every length whose spans begin before v0, lie across epochs and on one another."""
-    text = open(os.path.join(CSRC, "occupancy.hip")).read()
-    assert text.count("extern __shared__ uint32_t occ_lds[];") == 1
-    (tmp_path / "kernel_text.inc").write_text(text.replace("extern __shared__ uint32_t occ_lds[];", "extern uint32_t occ_lds[];"))
-    exe = str(tmp_path / "occupancy_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-I", os.path.join(ROOT, "tests", "c", "hip_grid_shim"), "-I", CSRC,
-                           f'-DOCC_KERNEL_TEXT="{tmp_path / "kernel_text.inc"}"',
-                           os.path.join(ROOT, "tests", "c", "occupancy_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("occupancy_kernel_main.cpp", tmp_path / "occupancy_kernel.bin")
     N, Ek, margin, n_ep, pllinc, n_taps, W, v0 = 130, 64, 5, 6, 0x10000 // 5, 36, 1024, 1000
     L = orf.lag(pllinc, n_taps, W)
     CB = Ek + -(-L // 64) + 2                               # the epoch, the rows it waits for, the open blocks

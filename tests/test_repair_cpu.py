@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import hip_cpu_build
 import repair_ref as rr
 from gnuais_amd import synth
 
@@ -313,20 +314,12 @@ def test_repair_candidate_standalone_under_asan_and_ubsan(L, tmp_path):
 
 
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path):
-    """hdlc_repair.hip compiled for the CPU behind tests/c/hip_block_shim (a thread per lane, a block at a time) under
-    ASan + UBSan: over the candidate ring of 40 noisy channels -- good, failed and abandoned records, ring slots that
+    """hdlc_repair.hip compiled for the CPU behind tests/c/hip_cpu (a thread per lane, a block at a time) under ASan +
+    UBSan and run through launch_hdlc_repair(): over the candidate ring of 40 noisy channels -- good, failed and abandoned records, ring slots that
     wrap, junk behind rawlen, stamps above 2^32, several passes per block -- the records it appends and its counters are
     the restatement's.  The kernel's control flow cannot be checked on a device by the CPU suite; this is that check."""
     from oracle_lib import FRAME_DTYPE, Oracle
-    text = open(os.path.join(CSRC, "hdlc_repair.hip")).read()
-    assert text.count("extern __shared__ uint32_t rp_rows[];") == 1
-    (tmp_path / "kernel_text.inc").write_text(text.replace("extern __shared__ uint32_t rp_rows[];",
-                                                           "extern uint32_t rp_rows[];"))
-    exe = str(tmp_path / "repair_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-I", os.path.join(ROOT, "tests", "c", "hip_block_shim"), "-I", CSRC,
-                           f'-DREPAIR_KERNEL_TEXT="{tmp_path / "kernel_text.inc"}"',
-                           os.path.join(ROOT, "tests", "c", "repair_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("repair_kernel_main.cpp", tmp_path / "repair_kernel.bin")
     N, K, rows = 40, 64, 36000
     x = np.stack([synth.make_stream(rows, seed=20, channel=c, amplitude=12000.0, sigma=6000.0, occupancy=0.5)[0]
                   for c in range(N)], axis=1)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import frame_time_ref as ftr
+import hip_cpu_build
 import unique_ref as ur
 from oracle_lib import FRAME_DTYPE
 
@@ -247,17 +248,13 @@ def write_cases(path, cases):
 
 @pytest.mark.parametrize("hash_bits", [64, 3, 1])
 def test_the_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path, hash_bits):
-    """frame_unique.hip compiled for the CPU behind tests/c/hip_serial_shim (its kernels have no barrier: a launch is a
-    loop over lanes; rocPRIM's sort and scan are stood in for by stable CPU ones) under ASan + UBSan, driven as the
+    """frame_unique.hip compiled for the CPU behind tests/c/hip_cpu's serial mode (its kernels have no barrier: a launch is
+    a loop over lanes; rocPRIM's sort and scan are stood in for by stable CPU ones) under ASan + UBSan, driven as the
     drain drives it with buffers of exactly the sizes the interface asks for: over random sets cut into drains the
     records, times, copies and the late count are the restatement's -- with the full hash without ever taking the exact
     path, with 3 and 1 bits through it.  The kernels' control flow and bounds cannot be checked on a device by the CPU
     suite; this is that check."""
-    exe = str(tmp_path / "unique_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "tests", "c", "hip_serial_shim"),
-                           "-I", CSRC, f'-DUNIQUE_KERNEL_TEXT="{os.path.join(CSRC, "frame_unique.hip")}"',
-                           os.path.join(ROOT, "tests", "c", "unique_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("unique_kernel_main.cpp", tmp_path / "unique_kernel.bin", "-DHIP_CPU_SERIAL")
     rng = np.random.default_rng(78)
     cases = []
     for _ in range(150):

@@ -15,6 +15,7 @@ import deframer_cases as dc
 import frame_signal_ref as fsr
 import frame_time_ref as ftr
 import heard_ref as hr
+import hip_cpu_build
 import iq_ref
 import occupancy_ref as orf
 import unique_ref as ur
@@ -22,8 +23,6 @@ import uptime_ref as up
 from gnuais_amd import lib, synth
 from oracle_lib import FRAME_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gnuais_amd", "csrc")
 N_CH, CALLS = 4, (5000, 5240, 5120)          # ragged segments: 2048 + 2048 + 904, 2048 + 2048 + 1144, 2048 + 2048 + 1024
 PLLINC = 0x10000 // 5
 SENTINEL = -7777
@@ -185,16 +184,13 @@ def run_call_case(R, B):
 
 
 def test_the_frame_time_kernels_own_text_on_the_cpu_equals_the_restatement(tmp_path):
-    """frame_time.hip compiled for the CPU behind tests/c/hip_grid_shim under ASan + UBSan, every buffer at exactly its
-    launch size.  Per case the ring, ctl and segcnt are built from FrameTimeRef: the fed count below 2^32; straddling it
+    """frame_time.hip compiled for the CPU behind tests/c/hip_cpu under ASan + UBSan and run through launch_frame_times(),
+    every buffer at exactly its launch size.  Per case the ring, ctl and segcnt are built from FrameTimeRef: the fed count below 2^32; straddling it
     (record stamped before the carry, ctl after it); exactly 2^32 and 2^32 - 1 after the call; straddling 2^37 (fed small,
     end_bit near 2^37) with and without high bits above the stamp's 37; n0 at every rows origin; stale records of an
     earlier call and a record of no channel, which are left alone; a ring that counted more than it holds; a grid
     smaller than the ring; and a decode_bits launch (len 0), which gives -1."""
-    exe = str(tmp_path / "frame_time_kernel.bin")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-pthread", "-I", os.path.join(ROOT, "tests", "c", "hip_grid_shim"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "c", "frame_time_kernel_main.cpp"), "-o", exe])
+    exe = hip_cpu_build.build("frame_time_kernel_main.cpp", tmp_path / "frame_time_kernel.bin")
     src, dst = tmp_path / "cases.bin", tmp_path / "times.bin"
     wants, names = [], []
     with open(src, "wb") as f:
